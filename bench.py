@@ -9,25 +9,29 @@ generated directly in HBM; one
 (canonicalise + MurmurHash3 + keep h <= max_hash), the device radix sort and the
 unique pass, leaving the sorted unique hash vector (the sketch) in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--records R] [--record-len L]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--records R] [--record-len L] [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver with torch.distributed.run.  Every rank sketches
 its own 1,000-record slice of the stream (weak scaling); value = (bases sketched by all
-ranks) / (max over ranks of the elapsed time).  After the timed region the ranks
-also run the two multi-GPU configurations of BASELINE.json through
+ranks) / (max over ranks of the elapsed time).  A plain run stops there: it prints the line
+with the headline figure and ms_per_step (roofline, cpu_baseline and summary null).
+--dump-outputs DIR writes the sketch of the last timed step (dump_outputs).
+
+With --full, after the timed region the ranks also exchange their sketches (one union
+all-gather) and run the two multi-GPU configurations of BASELINE.json through
 sourmash_amd.parallel (the same code at every N; N = 1 takes the same functions,
 SMG_BENCH_FORCE_COLLECTIVES=1 makes a single rank issue the collectives too):
     extra.compare_c4_dist   10,000 x 10,000 compare, row tiles dealt to the ranks, ONE all-gather
     extra.gather_c5_dist    10^6-hash query vs 100,000 sketches sharded 100,000 / N per rank,
                             one all-gather of candidate rows per batch of rounds
 
-Prints ONE JSON line of at most 8 KB on rank 0 (finalize_line) with the contract fields plus
+Prints ONE JSON line of at most 8 KB on rank 0 (finalize_line) with the contract fields plus, with --full,
   roofline:     HBM roofline of the dominant kernel (algorithmic bytes / measured kernel time)
   cpu_baseline: the oracle (CPU restatement of the reference algorithm) on bounded samples,
                 one thread and as many threads as this container may run (N = 1 only)
   summary:      the headline figure of every secondary metric
 The secondary metrics in full (`extra`, each with its own roofline object, ~25 KB) go to
-gpurun_out/bench_extra.json and to stderr as one `BENCH_EXTRA {...}` line (write_extras).
+EXTRA_FILE under the repository and to stderr as one `BENCH_EXTRA {...}` line (write_extras).
 """
 import argparse
 import json
@@ -86,7 +90,16 @@ def parse():
     ap.add_argument("--extras-timeout", type=float, default=900.0,
                     help="seconds the secondary metrics may take before the line is printed without the unfinished ones and every rank "
                          "leaves (a rank stuck in a collective cannot be interrupted any other way); 0 = no limit")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the sketch kernel's roofline, the CPU baseline, the "
+                         "union all-gather of N > 1 and the secondary metrics (compare / gather / API / protein / ksize / file ingest); "
+                         "without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the sketch the last step computed to DIR/<name>.npy (float64; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def main():
@@ -186,12 +199,16 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
 
+    # what the last timed step handed its caller, before anything below reuses the sketcher's buffers
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, hashes, np, "" if world == 1 else "_rank%d" % rank)
+
     # one exchange: every rank ends up with the sketch of the whole input (not in the timed region of
     # the per-step metric; it is one 10 MB all-gather per job, reported separately)
     n_unique_local = int(hashes.numel())
     gather_ms = None
-    n_unique_total = n_unique_local
-    if use_dist:
+    n_unique_total = n_unique_local if world == 1 else None     # N > 1: known after the exchange, which only --full runs
+    if use_dist and args.full:
         tg = time.perf_counter()
         n_unique_total = int(parallel.allgather_union(hashes, force=True).numel())
         torch.cuda.synchronize()
@@ -203,7 +220,7 @@ def main():
 
     # ---- roofline of the dominant kernel (sketch_dna_kernel): HIP events on the launch stream (rank 0) ----
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         cap = sk.cap
         raw = torch.empty(cap, dtype=torch.int64, device=dev)
         cnt = torch.zeros(2, dtype=torch.int64, device=dev)
@@ -231,7 +248,7 @@ def main():
 
     # ---- CPU baseline (rank 0, N = 1 only): the oracle on bounded samples of the same workloads ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, seq, n_bytes, sk, np)
 
     extra = {}
@@ -251,11 +268,12 @@ def main():
                        "bases_per_gpu": bases_per_step, "bytes_per_gpu": n_bytes, "ksize": args.ksize,
                        "scaled": args.scaled, "unique_hashes_rank0": n_unique_local,
                        "unique_hashes_job": n_unique_total, "allgather_ms": gather_ms,
-                       "collectives": coll(comm, "all-gather of the hash vectors (union)") + (" -- REHEARSAL: ranks share one GPU" if share_gpu else ""),
+                       "collectives": (coll(comm, "all-gather of the hash vectors (union)") if args.full else "none (the exchange runs with --full)")
+                                      + (" -- REHEARSAL: ranks share one GPU" if share_gpu else ""),
                        "comm": {k: v for k, v in comm.items() if k != "ranks"}},
             "roofline": roofline, "cpu_baseline": cpu,
-            "summary": extras_summary(extra),
-            "extra_file": EXTRA_FILE,
+            "summary": extras_summary(extra) if args.full else None,
+            "extra_file": EXTRA_FILE if args.full else None,
         }
 
     # The headline metric is measured; what follows are secondary metrics, some of them collectives among the ranks.  A rank stuck in
@@ -272,15 +290,18 @@ def main():
                 time.sleep(3.0)                              # the other ranks leave first: none of them sees a peer vanish
         finally:
             os._exit(0)
+    # a plain run (no --full) stops at the headline figure: none of the secondary metrics, no side file
+    run_extras = args.full and not args.no_compare
     watchdog = None
-    if args.extras_timeout > 0 and not args.no_compare:
+    if args.extras_timeout > 0 and run_extras:
         watchdog = threading.Timer(args.extras_timeout, give_up)
         watchdog.daemon = True
         watchdog.start()
 
     del seq, hashes                                          # 10 GB back before the matrices
-    torch.cuda.empty_cache()
-    be = parallel.DeviceBackend(dev)
+    if run_extras:
+        torch.cuda.empty_cache()
+        be = parallel.DeviceBackend(dev)
 
     def timed(fn, reps=5):
         fn()
@@ -294,7 +315,7 @@ def main():
         return e0.elapsed_time(e1) / reps
 
     # ---- BASELINE configs C4 / C5 through the multi-GPU drivers (every rank; same code at N = 1) ----
-    if not args.no_compare:
+    if run_extras:
         try:
             extra["compare_c4_dist"] = bench_compare_dist(torch, dist, np, dev, be, parallel, smd, synth_sketches, world, rank,
                                                           use_dist, barrier, max_over_ranks, comm)
@@ -309,7 +330,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- XL configurations for the scaling curve (every rank): C4 / C5 are over in milliseconds on one GPU ----
-    if not args.no_compare and not args.no_xl:
+    if run_extras and not args.no_xl:
         from sourmash_amd.synth import synth_sketches_device
         try:
             extra["compare_xl_dist"] = bench_compare_xl_dist(torch, dev, be, parallel, synth_sketches_device, world, rank, use_dist,
@@ -325,7 +346,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- single-GPU secondary metrics (N = 1): config C3 and the kernels behind C4 / C5 one by one ----
-    if rank == 0 and world == 1 and not args.no_compare:
+    if rank == 0 and world == 1 and run_extras:
         try:
             single_gpu_extras(extra, torch, np, dev, be, smd, synth_sketches, synth_gather, synth_gather_device, timed)
         except Exception as e:
@@ -333,7 +354,7 @@ def main():
 
     # ---- the reference-shaped entry points (lists of signature objects in, numpy matrices / result lists out) and the protein
     #      sketch kernels, N = 1 ----
-    if rank == 0 and world == 1 and not args.no_compare:
+    if rank == 0 and world == 1 and run_extras:
         try:
             api_extras(extra, torch, np, dev, smd, synth_sketches, synth_gather_device)
         except Exception as e:
@@ -349,17 +370,17 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- the steps either side of the kernels, on this box (N = 1): file ingest and bulk signature loading ----
-    if rank == 0 and world == 1 and not args.no_compare and not args.no_io:
+    if rank == 0 and world == 1 and run_extras and not args.no_io:
         try:
             io_extras(extra, torch, np, dev, smd)
         except Exception as e:
             extra["io_error"] = repr(e)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         extra["arena"] = {**smd.arena_stats(), "what": "the library's device arena (csrc/arena.hpp) over the whole run: driver "
                           "allocator calls, nanoseconds inside them, allocations served from cached blocks"}
     out = build_line() if rank == 0 else None
-    if rank == 0:
+    if rank == 0 and args.full:
         write_extras(extra, comm)
     if use_dist:
         dist.barrier()
@@ -377,6 +398,35 @@ def main():
     os.close(real_stdout)
     if out is not None:
         print(finalize_line(out), flush=True)
+
+
+DUMP_SAMPLE = 1 << 21      # positions of the sketch kept by dump_outputs: three float64 arrays of 2^21 = 48 MiB at most
+
+
+def dump_outputs(out_dir, hashes, np, suffix=""):
+    """The sorted unique hash vector (u64) the last timed step left, as float64 .npy files that hold it exactly:
+      sketch_size<suffix>.npy            [1]  its length
+      sketch_limb16_sums<suffix>.npy     [4]  the sum over the WHOLE vector of each 16-bit limb, low limb first (exact below 2^37 hashes)
+      sketch_sample_index<suffix>.npy    [m]  a fixed, seeded sample of m = min(length, DUMP_SAMPLE) positions, ascending
+      sketch_sample_hi32<suffix>.npy     [m]  the upper 32 bits of the hashes at those positions
+      sketch_sample_lo32<suffix>.npy     [m]  the lower 32 bits
+    The input is seeded, so two builds that compute the same sketch write the same files."""
+    h = hashes.cpu().numpy().view(np.uint64)
+    n = int(h.size)
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(42).choice(n, DUMP_SAMPLE, replace=False))
+    else:
+        idx = np.arange(n)
+    s = h[idx]
+    limbs = [int(((h >> np.uint64(16 * i)) & np.uint64(0xFFFF)).sum(dtype=np.uint64)) for i in range(4)]
+    arrays = {"sketch_size": np.array([n], dtype=np.float64),
+              "sketch_limb16_sums": np.array(limbs, dtype=np.float64),
+              "sketch_sample_index": idx.astype(np.float64),
+              "sketch_sample_hi32": (s >> np.uint64(32)).astype(np.float64),
+              "sketch_sample_lo32": (s & np.uint64(0xFFFFFFFF)).astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 LINE_LIMIT = 8000          # bytes of the stdout line: logs keep about 8 KB of tail, and a line that does not parse is no measurement (VERDICT r05)

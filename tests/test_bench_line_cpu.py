@@ -97,3 +97,35 @@ def test_default_workload_is_the_literal_c2(bench, monkeypatch):
     args = bench.parse()
     assert args.records == 1000 and args.record_len == 10_000_000 and not args.bases
     assert args.records * (args.record_len + 1) == 10_000_001_000
+
+
+def test_a_plain_run_leaves_the_secondary_metrics_to_full(bench, monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert not args.full and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = bench.parse()
+    assert args.full and args.dump_outputs == "out"
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+@pytest.mark.parametrize("n", [0, 5, 3_000_000])
+def test_dumped_outputs_hold_the_sketch_exactly(bench, tmp_path, n):
+    "float64 files only, at most 64 MB, the sampled hashes bit for bit and the limb sums over the whole vector"
+    np = pytest.importorskip("numpy")
+    torch = pytest.importorskip("torch")
+    h = np.unique(np.random.default_rng(n).integers(0, 2**64 // 1000, n, dtype=np.uint64))
+    bench.dump_outputs(str(tmp_path), torch.from_numpy(h.view(np.int64)), np)
+    files = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(files) == {"sketch_size", "sketch_limb16_sums", "sketch_sample_index", "sketch_sample_hi32", "sketch_sample_lo32"}
+    assert all(a.dtype == np.float64 for a in files.values())
+    assert sum(p.stat().st_size for p in tmp_path.glob("*.npy")) <= 64 << 20
+    assert files["sketch_size"][0] == h.size
+    idx = files["sketch_sample_index"].astype(np.int64)
+    assert idx.size == min(h.size, bench.DUMP_SAMPLE) and np.all(np.diff(idx) > 0)
+    got = (files["sketch_sample_hi32"].astype(np.uint64) << np.uint64(32)) | files["sketch_sample_lo32"].astype(np.uint64)
+    assert np.array_equal(got, h[idx])
+    limbs = [int(v) for v in files["sketch_limb16_sums"]]
+    assert limbs == [int(((h >> np.uint64(16 * i)) & np.uint64(0xFFFF)).sum(dtype=np.uint64)) for i in range(4)]

@@ -16,4 +16,4 @@ print({k:d[k] for k in ('index_build_ms','rounds','loop_ms','us_per_round','over
 done
 SMG_GATHER_TRACE=1 timeout 300 python tools/bench_gather.py 2>&1 | grep "persistent loop\|of which" | tail -4 >> $O/gather_ab.txt
 ( timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -25 ) > $O/pytest_gpu.txt
-( timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "rc $?" >> $O/bench.err; tail -5 $O/bench.err ) 
+( timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "rc $?" >> $O/bench.err; tail -5 $O/bench.err )

@@ -1,7 +1,7 @@
 # round 6, GPU call 1: the GPU suite, the default bench (the line must parse and stay under 8 KB), the sketch PMC passes
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r06; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.txt 2>&1; tail -3 $O/pytest_gpu.txt
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 python - <<'P'
 import json
 l=open('gpurun_out/r06/bench.json').read().strip().splitlines()

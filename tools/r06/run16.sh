@@ -3,7 +3,7 @@
 # device exchange paths); one parseable line of <= 8 KB from rank 0, transports and fell_back flags in it
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 O=gpurun_out/r06; mkdir -p $O
-SMG_BENCH_SHARE_GPU=1 timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 8 --steps 2 --warmup 1 --bases 1e9 --no-io > $O/eight_ranks.json 2> $O/eight_ranks.err; echo "rc=$?" >> $O/eight_ranks.err
+SMG_BENCH_SHARE_GPU=1 timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus 8 --steps 2 --warmup 1 --bases 1e9 --no-io > $O/eight_ranks.json 2> $O/eight_ranks.err; echo "rc=$?" >> $O/eight_ranks.err
 tail -3 $O/eight_ranks.err
 python - <<'PY'
 import json
