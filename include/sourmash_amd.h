@@ -86,6 +86,7 @@ typedef uint32_t SourmashErrorCode;
 typedef struct SourmashComputeParameters SourmashComputeParameters;
 typedef struct SourmashKmerMinHash SourmashKmerMinHash;
 typedef struct SourmashSignature SourmashSignature;
+typedef struct SourmashHyperLogLog SourmashHyperLogLog;
 
 /* include/sourmash.h:74-87 (ffi/utils.rs:209-316) */
 typedef struct {
@@ -209,6 +210,25 @@ const uint8_t *signatures_save_buffer(const SourmashSignature *const *ptr, uintp
                                       uintptr_t *osize);
 /* generic byte-buffer free (src/sourmash/signature.py:514 frees signatures_save_buffer output with it) */
 void nodegraph_buffer_free(uint8_t *ptr, uintptr_t insize);
+
+/* HyperLogLog (include/sourmash.h, src/core/src/ffi/hyperloglog.rs).  hll_to_buffer's buffer is freed with nodegraph_buffer_free. */
+void hll_add_hash(SourmashHyperLogLog *ptr, uint64_t hash);
+void hll_add_sequence(SourmashHyperLogLog *ptr, const char *sequence, uintptr_t insize, bool force);
+uintptr_t hll_cardinality(const SourmashHyperLogLog *ptr);
+double hll_containment(const SourmashHyperLogLog *ptr, const SourmashHyperLogLog *optr);
+void hll_free(SourmashHyperLogLog *ptr);
+SourmashHyperLogLog *hll_from_buffer(const char *ptr, uintptr_t insize);
+SourmashHyperLogLog *hll_from_path(const char *filename);
+uintptr_t hll_intersection_size(const SourmashHyperLogLog *ptr, const SourmashHyperLogLog *optr);
+uintptr_t hll_ksize(const SourmashHyperLogLog *ptr);
+uintptr_t hll_matches(const SourmashHyperLogLog *ptr, const SourmashKmerMinHash *mh_ptr);
+void hll_merge(SourmashHyperLogLog *ptr, const SourmashHyperLogLog *optr);
+SourmashHyperLogLog *hll_new(void);
+void hll_save(const SourmashHyperLogLog *ptr, const char *filename);
+double hll_similarity(const SourmashHyperLogLog *ptr, const SourmashHyperLogLog *optr);
+const uint8_t *hll_to_buffer(const SourmashHyperLogLog *ptr, uintptr_t *size);
+void hll_update_mh(SourmashHyperLogLog *ptr, const SourmashKmerMinHash *optr);
+SourmashHyperLogLog *hll_with_error_rate(double error_rate, uintptr_t ksize);
 
 /* ============================ PART 2: batch extensions ============================ */
 /* Same conventions (TLS error, zero on failure).  "d_" pointers are device
@@ -571,6 +591,22 @@ void smgpu_intersect_raw(const uint64_t *d_a, uint64_t na, const uint64_t *d_b, 
 /* query <- query minus match (src/sourmash/search.py:915-919): sorted set difference */
 void smgpu_subtract_raw(const uint64_t *d_a, uint64_t na, const uint64_t *d_b, uint64_t nb, uint64_t *d_out,
                         uint64_t *d_n, void *d_workspace, uint64_t workspace_bytes, void *stream);
+
+/* ---- HyperLogLog extensions (csrc/hll.hip) ---- */
+/* Hash the records queued by hll_add_sequence into the registers now (every reader does it anyway). */
+void smgpu_hll_flush(SourmashHyperLogLog *ptr);
+/* The 2^p registers (one byte each, owned by the handle, valid until its next change); *size = 2^p. */
+const uint8_t *smgpu_hll_registers(const SourmashHyperLogLog *ptr, uintptr_t *size);
+uint32_t smgpu_hll_precision(const SourmashHyperLogLog *ptr);
+/* Every record of a FASTA / FASTQ file (plain or gzip) into the registers through the streaming ingest (force = true
+ * semantics: bad k-mers are skipped).  *n_records (may be NULL) = records read; returns the bases read. */
+uint64_t smgpu_hll_add_file(SourmashHyperLogLog *ptr, const char *path, uint64_t *n_records);
+/* d_seq[0,len) already on the device (records separated by a byte outside ACGTacgt, e.g. '\n') into the registers;
+ * `stream` is the stream that wrote d_seq.  Synchronises. */
+void smgpu_hll_add_device(SourmashHyperLogLog *ptr, const uint8_t *d_seq, uint64_t len, void *stream);
+/* The kernel alone: d_regs[2^p] (device u32, one per register) updated with every canonical k-mer hash != 0 (seed 42) of
+ * d_seq[0,len); p in 4 .. 18.  Asynchronous on `stream`. */
+void smgpu_hll_dna_raw(const uint8_t *d_seq, uint64_t len, uint32_t ksize, uint32_t p, uint32_t *d_regs, void *stream);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,15 @@ hipError_t kmer_hashes_launch(const uint8_t* d_seq, uint64_t len, uint32_t k, ui
 // *d_first = min(*d_first, position of the first byte outside ACGTacgt)
 hipError_t first_invalid_launch(const uint8_t* d_seq, uint64_t len, unsigned long long* d_first, hipStream_t stream);
 
+// ---- hll.hip (HyperLogLog registers: one u32 per register, 2^p of them, p in 4 .. 18) ------------------
+// every canonical DNA k-mer hash h != 0 (seed 42) of d_seq[0,len): d_regs[h & (2^p-1)] = max(.., clz64(h >> p) + 1 - p).
+// Any alignment; bytes outside ACGTacgt kill the k-mers covering them.  k > 88 takes scratch from the library's arena.
+hipError_t hll_dna_launch(const uint8_t* d_seq, uint64_t len, uint32_t k, uint32_t p, uint32_t* d_regs, hipStream_t stream);
+// the same update for every hash of d_hashes[0,n) (skip_zero: hashes equal to 0 are left out)
+hipError_t hll_hashes_launch(const uint64_t* d_hashes, uint64_t n, uint32_t p, uint32_t* d_regs, bool skip_zero, hipStream_t stream);
+// d_out[i] = (uint8_t)d_regs[i]
+hipError_t hll_pack_launch(const uint32_t* d_regs, uint32_t n, uint8_t* d_out, hipStream_t stream);
+
 // ---- protein.hip (protein / dayhoff / hp sketches) ---------------------------------------------
 // d_aa[i] = alphabet(upper(d_seq[i]))  (hash_function 2 protein, 3 dayhoff, 4 hp)
 hipError_t residues_launch(const uint8_t* d_seq, uint64_t len, uint32_t hash_function, uint8_t* d_aa, hipStream_t stream);
