@@ -87,6 +87,7 @@ typedef struct SourmashComputeParameters SourmashComputeParameters;
 typedef struct SourmashKmerMinHash SourmashKmerMinHash;
 typedef struct SourmashSignature SourmashSignature;
 typedef struct SourmashHyperLogLog SourmashHyperLogLog;
+typedef struct SourmashNodegraph SourmashNodegraph;
 
 /* include/sourmash.h:74-87 (ffi/utils.rs:209-316) */
 typedef struct {
@@ -229,6 +230,28 @@ double hll_similarity(const SourmashHyperLogLog *ptr, const SourmashHyperLogLog 
 const uint8_t *hll_to_buffer(const SourmashHyperLogLog *ptr, uintptr_t *size);
 void hll_update_mh(SourmashHyperLogLog *ptr, const SourmashKmerMinHash *optr);
 SourmashHyperLogLog *hll_with_error_rate(double error_rate, uintptr_t ksize);
+
+/* Nodegraph, khmer's Bloom filter (include/sourmash.h, src/core/src/ffi/nodegraph.rs).  nodegraph_to_buffer's buffer is freed
+ * with nodegraph_buffer_free, nodegraph_hashsizes' array with kmerminhash_slice_free. */
+bool nodegraph_count(SourmashNodegraph *ptr, uint64_t h);
+bool nodegraph_count_kmer(SourmashNodegraph *ptr, const char *kmer);
+double nodegraph_expected_collisions(const SourmashNodegraph *ptr);
+void nodegraph_free(SourmashNodegraph *ptr);
+SourmashNodegraph *nodegraph_from_buffer(const char *ptr, uintptr_t insize);
+SourmashNodegraph *nodegraph_from_path(const char *filename);
+uintptr_t nodegraph_get(const SourmashNodegraph *ptr, uint64_t h);
+uintptr_t nodegraph_get_kmer(const SourmashNodegraph *ptr, const char *kmer);
+const uint64_t *nodegraph_hashsizes(const SourmashNodegraph *ptr, uintptr_t *size);
+uintptr_t nodegraph_ksize(const SourmashNodegraph *ptr);
+uintptr_t nodegraph_matches(const SourmashNodegraph *ptr, const SourmashKmerMinHash *mh_ptr);
+SourmashNodegraph *nodegraph_new(void);
+uintptr_t nodegraph_noccupied(const SourmashNodegraph *ptr);
+uintptr_t nodegraph_ntables(const SourmashNodegraph *ptr);
+void nodegraph_save(const SourmashNodegraph *ptr, const char *filename);
+const uint8_t *nodegraph_to_buffer(const SourmashNodegraph *ptr, uint8_t compression, uintptr_t *size);
+void nodegraph_update(SourmashNodegraph *ptr, const SourmashNodegraph *optr);
+void nodegraph_update_mh(SourmashNodegraph *ptr, const SourmashKmerMinHash *optr);
+SourmashNodegraph *nodegraph_with_tables(uintptr_t ksize, uintptr_t starting_size, uintptr_t n_tables);
 
 /* ============================ PART 2: batch extensions ============================ */
 /* Same conventions (TLS error, zero on failure).  "d_" pointers are device
@@ -607,6 +630,30 @@ void smgpu_hll_add_device(SourmashHyperLogLog *ptr, const uint8_t *d_seq, uint64
 /* The kernel alone: d_regs[2^p] (device u32, one per register) updated with every canonical k-mer hash != 0 (seed 42) of
  * d_seq[0,len); p in 4 .. 18.  Asynchronous on `stream`. */
 void smgpu_hll_dna_raw(const uint8_t *d_seq, uint64_t len, uint32_t ksize, uint32_t p, uint32_t *d_regs, void *stream);
+
+/* ---- Nodegraph extensions (csrc/nodegraph.hip) ---- */
+/* The bulk k-mer calls take ksize 1 .. 32 and fold lower case to upper case; a bulk call on another ksize is an error.  The
+ * tables and n_occupied after any mix of single and bulk calls equal what the same calls give one by one on the host. */
+/* add_sequence: the records are queued and counted when the graph is next read (force = false: InvalidDNA naming the first
+ * bad k-mer after the k-mers before it were counted; force = true: bad k-mers are skipped). */
+void smgpu_nodegraph_add_sequence(SourmashNodegraph *ptr, const char *sequence, uintptr_t insize, bool force);
+/* Count the queued records now (every reader does it anyway). */
+void smgpu_nodegraph_flush(SourmashNodegraph *ptr);
+/* Every record of a FASTA / FASTQ file (plain or gzip) through the streaming ingest (force = true semantics).  *n_records
+ * (may be NULL) = records read; returns the bases read. */
+uint64_t smgpu_nodegraph_add_file(SourmashNodegraph *ptr, const char *path, uint64_t *n_records);
+/* d_seq[0,len) already on the device (records separated by any byte outside ACGTacgt); `stream` wrote d_seq.  Synchronises. */
+void smgpu_nodegraph_add_device(SourmashNodegraph *ptr, const uint8_t *d_seq, uint64_t len, void *stream);
+/* nodegraph_update_mh of every row of a SketchSet, in one launch over its resident CSR. */
+void smgpu_nodegraph_update_sketchset(SourmashNodegraph *ptr, const SmgpuSketchSet *set);
+/* out[r] = nodegraph_matches of row r of a SketchSet (out: one uint64_t per row). */
+void smgpu_nodegraph_matches_sketchset(const SourmashNodegraph *ptr, const SmgpuSketchSet *set, uint64_t *out);
+/* Summed intersections over summed unions of the zipped tables / summed intersections over this graph's set bits. */
+double smgpu_nodegraph_similarity(const SourmashNodegraph *ptr, const SourmashNodegraph *optr);
+double smgpu_nodegraph_containment(const SourmashNodegraph *ptr, const SourmashNodegraph *optr);
+/* The table sizes nodegraph_with_tables(_, starting_size, n_tables) would make, without making the tables: the first
+ * min(n, cap) into out; returns n. */
+uintptr_t smgpu_nodegraph_table_sizes(uintptr_t starting_size, uintptr_t n_tables, uint64_t *out, uintptr_t cap);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,7 @@ from .minhash import MinHash, FrozenMinHash, hash_murmur, get_minhash_default_se
 from .signature import (SourmashSignature, FrozenSourmashSignature, load_signatures_from_json,  # noqa: E402
                         load_one_signature_from_json, save_signatures_to_json)
 from .hll import HLL  # noqa: E402
+from .nodegraph import Nodegraph  # noqa: E402
 
 DEFAULT_SEED = get_minhash_default_seed()
 MAX_HASH = get_minhash_max_hash()
@@ -24,6 +25,6 @@ def gpu_available():
     return bool(_lib.smgpu_available())
 
 
-__all__ = ["MinHash", "FrozenMinHash", "HLL", "SourmashSignature", "FrozenSourmashSignature", "hash_murmur",
+__all__ = ["MinHash", "FrozenMinHash", "HLL", "Nodegraph", "SourmashSignature", "FrozenSourmashSignature", "hash_murmur",
            "load_signatures_from_json", "load_one_signature_from_json", "save_signatures_to_json",
            "gpu_available", "DEFAULT_SEED", "MAX_HASH", "VERSION"]

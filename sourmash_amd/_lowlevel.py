@@ -33,7 +33,7 @@ _SCALARS = {
     "uintptr_t": C.c_size_t, "HashFunctions": C.c_uint32, "SourmashErrorCode": C.c_uint32,
     "SourmashStr": SourmashStr,
 }
-_OPAQUE = {"SourmashKmerMinHash", "SourmashSignature", "SourmashHyperLogLog", "SourmashComputeParameters", "SmgpuSketchSet", "SmgpuCounter", "SmgpuBitIndex",
+_OPAQUE = {"SourmashKmerMinHash", "SourmashSignature", "SourmashHyperLogLog", "SourmashNodegraph", "SourmashComputeParameters", "SmgpuSketchSet", "SmgpuCounter", "SmgpuBitIndex",
            "SmgpuGather", "SmgpuCollection", "SmgpuGatherXchg"}
 
 

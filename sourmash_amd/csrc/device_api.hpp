@@ -39,6 +39,28 @@ hipError_t hll_hashes_launch(const uint64_t* d_hashes, uint64_t n, uint32_t p, u
 // d_out[i] = (uint8_t)d_regs[i]
 hipError_t hll_pack_launch(const uint32_t* d_regs, uint32_t n, uint8_t* d_out, hipStream_t stream);
 
+// ---- nodegraph.hip (Bloom filter tables: one u32 word array, fixedbitset layout) ----------------------------------------
+// table t: `size` bits from word `off` of the array; magic = ng_magic(size) (nodegraph_core.hpp)
+struct NgTable { uint64_t size, magic, off; };
+// a graph's device mirror: tabs[n_tables] and words[n_words] on the device, t0_words = table 0's words (it starts at word 0),
+// *occ += table-0 bits turned from 0 to 1
+struct NgDev {
+    const NgTable* tabs = nullptr;
+    uint32_t n_tables = 0;
+    uint32_t* words = nullptr;
+    uint64_t n_words = 0;
+    uint64_t t0_words = 0;
+    unsigned long long* occ = nullptr;
+};
+// every k-mer (1 <= k <= 32) of d_seq[0,len) whose bytes are all in ACGTacgt sets bit min(fwd, rev two-bit word) mod size of
+// every table.  Any alignment.  Asynchronous on `stream`.
+hipError_t nodegraph_dna_launch(const uint8_t* d_seq, uint64_t len, uint32_t k, const NgDev& g, hipStream_t stream);
+// every hash of d_hashes[0,n) sets its bits
+hipError_t nodegraph_hashes_launch(const uint64_t* d_hashes, uint64_t n, const NgDev& g, hipStream_t stream);
+// d_out[r] = hashes of CSR row r (d_hashes[d_offsets[r] .. d_offsets[r+1])) found in every table (read-only)
+hipError_t nodegraph_matches_launch(const uint64_t* d_hashes, const uint64_t* d_offsets, uint64_t n_rows, const NgDev& g,
+                                    uint64_t* d_out, hipStream_t stream);
+
 // ---- protein.hip (protein / dayhoff / hp sketches) ---------------------------------------------
 // d_aa[i] = alphabet(upper(d_seq[i]))  (hash_function 2 protein, 3 dayhoff, 4 hp)
 hipError_t residues_launch(const uint8_t* d_seq, uint64_t len, uint32_t hash_function, uint8_t* d_aa, hipStream_t stream);

@@ -332,18 +332,22 @@ inline void* gunzip_file_to_device(IngestScratch& scratch, const std::string& pa
 // inflated: the file's bytes already in HBM (a member of a batch inflated by the caller: sketch_files_parallel), or
 // {nullptr, 0, true} when the device has refused the file already; default: the file is tried on the device here.
 // hll: HyperLogLog register files (device u32 registers, hll.hip) fed from the same compacted chunks as the sketches.
+// ng: Nodegraph device mirrors (nodegraph.hip, k <= 32), fed the same way.
 struct InflatedSlice { const void* p = nullptr; uint64_t len = 0; bool refused = false; };
 struct HllSink { uint32_t k; uint32_t p; uint32_t* regs; };
+struct NgSink { uint32_t k; NgDev g; };
 inline void sketch_file_with(IngestWorker& w, std::vector<KmerMinHash*>& mhs, const std::string& path, size_t CHUNK,
                              unsigned max_readers, uint64_t* n_records, uint64_t* n_bases, const InflatedSlice* inflated = nullptr,
-                             const std::vector<HllSink>* hll = nullptr) {
+                             const std::vector<HllSink>* hll = nullptr, const std::vector<NgSink>* ng = nullptr) {
     for (auto* mh : mhs)
         if (!mh->is_dna()) throw err_internal("the streaming file ingest takes DNA sketches; protein / dayhoff / hp sketches are fed record by record");
     uint32_t kmax = 0;
     for (auto* mh : mhs) kmax = std::max(kmax, mh->ksize);
     if (hll)
         for (const HllSink& h : *hll) kmax = std::max(kmax, h.k);
-    if ((mhs.empty() && !(hll && !hll->empty())) || kmax == 0) return;
+    if (ng)
+        for (const NgSink& n : *ng) kmax = std::max(kmax, n.k);
+    if ((mhs.empty() && !(hll && !hll->empty()) && !(ng && !ng->empty())) || kmax == 0) return;
     check_dna_ksize(kmax);
     hipStream_t st = w.stream;
     IngestScratch& scratch = w.scratch;
@@ -542,6 +546,10 @@ inline void sketch_file_with(IngestWorker& w, std::vector<KmerMinHash*>& mhs, co
             for (const HllSink& h : *hll)
                 if (h.k && (uint64_t)(h.k - 1) + n_kept >= h.k)
                     hip_check(hll_dna_launch(comp - (h.k - 1), (uint64_t)(h.k - 1) + n_kept, h.k, h.p, h.regs, st), "hll_dna");
+        if (ng)
+            for (const NgSink& n : *ng)
+                if (n.k && (uint64_t)(n.k - 1) + n_kept >= n.k)
+                    hip_check(nodegraph_dna_launch(comp - (n.k - 1), (uint64_t)(n.k - 1) + n_kept, n.k, n.g, st), "nodegraph_dna");
         // the next chunk's halo: the last kmax-1 bytes of the stream so far
         hip_check(fastx_halo_launch(comp, d_n, halo, scratch.comp[b ^ 1].as<uint8_t>() + scratch.halo - halo, st), "halo");
         cur = next;
@@ -764,7 +772,8 @@ inline void sketch_slices_batched(IngestWorker& w, const std::vector<InflatedSli
 
 // single-file entry point: the shared pipeline on the context's stream
 inline void sketch_file_into(std::vector<KmerMinHash*>& mhs, const std::string& path, uint64_t* n_records,
-                             uint64_t* n_bases, const std::vector<HllSink>* hll = nullptr) {
+                             uint64_t* n_bases, const std::vector<HllSink>* hll = nullptr,
+                             const std::vector<NgSink>* ng = nullptr) {
     DeviceCtx& ctx = DeviceCtx::get();
     std::lock_guard<std::recursive_mutex> g(ctx.mutex());
     static IngestWorker& shared = *new IngestWorker();   // guarded by the context mutex; leaked on purpose like the
@@ -773,7 +782,7 @@ inline void sketch_file_into(std::vector<KmerMinHash*>& mhs, const std::string& 
     // 32 MiB chunks; SMG_INGEST_CHUNK (bytes) overrides it so tests can force many chunk boundaries
     size_t chunk = (size_t)32 << 20;
     if (const char* e = getenv("SMG_INGEST_CHUNK")) { const long v = atol(e); if (v >= 256) chunk = (size_t)v; }
-    sketch_file_with(shared, mhs, path, chunk, 6, n_records, n_bases, nullptr, hll);
+    sketch_file_with(shared, mhs, path, chunk, 6, n_records, n_bases, nullptr, hll, ng);
 }
 
 // Many files at once: `threads` workers, each with its own stream, pinned ring and device chunks (4 MiB pieces: the
