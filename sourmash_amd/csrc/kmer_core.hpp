@@ -204,6 +204,16 @@ SMG_HD uint32_t nonzero_bytes4(uint32_t x) {
     return (t * 0x01020408u) >> 24 & 0xfu;
 }
 
+// The early reject of process_lane.  The top dword t of a kept hash satisfies t <= thr >> 32 = thr_hi, and the open form knows
+// s in {t - 1, t, t + 1} (mod 2^32, mmh3_close_hi_sum).  (s + 1) mod 2^32 is then t, t + 1 or t + 2: at most thr_hi + 2 whenever
+// t <= thr_hi (t = 0 with s = 2^32 - 1 wraps to 0, which passes).  Where thr_hi + 2 would wrap every k-mer is finished.
+SMG_HD uint32_t early_limit(uint64_t thr) {
+    const uint32_t thr_hi = (uint32_t)(thr >> 32);
+    return thr_hi >= 0xfffffffdu ? 0xffffffffu : thr_hi + 2u;
+}
+// false only if mmh3_close(open) > thr
+SMG_HD bool early_may_keep(Mmh3Open open, uint32_t lim) { return (uint32_t)(mmh3_close_hi_sum(open) + 1u) <= lim; }
+
 // Process the P start positions of one lane.
 //   raw[NW]  : the lane's window bytes as little-endian dwords (any case, any junk;
 //              bytes past the end of the sequence must be non-ACGT, e.g. 0)
@@ -217,9 +227,7 @@ template <int K, int P, bool EARLY, class Emit, int... O>
 SMG_HD void process_lane_impl(const uint32_t* raw, uint64_t seed, uint64_t thr, Emit&& emit,
                               std::integer_sequence<int, O...>) {
     using G = LaneGeom<K, P>;
-    // top dword t of a kept hash satisfies t <= thr >> 32; the open form knows t or t - 1 (mod 2^32)
-    const uint32_t thr_hi = (uint32_t)(thr >> 32);
-    const uint32_t lim = thr_hi >= 0xfffffffeu ? 0xffffffffu : thr_hi + 1u;
+    const uint32_t lim = early_limit(thr);
     uint32_t U[G::NW], C[G::NW];
     uint32_t anybad = 0;
 #pragma unroll
@@ -253,8 +261,7 @@ SMG_HD void process_lane_impl(const uint32_t* raw, uint64_t seed, uint64_t thr, 
         [&] {
             const Mmh3Open open = PosOps<K, P, O>::hash_open(U, C, seed);
             if constexpr (EARLY) {
-                // s in {t, t - 1}: (s + 1) mod 2^32 <= thr_hi + 1 whenever t <= thr_hi
-                if (!any_lane((uint32_t)(mmh3_close_hi(open) + 1u) <= lim)) return;
+                if (!any_lane(early_may_keep(open, lim))) return;
             }
             const uint64_t h = mmh3_close(open);
             bool ok = (h - 1) < thr;                          // h != 0 (signature.rs:50) and h <= thr (minhash.rs:319)

@@ -64,6 +64,19 @@ SMG_HD uint64_t mul5_add(uint64_t h, uint64_t c) {
 #endif
 }
 
+// The same with c in scalar registers: c MUST be wave-uniform (a constant, or a function of kernel arguments).  Taken where c is
+// not a literal: as a vector operand such a c is copied into a register pair again at every use.
+SMG_HD uint64_t mul5_add_uniform(uint64_t h, uint64_t c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint64_t t;
+    asm("v_lshl_add_u64 %0, %1, 2, %1" : "=v"(t) : "v"(h));
+    asm("v_lshl_add_u64 %0, %1, 0, %2" : "=v"(t) : "v"(t), "s"(c));
+    return t;
+#else
+    return h * 5 + c;
+#endif
+}
+
 SMG_HD uint64_t fmix64(uint64_t k) {
     k ^= k >> 33;
     k *= 0xff51afd7ed558ccdULL;
@@ -104,6 +117,17 @@ SMG_HD void mmh3_block(uint64_t& h1, uint64_t& h2, uint64_t k1, uint64_t k2) {
     h2 = rotl64<31>(h2); h2 += h1; h2 = mul5_add(h2, 0x38495ab5);
 }
 
+// mmh3_block for the FIRST block of a key, where h1 == h2 == seed on entry: `h1 += h2; h1 = h1 * 5 + 0x52dce729` is then
+// rotl27(seed ^ k1) * 5 + (5 * seed + 0x52dce729), and the bracket -- c1s, mmh3_seed_c1(seed) -- does not depend on the key.
+// The seed must be wave-uniform on the device (it is a kernel argument or a constant everywhere): c1s stays in scalar registers.
+SMG_HD uint64_t mmh3_seed_c1(uint64_t seed) { return seed * 5 + 0x52dce729; }
+SMG_HD void mmh3_block_first(uint64_t& h1, uint64_t& h2, uint64_t k1, uint64_t k2, uint64_t seed, uint64_t c1s) {
+    k1 *= MMH3_C1; k1 = rotl64<31>(k1); k1 *= MMH3_C2;
+    h1 = mul5_add_uniform(rotl64<27>(seed ^ k1), c1s);
+    k2 *= MMH3_C2; k2 = rotl64<33>(k2); k2 *= MMH3_C1; h2 = seed ^ k2;
+    h2 = rotl64<31>(h2); h2 += h1; h2 = mul5_add(h2, 0x38495ab5);
+}
+
 SMG_HD uint64_t mmh3_finish(uint64_t h1, uint64_t h2, uint64_t len) {
     h1 ^= len; h2 ^= len;
     h1 += h2; h2 += h1;
@@ -121,6 +145,10 @@ SMG_HD Mmh3Open mmh3_finish_open(uint64_t h1, uint64_t h2, uint64_t len) {
 SMG_HD uint64_t mmh3_close(Mmh3Open o) { return fmix64_tail(o.a) + fmix64_tail(o.b); }
 // top dword of mmh3_close(o), short of the carry out of the low dwords: the true value is this or this + 1
 SMG_HD uint32_t mmh3_close_hi(Mmh3Open o) { return fmix64_tail_hi(o.a) + fmix64_tail_hi(o.b); }
+// The same estimate from ONE product: a * c + b * c == (a + b) * c (mod 2^64), and the closing xor-shift by 33 moves each product
+// by less than 2^31, so mmh3_close(o) differs from (a + b) * c by less than 2^32.  The true top dword is this, this + 1 or
+// this - 1 (mod 2^32): a wider window than mmh3_close_hi's for three multiplies and an add less.
+SMG_HD uint32_t mmh3_close_hi_sum(Mmh3Open o) { return fmix64_tail_hi(o.a + o.b); }
 
 // Key given as zero-padded little-endian dwords w[0 .. ceil(K/4)-1].
 template <int K>
@@ -133,7 +161,8 @@ SMG_HD Mmh3Open mmh3_open_words(const uint32_t* w, uint64_t seed) {
     for (int b = 0; b < NB; ++b) {
         uint64_t k1 = (uint64_t)w[4 * b] | ((uint64_t)w[4 * b + 1] << 32);
         uint64_t k2 = (uint64_t)w[4 * b + 2] | ((uint64_t)w[4 * b + 3] << 32);
-        mmh3_block(h1, h2, k1, k2);
+        if (b == 0) mmh3_block_first(h1, h2, k1, k2, seed, mmh3_seed_c1(seed));   // (the seed is uniform: its constant is computed once)
+        else mmh3_block(h1, h2, k1, k2);
     }
     constexpr int tb = 4 * NB;
     if (T > 8) {
