@@ -31,6 +31,10 @@ __device__ __forceinline__ void hll_fold_lds(const uint32_t* s_reg, uint32_t n_r
 // of seq updates register h & (2^p - 1) to max(reg, rank(h)).  LDS == true: the workgroup's registers live in dynamic LDS (one
 // u32 each, native ds_max_u32) and are folded into `regs` at the end; LDS == false (p > HLL_LDS_MAX_P): straight to `regs`
 // behind a read filter.
+// The instantiations that keep the plain 64-bit constant multiply (murmur3.hpp, mul_c64<C, PLAIN>): the limb form would cost each
+// of them a wave per SIMD (profiles/mul_c64_kernel_resources.txt).
+constexpr bool hll_plain_mul(int k, bool lds) { return k == 28 || k == 60 || (k == 57 && lds); }
+
 template <int K, int P, bool LDS>
 __global__ __launch_bounds__(SK_BLOCK) void hll_dna_kernel(const uint8_t* __restrict__ seq, uint64_t len, uint32_t p,
                                                            uint32_t* regs, uint64_t n_tiles, uint32_t skip) {
@@ -78,7 +82,7 @@ __global__ __launch_bounds__(SK_BLOCK) void hll_dna_kernel(const uint8_t* __rest
             const uint4 v = wp[i];
             raw[4 * i] = v.x; raw[4 * i + 1] = v.y; raw[4 * i + 2] = v.z; raw[4 * i + 3] = v.w;
         }
-        process_lane<K, P, false>(raw, HLL_SEED, ~0ull, [&](int, uint64_t h) {
+        process_lane<K, P, false, hll_plain_mul(K, LDS)>(raw, HLL_SEED, ~0ull, [&](int, uint64_t h) {
             const uint32_t idx = (uint32_t)(h & mask);
             const uint32_t r = hll_rank(h, p);
             if constexpr (LDS) {

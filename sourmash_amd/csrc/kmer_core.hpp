@@ -180,6 +180,7 @@ struct PosOps {
     }
 
     // hash of the canonical k-mer at this position, last fmix64 multiplies left open (murmur3.hpp)
+    template <bool PLAIN = false>
     static SMG_HD Mmh3Open hash_open(const uint32_t* U, const uint32_t* C, uint64_t seed) {
         uint32_t F[G::NWK], R[G::NWK];
         build(U, C, F, R, std::make_integer_sequence<int, G::NWK>{});
@@ -191,7 +192,7 @@ struct PosOps {
         const uint32_t m = gt ? 0xffffffffu : 0u;
 #pragma unroll
         for (int d = 0; d < G::NWK; ++d) W[d] = bitselect(m, R[d], F[d]);
-        return mmh3_open_words<K>(W, seed);
+        return mmh3_open_words<K, PLAIN>(W, seed);
     }
 };
 
@@ -222,8 +223,8 @@ SMG_HD bool early_may_keep(Mmh3Open open, uint32_t lim) { return (uint32_t)(mmh3
 //
 // EARLY: test the top dword of the hash first and finish it only when some lane of the wave may keep its k-mer
 // (1 wave-step in 16 at scaled = 1000); the result is the same either way.  Dense callers (every hash wanted) turn
-// it off.
-template <int K, int P, bool EARLY, class Emit, int... O>
+// it off.  PLAIN: the 64-bit constant multiplies of the hash as plain products (murmur3.hpp, mul_c64); the same values.
+template <int K, int P, bool EARLY, bool PLAIN, class Emit, int... O>
 SMG_HD void process_lane_impl(const uint32_t* raw, uint64_t seed, uint64_t thr, Emit&& emit,
                               std::integer_sequence<int, O...>) {
     using G = LaneGeom<K, P>;
@@ -259,11 +260,11 @@ SMG_HD void process_lane_impl(const uint32_t* raw, uint64_t seed, uint64_t thr, 
     static_assert(G::NBYTES <= 192 && K <= 128 && P <= 64, "window too long for the 192-bit validity mask");
     (
         [&] {
-            const Mmh3Open open = PosOps<K, P, O>::hash_open(U, C, seed);
+            const Mmh3Open open = PosOps<K, P, O>::template hash_open<PLAIN>(U, C, seed);
             if constexpr (EARLY) {
                 if (!any_lane(early_may_keep(open, lim))) return;
             }
-            const uint64_t h = mmh3_close(open);
+            const uint64_t h = mmh3_close<PLAIN>(open);
             bool ok = (h - 1) < thr;                          // h != 0 (signature.rs:50) and h <= thr (minhash.rs:319)
             if (anybad != 0) {
                 // any invalid byte in [O, O+K) kills the k-mer (signature.rs:271-286, force=true)
@@ -279,9 +280,9 @@ SMG_HD void process_lane_impl(const uint32_t* raw, uint64_t seed, uint64_t thr, 
         ...);
 }
 
-template <int K, int P, bool EARLY = true, class Emit>
+template <int K, int P, bool EARLY = true, bool PLAIN = false, class Emit>
 SMG_HD void process_lane(const uint32_t* raw, uint64_t seed, uint64_t thr, Emit&& emit) {
-    process_lane_impl<K, P, EARLY>(raw, seed, thr, static_cast<Emit&&>(emit), std::make_integer_sequence<int, P>{});
+    process_lane_impl<K, P, EARLY, PLAIN>(raw, seed, thr, static_cast<Emit&&>(emit), std::make_integer_sequence<int, P>{});
 }
 
 }  // namespace smg

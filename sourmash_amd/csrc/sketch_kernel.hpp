@@ -18,6 +18,13 @@ constexpr int SK_FAST_MAX_K = 88;
 constexpr int sk_part_size(int first_k_minus_1) { return SK_FAST_MAX_K - first_k_minus_1 < 16 ? SK_FAST_MAX_K - first_k_minus_1 : 16; }
 constexpr int SK_OUT_CAP = 2048;   // LDS staging entries for kept hashes (16 KiB)
 
+// The instantiations that keep the plain 64-bit constant multiply in their hash (murmur3.hpp, mul_c64<C, PLAIN>): with the limb
+// form's one more live register each of these would run one wave per SIMD fewer (profiles/mul_c64_kernel_resources.txt).
+constexpr bool sk_plain_mul(int k, bool dense) {
+    if (dense) return k == 1 || k == 5 || k == 8 || k == 25 || k == 28 || k == 81 || k == 82 || k == 84;
+    return k == 50 || k == 51;
+}
+
 // DENSE == false: append kept hashes (unordered) to out, count in *out_count.
 // DENSE == true : out[i] = hash of the k-mer starting at i (out pre-zeroed by the
 //                 caller; bad k-mers and hash 0 stay 0) -- kmerminhash_seq_to_hashes.
@@ -79,7 +86,7 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
                 raw[4 * i] = p32[0]; raw[4 * i + 1] = p32[1]; raw[4 * i + 2] = p32[2]; raw[4 * i + 3] = p32[3];
             }
         }
-        process_lane<K, P, !DENSE>(raw, seed, thr, [&](int o, uint64_t h) {
+        process_lane<K, P, !DENSE, sk_plain_mul(K, DENSE)>(raw, seed, thr, [&](int o, uint64_t h) {
             if constexpr (DENSE) {
                 const uint64_t pos = base + (uint64_t)tid * P + (uint64_t)o - skip;   // valid k-mers never start in the prefix
                 if (pos < out_cap) out[pos] = h;

@@ -20,6 +20,10 @@ namespace {
 constexpr int SM_N = 3;              // ksizes per pass
 constexpr int SM_OUT_CAP = 1024;     // LDS staging entries for kept hashes, per ksize (8 KiB each)
 
+// The largest ksize keeps the plain 64-bit constant multiply (murmur3.hpp, mul_c64<C, PLAIN>): with the limb form in all three the
+// kernel no longer fits the 168 registers of 3 waves per SIMD (2 spilled, 12 bytes of scratch per lane at 21 / 31 / 51).
+constexpr bool SM_PLAIN_MUL_LAST = true;
+
 struct MultiArgs {
     uint64_t thr[SM_N];
     uint64_t* out[SM_N];
@@ -114,7 +118,7 @@ __global__ __launch_bounds__(SK_BLOCK) __attribute__((amdgpu_waves_per_eu(3, 8))
         fence();
         process_lane<KB, P, true>(raw, seed, a.thr[1], [&](int o, uint64_t h) { keep(1, o, h); });
         fence();
-        process_lane<KC, P, true>(raw, seed, a.thr[2], [&](int o, uint64_t h) { keep(2, o, h); });
+        process_lane<KC, P, true, SM_PLAIN_MUL_LAST>(raw, seed, a.thr[2], [&](int o, uint64_t h) { keep(2, o, h); });
         __syncthreads();
         flush(false);
     }

@@ -103,6 +103,54 @@ DEFK64(k_lshlrev_b64, S_LSHL64)
 DEFK64(k_lshrrev_b64, S_LSHR64)
 DEFK64(k_cmp_lt_u64, S_CMP64)
 
+// The operand shapes of the limb-wise constant multiply (murmur3.hpp, mul_c64): the constant's limb in an SGPR, the carry-out
+// pair an SGPR pair, and the addend either a register pair DISTINCT from the destination (chain i adds chain i + 1: the row
+// above times addend == destination) or the literal 0.  v_mul_lo_u32 with the SGPR limb and v_add_u32 / v_add3_u32 on
+// registers only are timed next to them, so that the four-instruction sequences can be priced from one run.
+#define DEFK64S(NAME, ASMSTR)                                                                      \
+    __global__ __launch_bounds__(256) void NAME(uint32_t* out, uint32_t seed) {                    \
+        uint64_t a0 = seed + threadIdx.x, a1 = a0 * 3, a2 = a0 * 5, a3 = a0 * 7, a4 = a0 * 11,     \
+                 a5 = a0 * 13, a6 = a0 * 17, a7 = a0 * 19;                                         \
+        uint32_t c = (seed | 1) + threadIdx.x;                                                     \
+        uint32_t k = seed * 0x1a85ec53u;              /* wave-uniform: a function of a kernel argument */ \
+        for (int i = 0; i < ITERS; ++i) {                                                          \
+            REP8(asm volatile(ASMSTR(0, 1) ASMSTR(1, 2) ASMSTR(2, 3) ASMSTR(3, 4) ASMSTR(4, 5)    \
+                              ASMSTR(5, 6) ASMSTR(6, 7) ASMSTR(7, 0)                               \
+                              : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5),      \
+                                "+v"(a6), "+v"(a7)                                                 \
+                              : "v"(c), "s"(k) : "vcc", "s10", "s11");)                            \
+        }                                                                                          \
+        out[blockIdx.x * blockDim.x + threadIdx.x] = (uint32_t)(a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7); \
+    }
+#define S_MAD64_SGPR_DISTINCT(i, j) "v_mad_u64_u32 %" #i ", s[10:11], %8, %9, %" #j "\n"
+#define S_MAD64_SGPR_SAME(i, j) "v_mad_u64_u32 %" #i ", s[10:11], %8, %9, %" #i "\n"
+#define S_MAD64_SGPR_ZERO(i, j) "v_mad_u64_u32 %" #i ", s[10:11], %8, %9, 0\n"
+DEFK64S(k_mad_u64_sgpr_distinct, S_MAD64_SGPR_DISTINCT)
+DEFK64S(k_mad_u64_sgpr_same, S_MAD64_SGPR_SAME)
+DEFK64S(k_mad_u64_sgpr_zero, S_MAD64_SGPR_ZERO)
+// 32-bit companions: 8 chains, v_mul_lo_u32 by the SGPR limb; add and add3 with the neighbouring chain as the other operand
+#define DEFK32S(NAME, ASMSTR)                                                                      \
+    __global__ __launch_bounds__(256) void NAME(uint32_t* out, uint32_t seed) {                    \
+        uint32_t a0 = seed + threadIdx.x, a1 = a0 * 3, a2 = a0 * 5, a3 = a0 * 7, a4 = a0 * 11,     \
+                 a5 = a0 * 13, a6 = a0 * 17, a7 = a0 * 19;                                         \
+        uint32_t c = (seed | 1) + threadIdx.x;                                                     \
+        uint32_t k = seed * 0x1a85ec53u;                                                           \
+        for (int i = 0; i < ITERS; ++i) {                                                          \
+            REP8(asm volatile(ASMSTR(0, 1) ASMSTR(1, 2) ASMSTR(2, 3) ASMSTR(3, 4) ASMSTR(4, 5)    \
+                              ASMSTR(5, 6) ASMSTR(6, 7) ASMSTR(7, 0)                               \
+                              : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5),      \
+                                "+v"(a6), "+v"(a7)                                                 \
+                              : "v"(c), "s"(k) : "vcc", "s10", "s11");)                            \
+        }                                                                                          \
+        out[blockIdx.x * blockDim.x + threadIdx.x] = a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7;       \
+    }
+#define S_MUL_LO_SGPR(i, j) "v_mul_lo_u32 %" #i ", %" #i ", %9\n"
+#define S_ADD_VV(i, j) "v_add_u32_e32 %" #i ", %" #i ", %" #j "\n"
+#define S_ADD3_VVV(i, j) "v_add3_u32 %" #i ", %" #i ", %" #j ", %8\n"
+DEFK32S(k_mul_lo_sgpr, S_MUL_LO_SGPR)
+DEFK32S(k_add_vv, S_ADD_VV)
+DEFK32S(k_add3_vvv, S_ADD3_VVV)
+
 typedef void (*kern_t)(uint32_t*, uint32_t);
 
 static void run(const char* name, kern_t k, int waves_per_simd) {
@@ -133,5 +181,6 @@ int main() {
     R(k_and_e32) R(k_or_e32) R(k_lshl_e32) R(k_lshr_e32) R(k_sub_e32) R(k_mov_e32) R(k_addco_e32) R(k_addc_e32) R(k_cnd_e32) R(k_cnd_e64_sgpr) R(k_and_or) R(k_lshl_or) R(k_or3) R(k_bfe) R(k_add_e64) R(k_xor_e64) R(k_mul_u24_e32) R(k_cmp_lt_u32_e32) R(k_bitop3_xor3) R(k_add) R(k_xor) R(k_add3) R(k_lshladd) R(k_perm) R(k_alignbit) R(k_cndmask)
     R(k_mul_u24) R(k_mad_u24) R(k_mul_lo) R(k_mul_hi) R(k_mad_u64_u32) R(k_lshl_add_u64)
     R(k_lshlrev_b64) R(k_lshrrev_b64) R(k_cmp_lt_u64)
+    R(k_mad_u64_sgpr_distinct) R(k_mad_u64_sgpr_same) R(k_mad_u64_sgpr_zero) R(k_mul_lo_sgpr) R(k_add_vv) R(k_add3_vvv)
     return 0;
 }
