@@ -285,4 +285,123 @@ SMG_HD void process_lane(const uint32_t* raw, uint64_t seed, uint64_t thr, Emit&
     process_lane_impl<K, P, EARLY, PLAIN>(raw, seed, thr, static_cast<Emit&&>(emit), std::make_integer_sequence<int, P>{});
 }
 
+// ---- the per-byte work done once, where the tile is staged (the appending form of sketch_kernel.hpp) -------------------------
+// A lane window is 46 bytes at k = 31 for 16 new ones: upper-casing, complement and validity per lane treat every staged byte
+// about 2.9 times.  Here the lane that stages a 16-byte chunk does them for the chunk, the tile goes to LDS twice -- upper-cased
+// and complemented -- and a flag per tile says whether any staged byte is invalid.  A lane of a clean tile reads U and C as they
+// are and does no validity work at all; a lane of a dirty tile rebuilds its bad-byte mask from U, as process_lane does.
+
+// Geometry of one tile of BLOCK lanes x P positions: what is staged, and what a lane reads back.
+template <int K, int P, int BLOCK>
+struct TileGeom {
+    using G = LaneGeom<K, P>;
+    static constexpr int TILE = BLOCK * P;                          // start positions per tile
+    static constexpr int LANE_RD = ((G::NW + 3) / 4) * 4;           // dwords each lane reads (whole 16-byte reads)
+    static constexpr int IN_DW = (BLOCK - 1) * (P / 4) + LANE_RD;   // dwords the tile needs in LDS
+    static constexpr int IN_CHUNKS = (IN_DW + 3) / 4;               // 16-byte chunks to stage
+};
+
+// The 16 bytes at seq + off as 4 little-endian dwords: zero past `len`, and the first `skip` (< 16) bytes of the buffer blanked.
+// seq + off is 16-byte aligned.
+SMG_HD void load_chunk(const uint8_t* seq, uint64_t off, uint64_t len, uint32_t skip, uint32_t* w) {
+    w[0] = w[1] = w[2] = w[3] = 0;
+    if (off + 16 <= len) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint4 v = *reinterpret_cast<const uint4*>(seq + off);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+#else
+        for (int b = 0; b < 16; ++b) w[b >> 2] |= (uint32_t)seq[off + b] << (8 * (b & 3));
+#endif
+    } else if (off < len) {
+        for (uint64_t b = off; b < len; ++b) w[(b - off) >> 2] |= (uint32_t)seq[b] << (8 * ((b - off) & 3));
+    }
+    if (off == 0 && skip) {                      // blank the alignment prefix
+        for (uint32_t b = 0; b < skip; ++b) w[b >> 2] &= ~(0xffu << (8 * (b & 3)));
+    }
+}
+
+// One chunk in place: w becomes its upper-cased bytes, c their complements; returns nonzero iff a byte is not ACGT
+// (the zero fill and the blanked prefix are such bytes).
+SMG_HD uint32_t stage_chunk(uint32_t* w, uint32_t* c) {
+    uint32_t anybad = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t u = w[j] & 0xdfdfdfdfu;              // upper-case (signature.rs:214)
+        const uint32_t code = (u >> 1) & 0x03030303u;
+        w[j] = u;
+        c[j] = perm_b32(0u, LUT_COMP, code);                 // encodings.rs:85-101
+        anybad |= perm_b32(0u, LUT_SELF, code) ^ u;          // encodings.rs:370-377
+    }
+    return anybad;
+}
+
+// The two halves of process_lane_impl's validity and position code, for a window that is already upper-cased and complemented
+// (process_lane_impl itself is left as it is: the per-position, multi-sketch and HyperLogLog kernels are built from it).
+// bit b of (badlo, badhi, badtop) = byte b of the upper-cased window U is invalid (192 bits: k <= 128 at P = 16 ... 64)
+template <int K, int P>
+SMG_HD void lane_bad_bits(const uint32_t* U, uint64_t& badlo, uint64_t& badhi, uint64_t& badtop) {
+    using G = LaneGeom<K, P>;
+    static_assert(G::NBYTES <= 192 && K <= 128 && P <= 64, "window too long for the 192-bit validity mask");
+#pragma unroll
+    for (int i = 0; i < G::NW; ++i) {
+        const uint32_t u = U[i];
+        const uint32_t code = (u >> 1) & 0x03030303u;
+        uint32_t bad = perm_b32(0u, LUT_SELF, code) ^ u;
+        if (i == G::NW - 1 && (G::NBYTES % 4) != 0) bad &= (1u << (8 * (G::NBYTES % 4))) - 1u;
+        const uint64_t nib = nonzero_bytes4(bad);
+        if (4 * i < 64) badlo |= nib << (4 * i);
+        else if (4 * i < 128) badhi |= nib << (4 * i - 64);
+        else badtop |= nib << (4 * i - 128);
+    }
+}
+
+// The P positions of a lane whose window is ready: U upper-cased, C its complement, anybad != 0 iff the window holds an invalid
+// byte, and then (badlo, badhi, badtop) says which.
+template <int K, int P, bool EARLY, bool PLAIN, class Emit, int... O>
+SMG_HD void lane_positions(const uint32_t* U, const uint32_t* C, uint32_t anybad, uint64_t badlo, uint64_t badhi, uint64_t badtop,
+                           uint64_t seed, uint64_t thr, Emit&& emit, std::integer_sequence<int, O...>) {
+    const uint32_t lim = early_limit(thr);
+    (
+        [&] {
+            const Mmh3Open open = PosOps<K, P, O>::template hash_open<PLAIN>(U, C, seed);
+            if constexpr (EARLY) {
+                if (!any_lane(early_may_keep(open, lim))) return;
+            }
+            const uint64_t h = mmh3_close<PLAIN>(open);
+            bool ok = (h - 1) < thr;                          // h != 0 (signature.rs:50) and h <= thr (minhash.rs:319)
+            if (anybad != 0) {
+                // any invalid byte in [O, O+K) kills the k-mer (signature.rs:271-286, force=true)
+                uint64_t lo, hi;                              // bits [O, O+128) of the mask (O < 64: P <= 64)
+                if constexpr (O == 0) { lo = badlo; hi = badhi; }
+                else { lo = (badlo >> O) | (badhi << (64 - O)); hi = (badhi >> O) | (badtop << (64 - O)); }
+                const uint64_t mlo = K >= 64 ? ~0ull : ((1ull << K) - 1);
+                const uint64_t mhi = K >= 128 ? ~0ull : K > 64 ? ((1ull << (K - 64)) - 1) : 0;
+                if ((lo & mlo) | (hi & mhi)) ok = false;
+            }
+            if (ok) emit(O, h);
+        }(),
+        ...);
+}
+
+// process_lane for a staged window.  `dirty` (the tile's flag) MUST be wave-uniform on the device.
+template <int K, int P, bool EARLY = true, bool PLAIN = false, class Emit>
+SMG_HD void process_lane_staged(const uint32_t* U, const uint32_t* C, bool dirty, uint64_t seed, uint64_t thr, Emit&& emit) {
+    using G = LaneGeom<K, P>;
+    uint32_t anybad = 0;
+    uint64_t badlo = 0, badhi = 0, badtop = 0;
+    if (dirty) {
+#pragma unroll
+        for (int i = 0; i < G::NW; ++i) {
+            const uint32_t u = U[i];
+            uint32_t bad = perm_b32(0u, LUT_SELF, (u >> 1) & 0x03030303u) ^ u;
+            if (i == G::NW - 1 && (G::NBYTES % 4) != 0)      // ignore slack bytes past the lane's window
+                bad &= (1u << (8 * (G::NBYTES % 4))) - 1u;
+            anybad |= bad;
+        }
+        if (anybad != 0) lane_bad_bits<K, P>(U, badlo, badhi, badtop);
+    }
+    lane_positions<K, P, EARLY, PLAIN>(U, C, anybad, badlo, badhi, badtop, seed, thr, static_cast<Emit&&>(emit),
+                                       std::make_integer_sequence<int, P>{});
+}
+
 }  // namespace smg

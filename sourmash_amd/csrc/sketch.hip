@@ -8,7 +8,10 @@
 // sequence is cut into tiles of 256 lanes x P positions; the tile's bytes (+ a
 // K-1 byte halo) are staged once through LDS with 16-byte coalesced loads, each
 // lane pulls its P+K-1 byte window into registers with ds_read_b128 and runs
-// smg::process_lane (kmer_core.hpp).  Kept hashes (about 1 in `scaled`) are
+// smg::process_lane (kmer_core.hpp).  The appending form does the per-byte work
+// (upper-casing, complement, validity) where the tile is staged: the tile goes
+// to LDS twice, upper-cased and complemented, with one dirty flag per tile, and
+// the lanes read both (process_lane_staged).  Kept hashes (about 1 in `scaled`) are
 // appended to a per-workgroup LDS buffer and flushed to HBM with one global
 // atomic per flush, so the single output counter sees a few thousand atomics
 // per launch instead of one per kept hash.

@@ -24,6 +24,11 @@ constexpr bool sk_plain_mul(int k, bool dense) {
     if (dense) return k == 1 || k == 5 || k == 8 || k == 25 || k == 28 || k == 81 || k == 82 || k == 84;
     return k == 50 || k == 51;
 }
+// The appending form stages the tile upper-cased and complemented and has the lanes read both from LDS (kmer_core.hpp,
+// process_lane_staged).  An instantiation that would run fewer waves per SIMD that way stays on process_lane: k <= 11, where the
+// second copy's 4 KiB of LDS take the seventh workgroup of a CU, and k = 18, 20 and 30, which need a few registers more and
+// cross a step of the register file (profiles/strand_lds_kernel_resources.txt).
+constexpr bool sk_staged(int k) { return k > 11 && k != 18 && k != 20 && k != 30; }
 
 // DENSE == false: append kept hashes (unordered) to out, count in *out_count.
 // DENSE == true : out[i] = hash of the k-mer starting at i (out pre-zeroed by the
@@ -35,14 +40,14 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
     uint64_t n_tiles, uint32_t skip) {
     // seq is 16-byte aligned; its first `skip` (< 16) bytes precede the caller's buffer and are
     // treated as invalid.  len includes them.  DENSE positions are reported relative to seq + skip.
-    using G = LaneGeom<K, P>;
-    constexpr int TILE = SK_BLOCK * P;                       // start positions per tile
-    constexpr int LANE_RD = ((G::NW + 3) / 4) * 4;           // dwords each lane reads (whole b128s)
-    constexpr int IN_DW = (SK_BLOCK - 1) * (P / 4) + LANE_RD;  // dwords the tile needs in LDS
-    constexpr int IN_CHUNKS = (IN_DW + 3) / 4;               // 16-byte chunks to stage
+    using T = TileGeom<K, P, SK_BLOCK>;
+    constexpr int TILE = T::TILE, LANE_RD = T::LANE_RD, IN_CHUNKS = T::IN_CHUNKS;
+    constexpr bool STAGED = !DENSE && sk_staged(K);          // per-byte work at staging, U and C from LDS
     static_assert(P % 4 == 0, "lane runs must start dword aligned");
 
     __shared__ __attribute__((aligned(16))) uint32_t s_in[IN_CHUNKS * 4];
+    __shared__ __attribute__((aligned(16))) uint32_t s_comp[STAGED ? IN_CHUNKS * 4 : 4];   // complement of s_in, byte for byte
+    __shared__ unsigned int s_dirty;                          // some staged byte of the tile is not ACGT
     __shared__ uint64_t s_out[SK_OUT_CAP];
     __shared__ unsigned int s_cnt;
     __shared__ unsigned long long s_base;
@@ -52,10 +57,21 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
 
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t base = tile * (uint64_t)TILE;
+        if constexpr (STAGED) {
+            if (tid == 0) s_dirty = 0;   // its readers of the previous tile are behind that tile's flush barrier
+        }
         __syncthreads();   // previous tile's readers are done with s_in; s_cnt reset visible
         // ---- stage TILE + halo bytes: coalesced 16-byte loads, zero fill past the end ----
         for (int c = tid; c < IN_CHUNKS; c += SK_BLOCK) {
             const uint64_t off = base + (uint64_t)c * 16;
+            if constexpr (STAGED) {
+                uint32_t w[4], cw[4];
+                load_chunk(seq, off, len, skip, w);
+                if (stage_chunk(w, cw)) s_dirty = 1;
+                *reinterpret_cast<uint4*>(&s_comp[c * 4]) = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+                *reinterpret_cast<uint4*>(&s_in[c * 4]) = make_uint4(w[0], w[1], w[2], w[3]);
+                continue;
+            }
             uint4 v = make_uint4(0, 0, 0, 0);
             if (off + 16 <= len) {
                 v = *reinterpret_cast<const uint4*>(seq + off);
@@ -86,7 +102,7 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
                 raw[4 * i] = p32[0]; raw[4 * i + 1] = p32[1]; raw[4 * i + 2] = p32[2]; raw[4 * i + 3] = p32[3];
             }
         }
-        process_lane<K, P, !DENSE, sk_plain_mul(K, DENSE)>(raw, seed, thr, [&](int o, uint64_t h) {
+        auto emit = [&](int o, uint64_t h) {
             if constexpr (DENSE) {
                 const uint64_t pos = base + (uint64_t)tid * P + (uint64_t)o - skip;   // valid k-mers never start in the prefix
                 if (pos < out_cap) out[pos] = h;
@@ -99,7 +115,21 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
                 const unsigned long long g = atomicAdd(out_count, 1ull);
                 if (g < out_cap) out[g] = h;
             }
-        });
+        };
+        if constexpr (STAGED) {
+            static_assert(!STAGED || P == 16, "the staged form reads whole 16-byte groups");
+            uint32_t comp[LANE_RD];
+            const uint4* cp = reinterpret_cast<const uint4*>(&s_comp[tid * (P / 4)]);
+#pragma unroll
+            for (int i = 0; i < LANE_RD / 4; ++i) {
+                const uint4 v = cp[i];
+                comp[4 * i] = v.x; comp[4 * i + 1] = v.y; comp[4 * i + 2] = v.z; comp[4 * i + 3] = v.w;
+            }
+            const bool dirty = __builtin_amdgcn_readfirstlane(s_dirty) != 0;
+            process_lane_staged<K, P, true, sk_plain_mul(K, false)>(raw, comp, dirty, seed, thr, emit);
+        } else {
+            process_lane<K, P, !DENSE, sk_plain_mul(K, DENSE)>(raw, seed, thr, emit);
+        }
         if constexpr (DENSE) continue;
         // ---- flush the LDS buffer when it is at least half full ----
         __syncthreads();

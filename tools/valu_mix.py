@@ -17,7 +17,11 @@ instruction MIX.  Round 1-3 carried that average as a constant (3.76) from a one
 The hot-path instruction count per k-mer is printed next to the counter value (116.5 per k-mer, profiles/r03_pmc.txt) as a check
 that the split is the right one.
 
-usage: python tools/valu_mix.py [--keep-asm PATH]"""
+A cold block may also be placed out of line: the branch then goes to a label outside the loop's span that holds nothing but an
+`s_branch` back to a later point of the loop (hipcc lays the clean-tile skip of the staged form and the no-tie skip out this way).
+Such a branch is followed through, so the region it skips is found as for a direct one.
+
+usage: python tools/valu_mix.py [--keep-asm PATH] [--csrc DIR --out PATH]   (another tree's csrc, e.g. the parent's, for comparison)"""
 import json
 import os
 import re
@@ -70,11 +74,15 @@ def opcode_cost(op, costs):
 
 def main():
     keep = sys.argv[sys.argv.index("--keep-asm") + 1] if "--keep-asm" in sys.argv else None
+    csrc = sys.argv[sys.argv.index("--csrc") + 1] if "--csrc" in sys.argv else CSRC
+    dest = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
+    if csrc != CSRC and not dest:
+        sys.exit("--csrc needs --out: profiles/valu_mix_sketch.json belongs to this tree's sources")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     with tempfile.TemporaryDirectory() as td:
         asm = keep or os.path.join(td, "sketch.s")
         subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-S",
-                               os.path.join(CSRC, "sketch.hip"), "-o", asm], stderr=subprocess.DEVNULL)
+                               os.path.join(csrc, "sketch.hip"), "-o", asm], stderr=subprocess.DEVNULL)
         lines = open(asm).read().splitlines()
     start = next(i for i, ln in enumerate(lines) if ln.startswith("_ZN3smg") and KERNEL in ln and ln.rstrip().endswith(tuple(": ;")) or (KERNEL in ln and re.match(r"^_ZN3smg\S+:", ln)))
     body = []
@@ -104,15 +112,24 @@ def main():
             if best is None or span > best[1] - best[0]:
                 best = (label_at[m.group(1)], i)
     lo, hi = best
+
+    def through(label):
+        "the label a branch to `label` ends at: an out-of-line block holding only `s_branch X` is followed to X"
+        j = label_at.get(label)
+        while j is not None and j + 1 < len(items) and items[j + 1][0] == "label":
+            j += 1
+        m = re.match(r"s_branch\s+(\.LBB\d+_\d+)$", items[j + 1][1]) if j is not None and j + 1 < len(items) else None
+        return m.group(1) if m and not lo <= j <= hi else label
     # forward regions skipped by a wave-level branch (class 1), or entered only by the lanes of an exec mask that may be empty
     # (s_cbranch_execz: class 2 -- appending a kept hash, 1 position in 1,000; flushing the workgroup's buffer)
     cold = [0] * len(items)
     for i in range(lo, hi):
         k, t = items[i]
         m = re.match(r"s_cbranch_(vccz|vccnz|scc0|scc1|execz)\s+(\.LBB\d+_\d+)", t) if k == "inst" else None
-        if m and m.group(2) in label_at and i < label_at[m.group(2)] <= hi:
+        target = through(m.group(2)) if m else None
+        if m and target in label_at and i < label_at[target] <= hi:
             cls = 2 if m.group(1) == "execz" else 1
-            for j in range(i + 1, label_at[m.group(2)]):
+            for j in range(i + 1, label_at[target]):
                 cold[j] = cold[j] or cls
     costs = ubench_costs()
     parts = {"hot": {}, "wave_conditional": {}, "lane_conditional": {}}
@@ -150,7 +167,7 @@ def main():
     out["mix_cycles_per_valu_inst"] = round(tot_c / tot_n, 3)
     half = sum(c["count"] for c in out["hot"]["opcodes"].values() if c["cycles_each"] > 3.5)
     out["hot_half_rate_fraction"] = round(half / out["hot"]["valu_insts_per_trip"], 3)
-    path = os.path.join(ROOT, "profiles", "valu_mix_sketch.json")
+    path = dest or os.path.join(ROOT, "profiles", "valu_mix_sketch.json")
     with open(path, "w") as f:
         json.dump(out, f, indent=1)
     print(f"{path}: hot path {out['hot']['valu_insts_per_kmer']} VALU / k-mer at {out['hot']['cycles_per_inst']} cycles, wave-conditional "
