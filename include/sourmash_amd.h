@@ -318,6 +318,32 @@ uint64_t smgpu_sketch_workspace_bytes(uint64_t out_capacity);
 uint64_t smgpu_sketch_dna_raw(const uint8_t *d_seq, uint64_t len, uint32_t ksize, uint64_t seed, uint64_t max_hash,
                               uint64_t *d_out, uint64_t out_capacity, uint64_t *d_result, void *d_workspace,
                               uint64_t workspace_bytes, void *stream);
+/* ---- one sketch per record (csrc/sketch_records.hip; `sourmash sketch dna --singleton`, src/sourmash/command_sketch.py:712-739) ----
+ * Records are described by d_starts[0 .. n_records], an ascending device array: record r is the bytes
+ * [d_starts[r], d_starts[r + 1]) of d_seq, d_starts[n_records] <= len; records may touch without a separator byte.  A k-mer
+ * counts for the record it lies in entirely; k-mers that span two records, or lie outside all of them, are dropped.
+ * Scratch size of smgpu_sketch_records_raw for a capacity of kept (hash, position) pairs. */
+uint64_t smgpu_sketch_records_workspace_bytes(uint64_t pair_capacity, uint64_t n_records);
+/* d_seq[0,len) ASCII (any alignment) -> the CSR of its records: row r = the sorted distinct hashes (1 <= h <= max_hash;
+ * max_hash 0 = keep all) of the canonical k-mers inside record r, in d_hashes[d_offsets[r], d_offsets[r + 1]); d_abunds
+ * (NULL = flat) their multiplicities.  ksize 1 .. 88.  capacity: entries of d_hashes / d_abunds and kept pairs the workspace
+ * holds; d_offsets: n_records + 1 entries.  d_result (device, 4 x u64): [0] kept k-mer occurrences, [1] entries, [3] non-zero
+ * when the starts are refused.  Synchronises the stream twice (the sort needs the kept count).  Returns the entries, or
+ * UINT64_MAX with an error set: starts not ascending or ending behind len; or more pairs kept than capacity -- the error says
+ * so and names the count (also in d_result[0]), and the caller retries with a larger buffer. */
+uint64_t smgpu_sketch_records_raw(const uint8_t *d_seq, uint64_t len, const uint64_t *d_starts, uint64_t n_records,
+                                  uint32_t ksize, uint64_t seed, uint64_t max_hash, uint64_t *d_hashes, uint64_t *d_abunds,
+                                  uint64_t capacity, uint64_t *d_offsets, uint64_t *d_result, void *d_workspace,
+                                  uint64_t workspace_bytes, void *stream);
+/* Only its k-mer kernel (no assign, no sort): every kept hash appended unordered to d_hashes and the position of its k-mer's
+ * first byte in d_seq to d_positions; the count is added to *d_count (device u64, caller zeroes).  Fully asynchronous. */
+void smgpu_sketch_records_kernel_raw(const uint8_t *d_seq, uint64_t len, uint32_t ksize, uint64_t seed, uint64_t max_hash,
+                                     uint64_t *d_hashes, uint64_t *d_positions, uint64_t capacity, uint64_t *d_count, void *stream);
+/* Every record of a FASTA / FASTQ file (plain or gzip, at most 2 GiB of text, resident as a whole) as a signature of its own,
+ * holding every sketch of `params` (DNA, scaled, ksizes 1 .. 88): the device parses the file and reports where the records
+ * start, one kernel pass per sketch covers all records.  Names are the header lines behind '>' / '@'.  *n = records.  Returns
+ * an array of *n signature handles (ownership as for smgpu_sketch_files). */
+SourmashSignature **smgpu_sketch_file_singleton(const char *path, const SourmashComputeParameters *params, uintptr_t *n);
 /* Only the k-mer kernel (no sort): appends kept hashes unordered to d_out, adds the
  * count to *d_count (device u64, caller zeroes).  Fully asynchronous. */
 void smgpu_sketch_dna_kernel_raw(const uint8_t *d_seq, uint64_t len, uint32_t ksize, uint64_t seed, uint64_t max_hash,
@@ -487,6 +513,15 @@ void smgpu_collection_params(const SmgpuCollection *ptr, uint32_t *ksize, uint32
 SmgpuSketchSet *smgpu_sketchset_from_collection(const SmgpuCollection *ptr);
 SmgpuSketchSet *smgpu_sketchset_load(const char *const *paths, uintptr_t n_paths, uint32_t ksize, const char *moltype,
                                      uint64_t scaled, uint32_t n_threads);
+/* The records of a device buffer (smgpu_sketch_records_raw describes them) as a set that owns its CSR: flat scaled DNA
+ * sketches, ksize 1 .. 88.  The pair buffer is sized from len / scaled; when repetitive input exceeds the estimate the call
+ * is repeated once with the count.  Work is enqueued on the library's stream: the caller's writes to d_seq / d_starts must
+ * have completed. */
+SmgpuSketchSet *smgpu_sketchset_sketch_records(const uint8_t *d_seq, uint64_t len, const uint64_t *d_starts, uint64_t n_records,
+                                               uint32_t ksize, uint64_t seed, uint64_t scaled);
+/* The records of a FASTA / FASTQ file (plain or gzip, at most 2 GiB of text) as such a set; the manifest rows carry each
+ * record's name and the file name. */
+SmgpuSketchSet *smgpu_sketchset_sketch_file(const char *path, uint32_t ksize, uint64_t seed, uint64_t scaled);
 /* rows[0..n) of a loaded set as a new set: row gather on the device, manifest rows follow.  Replaces the object loop of
  * Index.counter_gather (src/sourmash/index/__init__.py:302-320: `for result in self.prefetch(...): counter.add(
  * result.signature, ...)`): the rows that pass the prefetch become the counter's database without leaving HBM. */

@@ -83,6 +83,30 @@ hipError_t tag_gather_launch(const uint64_t* d_src, const TagSegment* d_segs, ui
 hipError_t sort_unique(uint64_t* d_keys, uint64_t n, uint64_t* d_out, uint64_t* d_counts, uint64_t* d_n_out,
                        void* d_temp, size_t temp_bytes, int bits, hipStream_t stream);
 
+// (key, value) pairs sorted by the low `bits` bits of the key (stable), and runs of equal (a, b) pairs with their lengths
+size_t sort_pairs_temp_bytes(uint64_t n);
+hipError_t sort_pairs(const uint64_t* d_keys_in, uint64_t* d_keys_out, const uint64_t* d_vals_in, uint64_t* d_vals_out, uint64_t n,
+                      int bits, void* d_temp, size_t temp_bytes, hipStream_t stream);
+size_t rle_pairs_temp_bytes(uint64_t n);
+hipError_t rle_pairs(const uint64_t* d_a, const uint64_t* d_b, uint64_t n, uint64_t* d_out_a, uint64_t* d_out_b, uint64_t* d_counts,
+                     uint64_t* d_n_out, void* d_temp, size_t temp_bytes, hipStream_t stream);
+
+// ---- sketch_records.hip (one sketch per record of a buffer: CSR rows) -----------------------------------------------------
+// Every hash h of a canonical DNA k-mer (1 <= k <= 88) of d_seq[0,len) with 1 <= h <= thr appended to d_hash, the position of the
+// k-mer's first byte to d_pos (unordered); *d_count += pairs (keeps counting past `cap`, pairs past cap are dropped).
+hipError_t records_pairs_launch(const uint8_t* d_seq, uint64_t len, uint32_t k, uint64_t seed, uint64_t thr, uint64_t* d_hash,
+                                uint64_t* d_pos, unsigned long long* d_count, uint64_t cap, hipStream_t stream);
+// *d_bad |= 1 if d_starts[0 .. n_records] is not ascending, |= 2 if d_starts[n_records] > len
+hipError_t records_check_starts_launch(const uint64_t* d_starts, uint64_t n_records, uint64_t len, unsigned long long* d_bad,
+                                       hipStream_t stream);
+size_t records_csr_temp_bytes(uint64_t n_pairs);
+// n_pairs (hash, position) pairs -> the CSR of the records d_starts describes (records_core.hpp: rec_assign): row r = sorted
+// distinct hashes of the k-mers inside record r, d_abunds (may be null) their multiplicities, d_offsets[0 .. n_records],
+// *d_n_out = entries.  The pair arrays are clobbered.  Asynchronous: no size is read back.
+hipError_t records_csr_launch(uint64_t* d_pair_hash, uint64_t* d_pair_pos, uint64_t n_pairs, const uint64_t* d_starts, uint64_t n_records,
+                              uint32_t k, uint64_t max_hash, uint64_t* d_hashes, uint64_t* d_abunds, uint64_t* d_offsets, uint64_t* d_n_out,
+                              void* d_temp, size_t temp_bytes, hipStream_t stream);
+
 // ---- synth.hip --------------------------------------------------------------------
 hipError_t synth_dna_launch(uint8_t* d_out, uint64_t start, uint64_t n, uint64_t seed, uint64_t record_len,
                             hipStream_t stream);

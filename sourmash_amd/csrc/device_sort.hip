@@ -12,6 +12,7 @@
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_run_length_encode.hpp>
+#include <rocprim/iterator/zip_iterator.hpp>
 #include "device_api.hpp"
 
 namespace smg {
@@ -57,6 +58,42 @@ hipError_t sort_unique(uint64_t* d_keys, uint64_t n, uint64_t* d_out, uint64_t* 
     e = rocprim::run_length_encode(prim, prim_bytes, sorted, (unsigned int)n, d_out,
                                    d_counts ? d_counts : counts_scratch, d_n_out, stream);
     return e;
+}
+
+// ---- (key, value) pairs: the wide form of the per-record sketches (sketch_records.hip), where record number and hash do not
+// fit one 64-bit key.  The radix sort is stable, so sorting by hash and then by record orders the pairs by (record, hash).
+size_t sort_pairs_temp_bytes(uint64_t n) {
+    size_t bytes = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint64_t*)nullptr,
+                                    (uint64_t*)nullptr, (size_t)(n ? n : 1), 0u, 64u, (hipStream_t)0);
+    return bytes;
+}
+
+hipError_t sort_pairs(const uint64_t* d_keys_in, uint64_t* d_keys_out, const uint64_t* d_vals_in, uint64_t* d_vals_out, uint64_t n,
+                      int bits, void* d_temp, size_t temp_bytes, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (temp_bytes < sort_pairs_temp_bytes(n)) return hipErrorInvalidValue;
+    if (bits < 1) bits = 1;
+    if (bits > 64) bits = 64;
+    return rocprim::radix_sort_pairs(d_temp, temp_bytes, d_keys_in, d_keys_out, d_vals_in, d_vals_out, (size_t)n, 0u, (unsigned)bits, stream);
+}
+
+size_t rle_pairs_temp_bytes(uint64_t n) {
+    size_t bytes = 0;
+    auto in = rocprim::make_zip_iterator(rocprim::make_tuple((const uint64_t*)nullptr, (const uint64_t*)nullptr));
+    auto out = rocprim::make_zip_iterator(rocprim::make_tuple((uint64_t*)nullptr, (uint64_t*)nullptr));
+    (void)rocprim::run_length_encode(nullptr, bytes, in, (unsigned int)(n ? n : 1), out, (uint64_t*)nullptr, (uint64_t*)nullptr, (hipStream_t)0);
+    return bytes;
+}
+
+// runs of equal (a[i], b[i]) -> (out_a, out_b)[0, *d_n_out) and their lengths
+hipError_t rle_pairs(const uint64_t* d_a, const uint64_t* d_b, uint64_t n, uint64_t* d_out_a, uint64_t* d_out_b, uint64_t* d_counts,
+                     uint64_t* d_n_out, void* d_temp, size_t temp_bytes, hipStream_t stream) {
+    if (n == 0) return hipMemsetAsync(d_n_out, 0, 8, stream);
+    if (n > 0xffffffffull || temp_bytes < rle_pairs_temp_bytes(n)) return hipErrorInvalidValue;
+    auto in = rocprim::make_zip_iterator(rocprim::make_tuple(d_a, d_b));
+    auto out = rocprim::make_zip_iterator(rocprim::make_tuple(d_out_a, d_out_b));
+    return rocprim::run_length_encode(d_temp, temp_bytes, in, (unsigned int)n, out, d_counts, d_n_out, stream);
 }
 
 // Many small hash lists sorted as ONE: list s (src[seg.src, seg.src + seg.n)) is copied to dst[seg.dst, ...) with its number in

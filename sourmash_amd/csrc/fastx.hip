@@ -182,7 +182,8 @@ __global__ __launch_bounds__(1024) void fx_offsets_kernel(const BlockSum* __rest
                                                           const uint8_t* __restrict__ raw, uint64_t n, const uint8_t* __restrict__ carry,
                                                           uint8_t* __restrict__ carry_out, uint8_t* __restrict__ entry,
                                                           unsigned long long* __restrict__ block_off, unsigned long long* __restrict__ total,
-                                                          unsigned long long* __restrict__ n_records) {
+                                                          unsigned long long* __restrict__ n_records,
+                                                          unsigned long long* __restrict__ block_rec) {
     __shared__ unsigned long long part[1024];
     __shared__ uint32_t st[1024];
     const unsigned per = (n_blocks + 1023) / 1024;
@@ -240,34 +241,62 @@ __global__ __launch_bounds__(1024) void fx_offsets_kernel(const BlockSum* __rest
         __syncthreads();
     }
     if (threadIdx.x == 0 && part[0]) atomicAdd(n_records, part[0]);
+    if (!block_rec) return;
+    // block_rec[i] = header lines in front of block i (the ordinal of its first record): one more prefix over the same scratch
+    __syncthreads();
+    part[threadIdx.x] = recs;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const unsigned long long v = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    unsigned long long ord = threadIdx.x ? part[threadIdx.x - 1] : 0;
+    for (unsigned i = lo; i < hi; ++i) {
+        block_rec[i] = ord;
+        ord += fastq ? sums[i].hdr[entry[i] & 3u] : sums[i].hdr[0];
+    }
 }
 
 // every block: flags from its entry state, compacted in LDS, written out contiguously
 __global__ __launch_bounds__(FX_THREADS) void fx_scatter_kernel(const uint8_t* __restrict__ raw, uint64_t n, int fastq,
                                                                  const uint8_t* __restrict__ carry, const uint8_t* __restrict__ entry,
-                                                                 const unsigned long long* __restrict__ block_off, uint8_t* __restrict__ out) {
+                                                                 const unsigned long long* __restrict__ block_off, uint8_t* __restrict__ out,
+                                                                 const unsigned long long* __restrict__ block_rec,
+                                                                 unsigned long long* __restrict__ rec_starts, uint64_t rec_cap) {
     __shared__ uint8_t s_out[FX_BLOCK_BYTES];
     __shared__ uint32_t s_wave[FX_THREADS / 64];
     const uint64_t base = (uint64_t)blockIdx.x * FX_BLOCK_BYTES + (uint64_t)threadIdx.x * FX_PER_THREAD;
     uint8_t bytes[FX_PER_THREAD];
     const LaneBits b = lane_bits(raw, base, n, carry[1], bytes);
     const uint32_t e = entry[blockIdx.x];
-    uint32_t mask, dummy;
+    uint32_t mask, dummy, hdr;                                   // hdr: the kept header bytes among mask
     if (!fastq) {
         uint32_t m1, m2, kind;
         fasta_masks(b, &m1, &m2, &kind);
         const uint32_t inh = block_excl<true>(kind, s_wave, &dummy);
         mask = (inh ? inh : e) == 1u ? m1 : m2;
+        hdr = b.ls & b.gt;
     } else {
-        uint32_t M[4], hm;
+        uint32_t M[4];
         fastq_classes(b, M);
         const uint32_t r = block_excl<false>(__popc(b.ls), s_wave, &dummy);
-        mask = fastq_keep(b, M, (e + r) & 3u, &hm);
+        mask = fastq_keep(b, M, (e + r) & 3u, &hdr);
     }
     const uint32_t cnt = __popc(mask);
     __syncthreads();                                             // s_wave is reused
     uint32_t total;
     unsigned pos = block_excl<false>(cnt, s_wave, &total);
+    if (rec_starts) {                                            // the j-th record starts just behind the j-th kept header byte
+        __syncthreads();
+        unsigned long long ord = block_rec[blockIdx.x] + block_excl<false>(__popc(hdr), s_wave, &dummy);
+        const unsigned long long at = block_off[blockIdx.x] + pos;
+        for (uint32_t h = hdr; h; h &= h - 1u, ++ord) {
+            const uint32_t below = (h & (0u - h)) - 1u;
+            if (ord < rec_cap) rec_starts[ord] = at + __popc(mask & below) + 1u;
+        }
+    }
 #pragma unroll
     for (int j = 0; j < FX_PER_THREAD; ++j)
         if (mask & (1u << j)) s_out[pos++] = bytes[j];
@@ -292,25 +321,32 @@ size_t fastx_temp_bytes(uint64_t max_chunk) {
     const uint64_t n_blocks = (max_chunk + FX_BLOCK_BYTES - 1) / FX_BLOCK_BYTES + 1;
     return align256(n_blocks * sizeof(BlockSum)) + align256(n_blocks) + align256(n_blocks * 8) + 256;
 }
+// ... and with the record starts: [first record ordinal of every block u64] behind it
+size_t fastx_records_temp_bytes(uint64_t max_chunk) {
+    const uint64_t n_blocks = (max_chunk + FX_BLOCK_BYTES - 1) / FX_BLOCK_BYTES + 1;
+    return fastx_temp_bytes(max_chunk) + align256(n_blocks * 8);
+}
 
 // d_state: unused since round 6 (the per-byte states are never materialised); kept in the signature for the callers' scratch layout
 hipError_t fastx_compact_launch(const uint8_t* d_raw, uint64_t n, int fastq, uint8_t* d_carry, uint8_t* d_state,
                                 uint8_t* d_out, unsigned long long* d_n_out, unsigned long long* d_n_records,
-                                void* d_temp, size_t temp_bytes, hipStream_t stream, bool last_piece) {
+                                void* d_temp, size_t temp_bytes, hipStream_t stream, bool last_piece,
+                                unsigned long long* d_record_starts, uint64_t record_cap) {
     (void)d_state;
     if (n == 0) return hipMemsetAsync(d_n_out, 0, 8, stream);
-    if (temp_bytes < fastx_temp_bytes(n)) return hipErrorInvalidValue;
+    if (temp_bytes < (d_record_starts ? fastx_records_temp_bytes(n) : fastx_temp_bytes(n))) return hipErrorInvalidValue;
     const uint64_t n_blocks = (n + FX_BLOCK_BYTES - 1) / FX_BLOCK_BYTES;
     if (n_blocks > 0x7fffffffull) return hipErrorInvalidValue;
     BlockSum* sums = reinterpret_cast<BlockSum*>(d_temp);
     uint8_t* entry = reinterpret_cast<uint8_t*>((char*)d_temp + align256((n_blocks + 1) * sizeof(BlockSum)));
     unsigned long long* block_off = reinterpret_cast<unsigned long long*>((char*)entry + align256(n_blocks + 1));
+    unsigned long long* block_rec = d_record_starts ? reinterpret_cast<unsigned long long*>((char*)d_temp + fastx_temp_bytes(n)) : nullptr;
     // the carry is read (first byte) and rewritten (last byte) by the same launches: go through a second slot
     hipLaunchKernelGGL(fx_summary_kernel, dim3((unsigned)n_blocks), dim3(FX_THREADS), 0, stream, d_raw, n, fastq, d_carry, sums);
     hipLaunchKernelGGL(fx_offsets_kernel, dim3(1), dim3(1024), 0, stream, (const BlockSum*)sums, (unsigned)n_blocks, fastq, d_raw, n, d_carry,
-                       d_carry + 2, entry, block_off, d_n_out, d_n_records);
+                       d_carry + 2, entry, block_off, d_n_out, d_n_records, block_rec);
     hipLaunchKernelGGL(fx_scatter_kernel, dim3((unsigned)n_blocks), dim3(FX_THREADS), 0, stream, d_raw, n, fastq, d_carry, (const uint8_t*)entry,
-                       (const unsigned long long*)block_off, d_out);
+                       (const unsigned long long*)block_off, d_out, (const unsigned long long*)block_rec, d_record_starts, record_cap);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || last_piece) return e;
     return hipMemcpyAsync(d_carry, d_carry + 2, 2, hipMemcpyDeviceToDevice, stream);

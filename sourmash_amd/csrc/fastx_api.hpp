@@ -15,7 +15,12 @@ size_t fastx_temp_bytes(uint64_t max_chunk);
 // not copied forward (one small copy less in the stream: it matters when a file is a single piece of a few megabytes).
 hipError_t fastx_compact_launch(const uint8_t* d_raw, uint64_t n, int fastq, uint8_t* d_carry, uint8_t* d_state,
                                 uint8_t* d_out, unsigned long long* d_n_out, unsigned long long* d_n_records,
-                                void* d_temp, size_t temp_bytes, hipStream_t stream, bool last_piece = false);
+                                void* d_temp, size_t temp_bytes, hipStream_t stream, bool last_piece = false,
+                                unsigned long long* d_record_starts = nullptr, uint64_t record_cap = 0);
+// With d_record_starts (a single piece: the whole file): d_record_starts[j] = offset in d_out just behind the j-th kept header
+// byte, i.e. where record j's sequence starts, for j < record_cap; d_temp then holds fastx_records_temp_bytes(n) bytes.  The
+// parser reports the records -- the compacted bytes are not searched for the separator, which a sequence line may hold too.
+size_t fastx_records_temp_bytes(uint64_t max_chunk);
 // d_dst[0,halo) = the last `halo` bytes of (d_src[-halo,0) ++ d_src[0,*d_n_new)): the k-1 bytes the next piece
 // must see in front of its own (halo <= 256)
 hipError_t fastx_halo_launch(const uint8_t* d_src, const unsigned long long* d_n_new, int halo, uint8_t* d_dst,

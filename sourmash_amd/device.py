@@ -57,6 +57,13 @@ def synth_dna(n, seed=42, record_len=0, start=0, device="cuda", out=None):
     return out
 
 
+def _records_error(code, message):
+    "the exception of a failed per-record call: starts the library refuses are the caller's ValueError"
+    if "record starts" in message:
+        return ValueError(message)
+    return exceptions_by_code.get(code, SourmashError)(message)
+
+
 class DeviceSketcher:
     """Reusable scratch for sketching device-resident sequence buffers.
 
@@ -105,6 +112,47 @@ class DeviceSketcher:
                 self._reserve(kept + 1024)
                 continue
             raise exceptions_by_code.get(code, SourmashError)(message)
+
+    def sketch_records(self, seq, starts, *, abund=False):
+        """One sketch per record of `seq` in one pass (smgpu_sketch_records_raw, csrc/sketch_records.hip).
+
+        starts: int64 device tensor of n_records + 1 ascending offsets, record r = seq[starts[r]:starts[r + 1]]; records may
+        touch, and a k-mer counts only for the record it lies in entirely.  -> (hashes, offsets[, abunds]): the CSR of
+        sorted distinct kept hashes (int64 tensors of u64 bit patterns; row r is hashes[offsets[r]:offsets[r + 1]]), new
+        tensors.  ksize 1 .. 88.  Starts that are not ascending or end behind the buffer raise ValueError."""
+        torch = self.torch
+        assert seq.dtype == torch.uint8 and seq.is_cuda and seq.is_contiguous()
+        assert starts.dtype == torch.int64 and starts.is_cuda and starts.is_contiguous()
+        if starts.numel() < 1:
+            raise ValueError("record starts: n_records + 1 offsets are needed")
+        n, n_records = seq.numel(), starts.numel() - 1
+        expect = n / max(self.scaled, 1)
+        cap = max(1, min(n, int(expect * 2 + 16 * (expect + 1) ** 0.5) + 4096))   # the slack of the batched ingest (csrc/ingest.hpp)
+        result = torch.zeros(4, dtype=torch.int64, device=seq.device)
+        offsets = _u64(torch, n_records + 1, seq.device)
+        for attempt in range(2):
+            hashes = _u64(torch, cap, seq.device)
+            abunds = _u64(torch, cap, seq.device) if abund else None
+            ws = torch.empty(int(lib.smgpu_sketch_records_workspace_bytes(cap, n_records)), dtype=torch.uint8, device=seq.device)
+            lib.sourmash_err_clear()
+            got = lib.smgpu_sketch_records_raw(_ptr(seq), n, _ptr(starts), n_records, self.ksize, self.seed, self.max_hash,
+                                               _ptr(hashes), _ptr(abunds) if abund else None, cap, _ptr(offsets), _ptr(result),
+                                               _ptr(ws), ws.numel(), _stream(torch))
+            code = lib.sourmash_err_get_last_code()
+            if code == 0:
+                return (hashes[:got], offsets, abunds[:got]) if abund else (hashes[:got], offsets)
+            message = decode_str(lib.sourmash_err_get_last_message())
+            kept = int(result[0].item())
+            if attempt == 0 and kept > cap:                            # repetitive input beat the estimate: grow and retry once
+                cap = kept
+                continue
+            raise _records_error(code, message)
+
+    def records_kernel_only(self, seq, out_hashes, out_positions, count):
+        "Just the (hash, position) kernel of sketch_records: appends to the two arrays, adds to `count` (int64[1], caller zeroes)."
+        torch = self.torch
+        rustcall(lib.smgpu_sketch_records_kernel_raw, _ptr(seq), seq.numel(), self.ksize, self.seed, self.max_hash,
+                 _ptr(out_hashes), _ptr(out_positions), min(out_hashes.numel(), out_positions.numel()), _ptr(count), _stream(torch))
 
     def kernel_only(self, seq, out, count):
         "Just the k-mer kernel (no sort): appends to `out`, adds to `count` (int64[1], caller zeroes)."

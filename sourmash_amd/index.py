@@ -145,6 +145,49 @@ class SketchSet(RustObject):
         return cls._from_objptr(rustcall(lib.smgpu_sketchset_load, arr, n, int(ksize or 0),
                                          moltype.encode() if moltype else None, int(scaled or 0), int(threads)))
 
+    @classmethod
+    def sketch_records(cls, seq, starts, *, ksize, scaled, seed=42):
+        """One flat scaled DNA sketch per record of a device buffer, in one pass (smgpu_sketchset_sketch_records).
+
+        seq: uint8 device tensor; starts: int64 device tensor of n_records + 1 ascending offsets, record r =
+        seq[starts[r]:starts[r + 1]].  ksize 1 .. 88 (longer k-mers: sketch the records one by one)."""
+        from .device import _ptr, _records_error, _torch
+        torch = _torch()
+        assert seq.dtype == torch.uint8 and seq.is_cuda and seq.is_contiguous()
+        assert starts.dtype == torch.int64 and starts.is_cuda and starts.is_contiguous()
+        if starts.numel() < 1:
+            raise ValueError("record starts: n_records + 1 offsets are needed")
+        torch.cuda.current_stream().synchronize()                   # the library works on its own stream
+        lib.sourmash_err_clear()
+        ptr = lib.smgpu_sketchset_sketch_records(_ptr(seq), seq.numel(), _ptr(starts), starts.numel() - 1, int(ksize), int(seed),
+                                                 int(scaled))
+        code = lib.sourmash_err_get_last_code()
+        if code:
+            raise _records_error(code, decode_str(lib.sourmash_err_get_last_message()))
+        return cls._from_objptr(ptr)
+
+    @classmethod
+    def sketch_file(cls, path, *, ksize=31, scaled=1000, seed=42):
+        """One flat scaled DNA sketch per record of a FASTA / FASTQ file (plain or gzip): the device parses the file and
+        sketches every record in one pass (smgpu_sketchset_sketch_file); manifest[row] carries the record's name and the
+        file name.  What that path does not take (k > 88, a file above its size limit) is sketched record by record."""
+        from .sketch import _records_path_takes, read_records
+        path = os.fspath(path)
+        if _records_path_takes(path, [int(ksize)]):
+            return cls._from_objptr(rustcall(lib.smgpu_sketchset_sketch_file, os.fsencode(path), int(ksize), int(seed), int(scaled)))
+        from .minhash import MinHash
+        mhs, names = [], []
+        for name, seq in read_records(path):
+            mh = MinHash(0, int(ksize), scaled=int(scaled), seed=int(seed))
+            mh.add_sequence(seq, True)
+            mhs.append(mh)
+            names.append(name)
+        out = cls(mhs)
+        sizes = out.sizes
+        out._manifest = [dict(internal_location="", md5="", md5short="", ksize=int(ksize), moltype="DNA", num=0, scaled=int(scaled),
+                              n_hashes=int(sizes[i]), with_abundance=False, name=names[i], filename=path) for i in range(len(names))]
+        return out
+
     def __len__(self):
         return self._methodcall(lib.smgpu_sketchset_len)
 

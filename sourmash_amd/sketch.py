@@ -372,14 +372,40 @@ def _add_buffer_to_signature(sig, buf):
             rustcall(lib.signature_push_mh, sig._get_objptr(), mh._get_objptr())
 
 
+RECORDS_MAX_FILE = 2 << 30           # text bytes the per-record path keeps resident (csrc/capi.cpp: RECORDS_MAX_FILE)
+RECORDS_MAX_KSIZE = 88               # the longest k-mer of its kernel (csrc/sketch_kernel.hpp: SK_FAST_MAX_K)
+
+
+def _records_path_takes(path, ksizes):
+    """Whether the one-pass per-record path (csrc/sketch_records.hip) takes this file at these DNA ksizes: every k within
+    its kernel's range and the text within its size limit.  A gzip file's text is bounded from its compressed size
+    (deflate's 1032:1 limit is far away from sequence text: 8:1 is allowed for)."""
+    if not ksizes or any(k < 1 or k > RECORDS_MAX_KSIZE for k in ksizes):
+        return False
+    with open(path, "rb") as fh:
+        gz = fh.read(2) == b"\x1f\x8b"
+        size = fh.seek(0, 2)
+    return size <= (RECORDS_MAX_FILE // 8 if gz else RECORDS_MAX_FILE)
+
+
 def sketch_file(path, param_str=DEFAULTS["dna"], *, name=None, check_sequence=False, singleton=False, moltype="dna",
                 input_is_protein=False):
     """`sourmash sketch dna -p <param_str> <path>` -> list of SourmashSignature.
 
     Default mode (one signature per file, force=True) runs the native streaming ingest
     (smgpu_signature_add_file: C++ FASTA/FASTQ(.gz) reader -> pinned buffers -> GPU, every ksize in one
-    pass); --singleton and --check-sequence go record by record like the reference."""
+    pass).  --singleton with scaled DNA sketches of k <= 88 and a file of at most 2 GiB of text sketches every record
+    in one pass per ksize (smgpu_sketch_file_singleton: the device parses the file and reports the record starts, the
+    records become the rows of one CSR); every other --singleton case -- protein / dayhoff / hp, num sketches, k >= 89,
+    larger files -- and --check-sequence go record by record like the reference, with equal results."""
     params = ComputeParameters.from_param_str(param_str, default_moltype=moltype)
+    if (singleton and not check_sequence and params.dna and params.num_hashes == 0 and params.scaled
+            and _records_path_takes(path, params.ksizes)):
+        n = C.c_size_t(0)
+        ptr = rustcall(lib.smgpu_sketch_file_singleton, str(path).encode("utf-8"), params._get_objptr(), C.byref(n))
+        sigs = [SourmashSignature._from_objptr(ptr[i]) for i in range(n.value)]
+        lib.nodegraph_buffer_free(C.cast(ptr, C.POINTER(C.c_uint8)), max(n.value, 1) * C.sizeof(C.c_void_p))
+        return sigs
     if not singleton and not check_sequence and params.dna:
         sig = SourmashSignature.from_params(params)
         n_records = C.c_uint64(0)
