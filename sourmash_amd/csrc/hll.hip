@@ -7,7 +7,7 @@
 //
 //   p <= 14: each workgroup keeps its own register file in LDS (one u32 per register: ds_max_u32 is native; 64 KiB at p = 14)
 //            and folds it into the device array at the end (read, atomicMax only where larger).  The grid is sized so that
-//            the fold -- 2^p checks per workgroup -- stays a small share of the hashing (hll_kernel.hpp: hll_grid).
+//            the fold -- 2^p checks per workgroup -- stays a small share of the hashing (tile_launch.hpp: lds_grid).
 //   p >= 15: the LDS file would cost occupancy; the update goes to the device array (at most 1 MiB, L2 resident) behind a
 //            read filter.
 // Device registers are u32 (atomicMax has no byte form); hll_pack_launch narrows them to the u8 layout of the host container.
@@ -58,7 +58,7 @@ hipError_t hll_pack_launch(const uint32_t* d_regs, uint32_t n, uint8_t* d_out, h
 hipError_t hll_dna_launch(const uint8_t* d_seq, uint64_t len, uint32_t k, uint32_t p, uint32_t* d_regs, hipStream_t stream) {
     if (k == 0 || len < k) return hipSuccess;
     if (p < 4 || p > 18) return hipErrorInvalidValue;
-    if (k <= (uint32_t)SK_FAST_MAX_K) return hll_launcher(k)(d_seq, len, p, d_regs, stream);
+    if (k <= (uint32_t)SK_FAST_MAX_K) return launcher<HllLaunch>(k)(d_seq, len, p, d_regs, stream);
     if (k > sketch_dna_max_k()) return hipErrorInvalidValue;
     // per-position hashes of up to CHUNK k-mers at a time (8 B each), then the fold
     constexpr uint64_t CHUNK = (uint64_t)16 << 20;

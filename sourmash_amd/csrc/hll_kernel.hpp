@@ -38,11 +38,8 @@ constexpr bool hll_plain_mul(int k, bool lds) { return k == 28 || k == 60 || (k 
 template <int K, int P, bool LDS>
 __global__ __launch_bounds__(SK_BLOCK) void hll_dna_kernel(const uint8_t* __restrict__ seq, uint64_t len, uint32_t p,
                                                            uint32_t* regs, uint64_t n_tiles, uint32_t skip) {
-    using G = LaneGeom<K, P>;
-    constexpr int TILE = SK_BLOCK * P;
-    constexpr int LANE_RD = ((G::NW + 3) / 4) * 4;
-    constexpr int IN_DW = (SK_BLOCK - 1) * (P / 4) + LANE_RD;
-    constexpr int IN_CHUNKS = (IN_DW + 3) / 4;
+    using T = TileGeom<K, P, SK_BLOCK>;
+    constexpr int TILE = T::TILE, LANE_RD = T::LANE_RD, IN_CHUNKS = T::IN_CHUNKS;
     static_assert(P == 16, "lane runs of 16 positions");
 
     __shared__ __attribute__((aligned(16))) uint32_t s_in[IN_CHUNKS * 4];
@@ -57,6 +54,8 @@ __global__ __launch_bounds__(SK_BLOCK) void hll_dna_kernel(const uint8_t* __rest
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t base = tile * (uint64_t)TILE;
         __syncthreads();
+        // stage_tile<IN_CHUNKS, false> (kmer_core.hpp), kept inline: through the function, in either shape of its loader, <19, 16, true>
+        // goes from 80 to 86 VGPRs, <20, 16, false> from 80 to 84, <28, 16, true> from 96 to 98 -- a wave per SIMD each.
         for (int c = tid; c < IN_CHUNKS; c += SK_BLOCK) {
             const uint64_t off = base + (uint64_t)c * 16;
             uint4 v = make_uint4(0, 0, 0, 0);
@@ -67,7 +66,7 @@ __global__ __launch_bounds__(SK_BLOCK) void hll_dna_kernel(const uint8_t* __rest
                 for (uint64_t b = off; b < len; ++b) w[(b - off) >> 2] |= (uint32_t)seq[b] << (8 * ((b - off) & 3));
                 v = make_uint4(w[0], w[1], w[2], w[3]);
             }
-            if (off == 0 && skip) {
+            if (off == 0 && skip) {                      // blank the alignment prefix
                 uint32_t w[4] = {v.x, v.y, v.z, v.w};
                 for (uint32_t b = 0; b < skip; ++b) w[b >> 2] &= ~(0xffu << (8 * (b & 3)));
                 v = make_uint4(w[0], w[1], w[2], w[3]);
@@ -76,12 +75,7 @@ __global__ __launch_bounds__(SK_BLOCK) void hll_dna_kernel(const uint8_t* __rest
         }
         __syncthreads();
         uint32_t raw[LANE_RD];
-        const uint4* wp = reinterpret_cast<const uint4*>(&s_in[tid * (P / 4)]);
-#pragma unroll
-        for (int i = 0; i < LANE_RD / 4; ++i) {
-            const uint4 v = wp[i];
-            raw[4 * i] = v.x; raw[4 * i + 1] = v.y; raw[4 * i + 2] = v.z; raw[4 * i + 3] = v.w;
-        }
+        read_window<LANE_RD, P>(s_in, tid, raw);
         process_lane<K, P, false, hll_plain_mul(K, LDS)>(raw, HLL_SEED, ~0ull, [&](int, uint64_t h) {
             const uint32_t idx = (uint32_t)(h & mask);
             const uint32_t r = hll_rank(h, p);
@@ -98,62 +92,28 @@ __global__ __launch_bounds__(SK_BLOCK) void hll_dna_kernel(const uint8_t* __rest
     }
 }
 
-typedef hipError_t (*hll_launch_fn)(const uint8_t*, uint64_t, uint32_t, uint32_t*, hipStream_t);
-
-// workgroups for a launch: up to 2048 (the sketch kernel's grid), but in the LDS form at least 8 tiles per workgroup, so that
-// the final fold (2^p register checks per workgroup, about one tile's work at p = 14) stays small next to the hashing
-inline unsigned hll_grid(uint64_t n_tiles, bool lds) {
-    uint64_t g = n_tiles < 2048 ? n_tiles : 2048;
-    if (lds && g > 256 && g > n_tiles / 8) g = n_tiles / 8 > 256 ? n_tiles / 8 : 256;
-    return (unsigned)g;
-}
-
-template <int K>
-static hipError_t launch_hll_k(const uint8_t* d_seq, uint64_t len, uint32_t p, uint32_t* d_regs, hipStream_t stream) {
-    constexpr uint64_t TILE = (uint64_t)SK_BLOCK * 16;
-    const uint32_t skip = (uint32_t)((uintptr_t)d_seq & 15);
-    d_seq -= skip;
-    len += skip;
-    const uint64_t n_tiles = (len + TILE - 1) / TILE;
-    if (n_tiles == 0) return hipSuccess;
-    const bool lds = p <= (uint32_t)HLL_LDS_MAX_P;
-    const unsigned grid = hll_grid(n_tiles, lds);
-    if (lds) {
-        const size_t shm = (size_t)4 << p;
-        if (shm > 48 * 1024) {             // more dynamic LDS than a kernel gets unasked: allow the largest form once
-            static hipError_t allowed = hipFuncSetAttribute((const void*)hll_dna_kernel<K, 16, true>,
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 4 << HLL_LDS_MAX_P);
+// The launchers of hll_dna_kernel<K, 16, LDS>, one per ksize: six parts in hll_dense.hip (tile_launch.hpp)
+struct HllLaunch {
+    using fn = hipError_t (*)(const uint8_t*, uint64_t, uint32_t, uint32_t*, hipStream_t);
+    static constexpr int KMAX = SK_FAST_MAX_K;
+    template <int K>
+    static hipError_t launch(const uint8_t* d_seq, uint64_t len, uint32_t p, uint32_t* d_regs, hipStream_t stream) {
+        const TileSpan t = align_to_tiles(d_seq, len, (uint64_t)SK_BLOCK * 16);
+        if (t.n_tiles == 0) return hipSuccess;
+        const bool lds = p <= (uint32_t)HLL_LDS_MAX_P;
+        const unsigned grid = lds_grid(t.n_tiles, lds);      // the fold is 2^p register checks per workgroup
+        if (lds) {
+            const size_t shm = (size_t)4 << p;
+            const hipError_t allowed = allow_dynamic_lds<&hll_dna_kernel<K, 16, true>>(shm, (size_t)4 << HLL_LDS_MAX_P);
             if (allowed != hipSuccess) return allowed;
+            hipLaunchKernelGGL((hll_dna_kernel<K, 16, true>), dim3(grid), dim3(SK_BLOCK), shm, stream, t.seq, t.len, p, d_regs,
+                               t.n_tiles, t.skip);
+        } else {
+            hipLaunchKernelGGL((hll_dna_kernel<K, 16, false>), dim3(grid), dim3(SK_BLOCK), 0, stream, t.seq, t.len, p, d_regs,
+                               t.n_tiles, t.skip);
         }
-        hipLaunchKernelGGL((hll_dna_kernel<K, 16, true>), dim3(grid), dim3(SK_BLOCK), shm, stream, d_seq, len, p, d_regs, n_tiles,
-                           skip);
-    } else {
-        hipLaunchKernelGGL((hll_dna_kernel<K, 16, false>), dim3(grid), dim3(SK_BLOCK), 0, stream, d_seq, len, p, d_regs, n_tiles,
-                           skip);
+        return hipGetLastError();
     }
-    return hipGetLastError();
-}
-template <int K0, int... KS>
-static hll_launch_fn hll_launcher_from(uint32_t k, std::integer_sequence<int, KS...>) {
-    static const hll_launch_fn table[] = {&launch_hll_k<K0 + KS + 1>...};
-    return table[k - K0 - 1];
-}
-// hll_dense.hip, compiled as six parts of up to 16 ksizes each: k = 1 .. 16, ..., 81 .. 88
-hll_launch_fn hll_launcher_0(uint32_t k);
-hll_launch_fn hll_launcher_1(uint32_t k);
-hll_launch_fn hll_launcher_2(uint32_t k);
-hll_launch_fn hll_launcher_3(uint32_t k);
-hll_launch_fn hll_launcher_4(uint32_t k);
-hll_launch_fn hll_launcher_5(uint32_t k);
-inline hll_launch_fn hll_launcher(uint32_t k) {
-    switch ((k - 1u) / 16u) {
-    case 0: return hll_launcher_0(k);
-    case 1: return hll_launcher_1(k);
-    case 2: return hll_launcher_2(k);
-    case 3: return hll_launcher_3(k);
-    case 4: return hll_launcher_4(k);
-    default: return hll_launcher_5(k);
-    }
-}
+};
 
 }  // namespace smg

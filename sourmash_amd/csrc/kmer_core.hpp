@@ -215,46 +215,64 @@ SMG_HD uint32_t early_limit(uint64_t thr) {
 // false only if mmh3_close(open) > thr
 SMG_HD bool early_may_keep(Mmh3Open open, uint32_t lim) { return (uint32_t)(mmh3_close_hi_sum(open) + 1u) <= lim; }
 
-// Process the P start positions of one lane.
-//   raw[NW]  : the lane's window bytes as little-endian dwords (any case, any junk;
-//              bytes past the end of the sequence must be non-ACGT, e.g. 0)
+// Process the P start positions of one lane: the one copy of the validity and position code, behind process_lane and
+// process_lane_staged below.
+//   STAGED == false: raw[NW] holds the lane's window bytes as little-endian dwords (any case, any junk; bytes past the end of the
+//                    sequence must be non-ACGT, e.g. 0); they are upper-cased, complemented and checked here.
+//   STAGED == true : raw is the window already upper-cased, comp its complement (stage_chunk, where the tile is staged); `dirty`
+//                    says whether the tile holds an invalid byte at all, and only then is the window checked.
 //   thr      : keep iff 1 <= h <= thr   (thr = max_hash, or 2^64-1 for num sketches)
 //   emit(o,h): called for every kept k-mer (o = position within the lane's run)
-//
-// EARLY: test the top dword of the hash first and finish it only when some lane of the wave may keep its k-mer
-// (1 wave-step in 16 at scaled = 1000); the result is the same either way.  Dense callers (every hash wanted) turn
-// it off.  PLAIN: the 64-bit constant multiplies of the hash as plain products (murmur3.hpp, mul_c64); the same values.
-template <int K, int P, bool EARLY, bool PLAIN, class Emit, int... O>
-SMG_HD void process_lane_impl(const uint32_t* raw, uint64_t seed, uint64_t thr, Emit&& emit,
-                              std::integer_sequence<int, O...>) {
+// The two prologues and the positions sit in ONE function on purpose: with the prologue in one function and the positions in
+// another the compiler pairs the window's LDS reads differently, and sketch_dna_kernel<18, 16, false> (96 -> 98 VGPRs) and
+// hll_dna_kernel<19, 16, true> (80 -> 82) each lose a wave per SIMD.
+template <int K, int P, bool EARLY, bool PLAIN, bool STAGED, class Emit, int... O>
+SMG_HD void process_window(const uint32_t* raw, const uint32_t* comp, bool dirty, uint64_t seed, uint64_t thr, Emit&& emit,
+                           std::integer_sequence<int, O...>) {
     using G = LaneGeom<K, P>;
     const uint32_t lim = early_limit(thr);
-    uint32_t U[G::NW], C[G::NW];
+    uint32_t Ubuf[STAGED ? 1 : G::NW], Cbuf[STAGED ? 1 : G::NW];
+    const uint32_t* U = STAGED ? raw : Ubuf;
+    const uint32_t* C = STAGED ? comp : Cbuf;
     uint32_t anybad = 0;
+    if constexpr (!STAGED) {
 #pragma unroll
-    for (int i = 0; i < G::NW; ++i) {
-        const uint32_t u = raw[i] & 0xdfdfdfdfu;            // upper-case (signature.rs:214)
-        const uint32_t code = (u >> 1) & 0x03030303u;
-        U[i] = u;
-        C[i] = perm_b32(0u, LUT_COMP, code);                 // encodings.rs:85-101
-        uint32_t bad = perm_b32(0u, LUT_SELF, code) ^ u;     // != 0 where byte not in ACGT (encodings.rs:370-377)
-        if (i == G::NW - 1 && (G::NBYTES % 4) != 0)          // ignore slack bytes past the lane's window
-            bad &= (1u << (8 * (G::NBYTES % 4))) - 1u;
-        anybad |= bad;
+        for (int i = 0; i < G::NW; ++i) {
+            const uint32_t u = raw[i] & 0xdfdfdfdfu;             // upper-case (signature.rs:214)
+            const uint32_t code = (u >> 1) & 0x03030303u;
+            Ubuf[i] = u;
+            Cbuf[i] = perm_b32(0u, LUT_COMP, code);              // encodings.rs:85-101
+            uint32_t bad = perm_b32(0u, LUT_SELF, code) ^ u;     // != 0 where byte not in ACGT (encodings.rs:370-377)
+            if (i == G::NW - 1 && (G::NBYTES % 4) != 0)          // ignore slack bytes past the lane's window
+                bad &= (1u << (8 * (G::NBYTES % 4))) - 1u;
+            anybad |= bad;
+        }
     }
     // bit b of (badlo, badhi, badtop) = window byte b is invalid (192 bits: k <= 128 at P = 16 ... 64).  Rare: built only if needed.
     uint64_t badlo = 0, badhi = 0, badtop = 0;
-    if (anybad != 0) {
+    if (!STAGED || dirty) {                                      // (dirty MUST be wave-uniform on the device)
+        if constexpr (STAGED) {
 #pragma unroll
-        for (int i = 0; i < G::NW; ++i) {
-            const uint32_t u = U[i];
-            const uint32_t code = (u >> 1) & 0x03030303u;
-            uint32_t bad = perm_b32(0u, LUT_SELF, code) ^ u;
-            if (i == G::NW - 1 && (G::NBYTES % 4) != 0) bad &= (1u << (8 * (G::NBYTES % 4))) - 1u;
-            const uint64_t nib = nonzero_bytes4(bad);
-            if (4 * i < 64) badlo |= nib << (4 * i);
-            else if (4 * i < 128) badhi |= nib << (4 * i - 64);
-            else badtop |= nib << (4 * i - 128);
+            for (int i = 0; i < G::NW; ++i) {
+                const uint32_t u = U[i];
+                uint32_t bad = perm_b32(0u, LUT_SELF, (u >> 1) & 0x03030303u) ^ u;
+                if (i == G::NW - 1 && (G::NBYTES % 4) != 0)      // ignore slack bytes past the lane's window
+                    bad &= (1u << (8 * (G::NBYTES % 4))) - 1u;
+                anybad |= bad;
+            }
+        }
+        if (anybad != 0) {
+#pragma unroll
+            for (int i = 0; i < G::NW; ++i) {
+                const uint32_t u = U[i];
+                const uint32_t code = (u >> 1) & 0x03030303u;
+                uint32_t bad = perm_b32(0u, LUT_SELF, code) ^ u;
+                if (i == G::NW - 1 && (G::NBYTES % 4) != 0) bad &= (1u << (8 * (G::NBYTES % 4))) - 1u;
+                const uint64_t nib = nonzero_bytes4(bad);
+                if (4 * i < 64) badlo |= nib << (4 * i);
+                else if (4 * i < 128) badhi |= nib << (4 * i - 64);
+                else badtop |= nib << (4 * i - 128);
+            }
         }
     }
     static_assert(G::NBYTES <= 192 && K <= 128 && P <= 64, "window too long for the 192-bit validity mask");
@@ -280,16 +298,30 @@ SMG_HD void process_lane_impl(const uint32_t* raw, uint64_t seed, uint64_t thr, 
         ...);
 }
 
+// A lane's raw window.  EARLY: test the top dword of the hash first and finish it only when some lane of the wave may keep its
+// k-mer (1 wave-step in 16 at scaled = 1000); the result is the same either way.  Dense callers (every hash wanted) turn it off.
+// PLAIN: the 64-bit constant multiplies of the hash as plain products (murmur3.hpp, mul_c64); the same values.
 template <int K, int P, bool EARLY = true, bool PLAIN = false, class Emit>
 SMG_HD void process_lane(const uint32_t* raw, uint64_t seed, uint64_t thr, Emit&& emit) {
-    process_lane_impl<K, P, EARLY, PLAIN>(raw, seed, thr, static_cast<Emit&&>(emit), std::make_integer_sequence<int, P>{});
+    process_window<K, P, EARLY, PLAIN, false>(raw, nullptr, false, seed, thr, static_cast<Emit&&>(emit),
+                                              std::make_integer_sequence<int, P>{});
+}
+// A staged window: U upper-cased, C its complement.  `dirty` (the tile's flag) MUST be wave-uniform on the device.
+template <int K, int P, bool EARLY = true, bool PLAIN = false, class Emit>
+SMG_HD void process_lane_staged(const uint32_t* U, const uint32_t* C, bool dirty, uint64_t seed, uint64_t thr, Emit&& emit) {
+    process_window<K, P, EARLY, PLAIN, true>(U, C, dirty, seed, thr, static_cast<Emit&&>(emit), std::make_integer_sequence<int, P>{});
 }
 
-// ---- the per-byte work done once, where the tile is staged (the appending form of sketch_kernel.hpp) -------------------------
-// A lane window is 46 bytes at k = 31 for 16 new ones: upper-casing, complement and validity per lane treat every staged byte
-// about 2.9 times.  Here the lane that stages a 16-byte chunk does them for the chunk, the tile goes to LDS twice -- upper-cased
-// and complemented -- and a flag per tile says whether any staged byte is invalid.  A lane of a clean tile reads U and C as they
-// are and does no validity work at all; a lane of a dirty tile rebuilds its bad-byte mask from U, as process_lane does.
+// ---- the tile walk: what every DNA k-mer kernel does around its per-position code ---------------------------------------------
+// A workgroup of BLOCK lanes takes tiles of BLOCK x P start positions.  It stages the tile and its halo into LDS as 16-byte
+// chunks (stage_tile over load_chunk), each lane reads its window back as whole 16-byte groups (read_window) and hashes it, and
+// kept values wait in LDS for one global atomic per flush (LdsSink).
+//
+// STAGED, the per-byte work done once (the appending form of sketch_kernel.hpp): a lane window is 46 bytes at k = 31 for 16 new
+// ones, so upper-casing, complement and validity per lane treat every staged byte about 2.9 times.  Here the lane that stages a
+// 16-byte chunk does them for the chunk, the tile goes to LDS twice -- upper-cased and complemented -- and a flag per tile says
+// whether any staged byte is invalid.  A lane of a clean tile reads U and C as they are and does no validity work at all; a lane
+// of a dirty tile rebuilds its bad-byte mask from U (process_window).
 
 // Geometry of one tile of BLOCK lanes x P positions: what is staged, and what a lane reads back.
 template <int K, int P, int BLOCK>
@@ -335,73 +367,106 @@ SMG_HD uint32_t stage_chunk(uint32_t* w, uint32_t* c) {
     return anybad;
 }
 
-// The two halves of process_lane_impl's validity and position code, for a window that is already upper-cased and complemented
-// (process_lane_impl itself is left as it is: the per-position, multi-sketch and HyperLogLog kernels are built from it).
-// bit b of (badlo, badhi, badtop) = byte b of the upper-cased window U is invalid (192 bits: k <= 128 at P = 16 ... 64)
-template <int K, int P>
-SMG_HD void lane_bad_bits(const uint32_t* U, uint64_t& badlo, uint64_t& badhi, uint64_t& badtop) {
-    using G = LaneGeom<K, P>;
-    static_assert(G::NBYTES <= 192 && K <= 128 && P <= 64, "window too long for the 192-bit validity mask");
-#pragma unroll
-    for (int i = 0; i < G::NW; ++i) {
-        const uint32_t u = U[i];
-        const uint32_t code = (u >> 1) & 0x03030303u;
-        uint32_t bad = perm_b32(0u, LUT_SELF, code) ^ u;
-        if (i == G::NW - 1 && (G::NBYTES % 4) != 0) bad &= (1u << (8 * (G::NBYTES % 4))) - 1u;
-        const uint64_t nib = nonzero_bytes4(bad);
-        if (4 * i < 64) badlo |= nib << (4 * i);
-        else if (4 * i < 128) badhi |= nib << (4 * i - 64);
-        else badtop |= nib << (4 * i - 128);
-    }
+SMG_HD void store_chunk(uint32_t* dst, const uint32_t* w) {      // dst is 16-byte aligned
+#if defined(__HIP_DEVICE_COMPILE__)
+    *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
+#else
+    dst[0] = w[0]; dst[1] = w[1]; dst[2] = w[2]; dst[3] = w[3];
+#endif
 }
 
-// The P positions of a lane whose window is ready: U upper-cased, C its complement, anybad != 0 iff the window holds an invalid
-// byte, and then (badlo, badhi, badtop) says which.
-template <int K, int P, bool EARLY, bool PLAIN, class Emit, int... O>
-SMG_HD void lane_positions(const uint32_t* U, const uint32_t* C, uint32_t anybad, uint64_t badlo, uint64_t badhi, uint64_t badtop,
-                           uint64_t seed, uint64_t thr, Emit&& emit, std::integer_sequence<int, O...>) {
-    const uint32_t lim = early_limit(thr);
-    (
-        [&] {
-            const Mmh3Open open = PosOps<K, P, O>::template hash_open<PLAIN>(U, C, seed);
-            if constexpr (EARLY) {
-                if (!any_lane(early_may_keep(open, lim))) return;
-            }
-            const uint64_t h = mmh3_close<PLAIN>(open);
-            bool ok = (h - 1) < thr;                          // h != 0 (signature.rs:50) and h <= thr (minhash.rs:319)
-            if (anybad != 0) {
-                // any invalid byte in [O, O+K) kills the k-mer (signature.rs:271-286, force=true)
-                uint64_t lo, hi;                              // bits [O, O+128) of the mask (O < 64: P <= 64)
-                if constexpr (O == 0) { lo = badlo; hi = badhi; }
-                else { lo = (badlo >> O) | (badhi << (64 - O)); hi = (badhi >> O) | (badtop << (64 - O)); }
-                const uint64_t mlo = K >= 64 ? ~0ull : ((1ull << K) - 1);
-                const uint64_t mhi = K >= 128 ? ~0ull : K > 64 ? ((1ull << (K - 64)) - 1) : 0;
-                if ((lo & mlo) | (hi & mhi)) ok = false;
-            }
-            if (ok) emit(O, h);
-        }(),
-        ...);
-}
-
-// process_lane for a staged window.  `dirty` (the tile's flag) MUST be wave-uniform on the device.
-template <int K, int P, bool EARLY = true, bool PLAIN = false, class Emit>
-SMG_HD void process_lane_staged(const uint32_t* U, const uint32_t* C, bool dirty, uint64_t seed, uint64_t thr, Emit&& emit) {
-    using G = LaneGeom<K, P>;
-    uint32_t anybad = 0;
-    uint64_t badlo = 0, badhi = 0, badtop = 0;
-    if (dirty) {
-#pragma unroll
-        for (int i = 0; i < G::NW; ++i) {
-            const uint32_t u = U[i];
-            uint32_t bad = perm_b32(0u, LUT_SELF, (u >> 1) & 0x03030303u) ^ u;
-            if (i == G::NW - 1 && (G::NBYTES % 4) != 0)      // ignore slack bytes past the lane's window
-                bad &= (1u << (8 * (G::NBYTES % 4))) - 1u;
-            anybad |= bad;
+// Stage the IN_CHUNKS chunks of the tile at seq + base into s_in: on the device chunk c by lane c mod BLOCK of the workgroup (the
+// callers put a barrier on either side), on the host all of them.  STAGED: s_in upper-cased, s_comp its complement byte for
+// byte, and *s_dirty set where a staged byte is not ACGT (the caller has zeroed it in front of the barrier).  The unstaged forms of
+// sketch_dna_kernel and hll_dna_kernel keep the unstaged loop inline, for their registers' sake: sketch_kernel.hpp, hll_kernel.hpp.
+template <int IN_CHUNKS, bool STAGED, int BLOCK>
+SMG_HD void stage_tile(const uint8_t* seq, uint64_t base, uint64_t len, uint32_t skip, uint32_t* s_in, uint32_t* s_comp,
+                       unsigned int* s_dirty) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int first = threadIdx.x, step = BLOCK;
+#else
+    const int first = 0, step = 1;
+#endif
+    for (int c = first; c < IN_CHUNKS; c += step) {
+        uint32_t w[4];
+        load_chunk(seq, base + (uint64_t)c * 16, len, skip, w);
+        if constexpr (STAGED) {
+            uint32_t cw[4];
+            if (stage_chunk(w, cw)) *s_dirty = 1;
+            store_chunk(&s_comp[c * 4], cw);
         }
-        if (anybad != 0) lane_bad_bits<K, P>(U, badlo, badhi, badtop);
+        store_chunk(&s_in[c * 4], w);
     }
-    lane_positions<K, P, EARLY, PLAIN>(U, C, anybad, badlo, badhi, badtop, seed, thr, static_cast<Emit&&>(emit),
-                                       std::make_integer_sequence<int, P>{});
 }
+
+// The window of lane `tid`: LANE_RD dwords of the staged tile s from dword tid * P / 4 on, read as whole 16-byte groups where
+// the lane's run starts on one (P = 16, 32), as dwords otherwise.
+template <int LANE_RD, int P>
+SMG_HD void read_window(const uint32_t* s, int tid, uint32_t* out) {
+    static_assert(P % 4 == 0 && LANE_RD % 4 == 0, "lane runs must start dword aligned");
+    const uint32_t* p = &s[tid * (P / 4)];
+#pragma unroll
+    for (int i = 0; i < LANE_RD / 4; ++i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr ((P / 4) % 4 == 0) {
+            const uint4 v = reinterpret_cast<const uint4*>(p)[i];
+            out[4 * i] = v.x; out[4 * i + 1] = v.y; out[4 * i + 2] = v.z; out[4 * i + 3] = v.w;
+            continue;
+        }
+#endif
+        out[4 * i] = p[4 * i]; out[4 * i + 1] = p[4 * i + 1]; out[4 * i + 2] = p[4 * i + 2]; out[4 * i + 3] = p[4 * i + 3];
+    }
+}
+
+#if defined(__HIPCC__)
+// Where a workgroup of BLOCK lanes keeps its kept values: entries of NV u64 values each (a hash; a hash and its position) wait in
+// LDS, CAP of them, and go out with one global atomic per flush, so that the output counter sees a few thousand atomics per launch
+// instead of one per kept value.  The output is unordered; *out_count keeps counting past out_cap, entries past it are dropped.
+// The kernel declares the LDS (s_val[j][CAP], s_cnt, s_base) and zeroes *s_cnt in front of its first barrier.
+template <int CAP, int BLOCK, int NV = 1>
+struct LdsSink {
+    uint64_t* s_val[NV];
+    unsigned int* s_cnt;
+    unsigned long long* s_base;
+    uint64_t* out[NV];
+    unsigned long long* out_count;
+    uint64_t out_cap;
+
+    template <class... V>
+    __device__ __forceinline__ void append(V... v) const {
+        static_assert(sizeof...(V) == NV, "one value per array");
+        const uint64_t e[NV] = {(uint64_t)v...};
+        const unsigned int idx = atomicAdd(s_cnt, 1u);
+        if (idx < (unsigned)CAP) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) s_val[j][idx] = e[j];
+        } else {  // pathological density (e.g. scaled == 1): spill straight to HBM
+            const unsigned long long g = atomicAdd(out_count, 1ull);
+            if (g < out_cap) {
+#pragma unroll
+                for (int j = 0; j < NV; ++j) out[j][g] = e[j];
+            }
+        }
+    }
+    // Write the buffer out if it holds at least `at_least` entries: CAP / 2 between tiles, 1 at the end.  Called by every thread
+    // of the workgroup, behind a barrier.
+    __device__ __forceinline__ void flush(unsigned int at_least) const {
+        const unsigned int cnt = *s_cnt;                      // workgroup-uniform
+        if (cnt < at_least) return;
+        const unsigned int n = cnt < (unsigned)CAP ? cnt : (unsigned)CAP;
+        if (threadIdx.x == 0) *s_base = atomicAdd(out_count, (unsigned long long)n);
+        __syncthreads();
+        const unsigned long long b = *s_base;
+        for (unsigned int i = threadIdx.x; i < n; i += BLOCK) {
+            if (b + i < out_cap) {
+#pragma unroll
+                for (int j = 0; j < NV; ++j) out[j][b + i] = s_val[j][i];
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) *s_cnt = 0;
+    }
+};
+#endif
 
 }  // namespace smg

@@ -24,42 +24,27 @@
 #include <stdint.h>
 #include "device_api.hpp"
 #include "nodegraph_kernel.hpp"
+#include "tile_launch.hpp"
 
 namespace smg {
 
-static unsigned ng_grid(uint64_t n_tiles, bool lds) {
-    uint64_t g = n_tiles < 2048 ? n_tiles : 2048;
-    if (lds && g > 256 && g > n_tiles / 8) g = n_tiles / 8 > 256 ? n_tiles / 8 : 256;
-    return (unsigned)g;
-}
-
 static bool ng_lds(const NgDev& g) { return g.n_words <= NG_LDS_MAX_WORDS; }
-
-// dynamic LDS above 48 KiB has to be allowed once per kernel
-template <class KernelPtr>
-static hipError_t ng_allow_lds(KernelPtr kernel, size_t shm) {
-    if (shm <= 48 * 1024) return hipSuccess;
-    return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(NG_LDS_MAX_WORDS * 4));
-}
 
 hipError_t nodegraph_dna_launch(const uint8_t* d_seq, uint64_t len, uint32_t k, const NgDev& g, hipStream_t stream) {
     if (k == 0 || k > NG_MAX_K) return hipErrorInvalidValue;
     if (len < k || g.n_tables == 0) return hipSuccess;
-    const uint32_t skip = (uint32_t)((uintptr_t)d_seq & 15);
-    d_seq -= skip;
-    len += skip;
-    const uint64_t n_tiles = (len + NG_TILE - 1) / NG_TILE;
+    const TileSpan t = align_to_tiles(d_seq, len, NG_TILE);
     const bool lds = ng_lds(g);
-    const unsigned grid = ng_grid(n_tiles, lds);
+    const unsigned grid = lds_grid(t.n_tiles, lds);
     if (lds) {
         const size_t shm = (size_t)g.n_words * 4;
-        static const hipError_t allowed = ng_allow_lds(ng_dna_kernel<true>, (size_t)NG_LDS_MAX_WORDS * 4);
-        if (shm > 48 * 1024 && allowed != hipSuccess) return allowed;
-        hipLaunchKernelGGL(ng_dna_kernel<true>, dim3(grid), dim3(NG_BLOCK), shm, stream, d_seq, len, k, g.tabs, g.n_tables,
-                           g.words, (uint32_t)g.n_words, g.t0_words, g.occ, n_tiles, skip);
+        const hipError_t allowed = allow_dynamic_lds<&ng_dna_kernel<true>>(shm, (size_t)NG_LDS_MAX_WORDS * 4);
+        if (allowed != hipSuccess) return allowed;
+        hipLaunchKernelGGL(ng_dna_kernel<true>, dim3(grid), dim3(NG_BLOCK), shm, stream, t.seq, t.len, k, g.tabs, g.n_tables,
+                           g.words, (uint32_t)g.n_words, g.t0_words, g.occ, t.n_tiles, t.skip);
     } else {
-        hipLaunchKernelGGL(ng_dna_kernel<false>, dim3(grid), dim3(NG_BLOCK), 0, stream, d_seq, len, k, g.tabs, g.n_tables,
-                           g.words, 0u, g.t0_words, g.occ, n_tiles, skip);
+        hipLaunchKernelGGL(ng_dna_kernel<false>, dim3(grid), dim3(NG_BLOCK), 0, stream, t.seq, t.len, k, g.tabs, g.n_tables,
+                           g.words, 0u, g.t0_words, g.occ, t.n_tiles, t.skip);
     }
     return hipGetLastError();
 }
@@ -69,11 +54,11 @@ hipError_t nodegraph_hashes_launch(const uint64_t* d_hashes, uint64_t n, const N
     const uint64_t nb = (n + NG_BLOCK - 1) / NG_BLOCK;
     const bool lds = ng_lds(g);
     // LDS form: at least 8 blocks' worth of hashes per workgroup, as for the k-mer kernel's tiles
-    const unsigned grid = ng_grid(nb, lds);
+    const unsigned grid = lds_grid(nb, lds);
     if (lds) {
         const size_t shm = (size_t)g.n_words * 4;
-        static const hipError_t allowed = ng_allow_lds(ng_hashes_kernel<true>, (size_t)NG_LDS_MAX_WORDS * 4);
-        if (shm > 48 * 1024 && allowed != hipSuccess) return allowed;
+        const hipError_t allowed = allow_dynamic_lds<&ng_hashes_kernel<true>>(shm, (size_t)NG_LDS_MAX_WORDS * 4);
+        if (allowed != hipSuccess) return allowed;
         hipLaunchKernelGGL(ng_hashes_kernel<true>, dim3(grid), dim3(NG_BLOCK), shm, stream, d_hashes, n, g.tabs, g.n_tables,
                            g.words, (uint32_t)g.n_words, g.t0_words, g.occ);
     } else {

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "device_api.hpp"
+#include "kmer_core.hpp"
 #include "nodegraph_core.hpp"
 
 namespace smg {
@@ -83,23 +84,7 @@ __global__ __launch_bounds__(NG_BLOCK) void ng_dna_kernel(const uint8_t* __restr
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t base = tile * (uint64_t)NG_TILE;
         __syncthreads();
-        for (int c = tid; c < NG_IN_CHUNKS; c += NG_BLOCK) {
-            const uint64_t off = base + (uint64_t)c * 16;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (off + 16 <= len) {
-                v = *reinterpret_cast<const uint4*>(seq + off);
-            } else if (off < len) {
-                uint32_t w[4] = {0, 0, 0, 0};
-                for (uint64_t b = off; b < len; ++b) w[(b - off) >> 2] |= (uint32_t)seq[b] << (8 * ((b - off) & 3));
-                v = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-            if (off == 0 && skip) {
-                uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                for (uint32_t b = 0; b < skip; ++b) w[b >> 2] &= ~(0xffu << (8 * (b & 3)));
-                v = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-            *reinterpret_cast<uint4*>(&s_in[c * 4]) = v;
-        }
+        stage_tile<NG_IN_CHUNKS, false, NG_BLOCK>(seq, base, len, skip, s_in, nullptr, nullptr);
         __syncthreads();
         const uint32_t* lane = &s_in[tid * (NG_RUN / 4)];
         uint64_t fw = 0, rv = 0;

@@ -94,7 +94,11 @@ __global__ __launch_bounds__(SK_BLOCK) void first_invalid_kernel(const uint8_t* 
 // this unit, 65 .. 88 in sketch_long.hip, the per-position form of all of them in sketch_dense.hip.  Longer k-mers take the
 // run-time-k kernel of sketch_words.hip (sketch_kernel.hpp says why the line is drawn at 88).
 constexpr int FAST_MAX_K = SK_FAST_MAX_K;
-constexpr int FAST_HERE_K = 64;
+// parts 0 .. 3 of the appending form's launch table: k = 1 .. 64
+SMG_KMER_PART(SketchLaunch<false>, 0)
+SMG_KMER_PART(SketchLaunch<false>, 1)
+SMG_KMER_PART(SketchLaunch<false>, 2)
+SMG_KMER_PART(SketchLaunch<false>, 3)
 
 static hipError_t sketch_any(const uint8_t* d_seq, uint64_t len, uint32_t k, uint64_t seed, uint64_t thr,
                              uint64_t* d_out, unsigned long long* d_count, uint64_t cap, bool dense,
@@ -103,20 +107,15 @@ static hipError_t sketch_any(const uint8_t* d_seq, uint64_t len, uint32_t k, uin
     static const bool generic_only = [] { const char* e = getenv("SMG_SKETCH_GENERIC"); return e && *e == '1'; }();
     constexpr uint32_t words_from = (uint32_t)FAST_MAX_K + 1u;         // from this k on the run-time-k kernel is taken (it accepts any k >= 16)
     if (k >= words_from && !generic_only) return sketch_dna_words_launch(d_seq, len, k, seed, thr, d_out, d_count, cap, dense, stream);
-    if (!dense && k <= (uint32_t)FAST_MAX_K && !generic_only) {
-        const sketch_launch_fn f = k <= (uint32_t)FAST_HERE_K ? sparse_launcher_from<0>(k, std::make_integer_sequence<int, FAST_HERE_K>())
-                                                             : sparse_launcher_long(k);
-        return f(d_seq, len, seed, thr, d_out, d_count, cap, false, stream);
-    }
+    if (!dense && k <= (uint32_t)FAST_MAX_K && !generic_only)
+        return launcher<SketchLaunch<false>>(k)(d_seq, len, seed, thr, d_out, d_count, cap, stream);
     if (dense && k <= (uint32_t)FAST_MAX_K && !generic_only)          // per-position output (seq_to_hashes): every k <= 88 (sketch_dense.hip)
-        return dense_launcher(k)(d_seq, len, seed, thr, d_out, d_count, cap, true, stream);
+        return launcher<SketchLaunch<true>>(k)(d_seq, len, seed, thr, d_out, d_count, cap, stream);
     // longer k-mers: 16 key bytes at a time from the staged stretch (sketch_words.hip); the byte loop below stays as the form the
     // others are tested against (SMG_SKETCH_GENERIC=1, k <= 256)
     if (!generic_only || k > (uint32_t)GENERIC_MAX_K) return sketch_dna_words_launch(d_seq, len, k, seed, thr, d_out, d_count, cap, dense, stream);
     const uint64_t n_tiles = (len + GENERIC_TILE - 1) / GENERIC_TILE;
-    const uint64_t max_blocks = 256ull * 8;
-    const unsigned grid = (unsigned)(n_tiles < max_blocks ? n_tiles : max_blocks);
-    hipLaunchKernelGGL(sketch_dna_generic_kernel, dim3(grid), dim3(SK_BLOCK), 0, stream, d_seq, len, k, seed, thr,
+    hipLaunchKernelGGL(sketch_dna_generic_kernel, dim3(sk_grid(n_tiles)), dim3(SK_BLOCK), 0, stream, d_seq, len, k, seed, thr,
                        d_out, d_count, cap, n_tiles, dense ? 1 : 0);
     return hipGetLastError();
 }

@@ -38,73 +38,30 @@ __global__ __launch_bounds__(SK_BLOCK) __attribute__((amdgpu_waves_per_eu(3, 8))
                                                                     uint64_t n_tiles, uint32_t skip) {
     static_assert(KA < KB && KB < KC, "ascending ksizes: the window of the last one holds the others'");
     constexpr int P = 16;
-    using G = LaneGeom<KC, P>;
-    constexpr int TILE = SK_BLOCK * P;
-    constexpr int LANE_RD = ((G::NW + 3) / 4) * 4;
-    constexpr int IN_DW = (SK_BLOCK - 1) * (P / 4) + LANE_RD;
-    constexpr int IN_CHUNKS = (IN_DW + 3) / 4;
+    using T = TileGeom<KC, P, SK_BLOCK>;
+    constexpr int TILE = T::TILE, LANE_RD = T::LANE_RD, IN_CHUNKS = T::IN_CHUNKS;
     __shared__ __attribute__((aligned(16))) uint32_t s_in[IN_CHUNKS * 4];
     __shared__ uint64_t s_out[SM_N][SM_OUT_CAP];
     __shared__ unsigned int s_cnt[SM_N];
     __shared__ unsigned long long s_base[SM_N];
+    using Sink = LdsSink<SM_OUT_CAP, SK_BLOCK>;
+    const Sink sink[SM_N] = {Sink{{s_out[0]}, &s_cnt[0], &s_base[0], {a.out[0]}, a.count[0], a.cap[0]},
+                             Sink{{s_out[1]}, &s_cnt[1], &s_base[1], {a.out[1]}, a.count[1], a.cap[1]},
+                             Sink{{s_out[2]}, &s_cnt[2], &s_base[2], {a.out[2]}, a.count[2], a.cap[2]}};
     const int tid = threadIdx.x;
     if (tid < SM_N) s_cnt[tid] = 0;
-
-    auto flush = [&](bool always) {                    // (called by every thread, after a barrier)
-#pragma unroll
-        for (int j = 0; j < SM_N; ++j) {
-            const unsigned int cnt = s_cnt[j];
-            const bool go = always ? cnt != 0 : cnt >= (unsigned)SM_OUT_CAP / 2;       // workgroup-uniform
-            if (!go) continue;
-            const unsigned int n = cnt < (unsigned)SM_OUT_CAP ? cnt : (unsigned)SM_OUT_CAP;
-            if (tid == 0) s_base[j] = atomicAdd(a.count[j], (unsigned long long)n);
-            __syncthreads();
-            const unsigned long long b = s_base[j];
-            for (unsigned int i = tid; i < n; i += SK_BLOCK)
-                if (b + i < a.cap[j]) a.out[j][b + i] = s_out[j][i];
-            __syncthreads();
-            if (tid == 0) s_cnt[j] = 0;
-        }
-    };
 
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t base = tile * (uint64_t)TILE;
         __syncthreads();
-        for (int c = tid; c < IN_CHUNKS; c += SK_BLOCK) {
-            const uint64_t off = base + (uint64_t)c * 16;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (off + 16 <= len) {
-                v = *reinterpret_cast<const uint4*>(seq + off);
-            } else if (off < len) {
-                uint32_t w[4] = {0, 0, 0, 0};
-                for (uint64_t b = off; b < len; ++b) w[(b - off) >> 2] |= (uint32_t)seq[b] << (8 * ((b - off) & 3));
-                v = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-            if (off == 0 && skip) {                      // blank the alignment prefix
-                uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                for (uint32_t b = 0; b < skip; ++b) w[b >> 2] &= ~(0xffu << (8 * (b & 3)));
-                v = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-            *reinterpret_cast<uint4*>(&s_in[c * 4]) = v;
-        }
+        stage_tile<IN_CHUNKS, false, SK_BLOCK>(seq, base, len, skip, s_in, nullptr, nullptr);
         __syncthreads();
         uint32_t raw[LANE_RD];
-        const uint4* wp = reinterpret_cast<const uint4*>(&s_in[tid * (P / 4)]);
-#pragma unroll
-        for (int i = 0; i < LANE_RD / 4; ++i) {
-            const uint4 v = wp[i];
-            raw[4 * i] = v.x; raw[4 * i + 1] = v.y; raw[4 * i + 2] = v.z; raw[4 * i + 3] = v.w;
-        }
+        read_window<LANE_RD, P>(s_in, tid, raw);
         const uint64_t lane0 = base + (uint64_t)tid * P;
         auto keep = [&](int j, int o, uint64_t h) {
             if (lane0 + (uint64_t)o < (uint64_t)a.start[j]) return;        // hashed with the previous piece (see MultiArgs)
-            const unsigned int idx = atomicAdd(&s_cnt[j], 1u);
-            if (idx < (unsigned)SM_OUT_CAP) {
-                s_out[j][idx] = h;
-            } else {                                     // pathological density: straight to HBM
-                const unsigned long long g = atomicAdd(a.count[j], 1ull);
-                if (g < a.cap[j]) a.out[j][g] = h;
-            }
+            sink[j].append(h);
         };
         // one ksize after the other on the same registers (a fence keeps the scheduler from interleaving three hash pipelines)
         // (the window passes through an empty asm between the phases: without it the compiler shares the upper-cased and
@@ -120,30 +77,26 @@ __global__ __launch_bounds__(SK_BLOCK) __attribute__((amdgpu_waves_per_eu(3, 8))
         fence();
         process_lane<KC, P, true, SM_PLAIN_MUL_LAST>(raw, seed, a.thr[2], [&](int o, uint64_t h) { keep(2, o, h); });
         __syncthreads();
-        flush(false);
+#pragma unroll
+        for (int j = 0; j < SM_N; ++j) sink[j].flush(SM_OUT_CAP / 2);
     }
     __syncthreads();
-    flush(true);
+#pragma unroll
+    for (int j = 0; j < SM_N; ++j) sink[j].flush(1);
 }
 
 template <int KA, int KB, int KC>
 hipError_t launch_multi(const uint8_t* d_new, uint64_t n_new, uint64_t seed, const SketchMultiOut* o, hipStream_t stream) {
-    constexpr uint64_t TILE = (uint64_t)SK_BLOCK * 16;
-    const uint8_t* seq = d_new - (KC - 1);
-    const uint32_t skip = (uint32_t)((uintptr_t)seq & 15);
-    seq -= skip;
-    const uint64_t len = (uint64_t)skip + (uint64_t)(KC - 1) + n_new;
-    const uint64_t n_tiles = (len + TILE - 1) / TILE;
-    if (n_tiles == 0) return hipSuccess;
+    const TileSpan t = align_to_tiles(d_new - (KC - 1), (uint64_t)(KC - 1) + n_new, (uint64_t)SK_BLOCK * 16);
+    if (t.n_tiles == 0) return hipSuccess;
     MultiArgs a;
     const int ks[SM_N] = {KA, KB, KC};
     for (int j = 0; j < SM_N; ++j) {
         a.thr[j] = o[j].thr; a.out[j] = o[j].out; a.count[j] = o[j].count; a.cap[j] = o[j].cap;
-        a.start[j] = skip + (uint32_t)(KC - ks[j]);
+        a.start[j] = t.skip + (uint32_t)(KC - ks[j]);
     }
-    const uint64_t max_blocks = 256ull * 8;
-    const unsigned grid = (unsigned)(n_tiles < max_blocks ? n_tiles : max_blocks);
-    hipLaunchKernelGGL((sketch_dna_multi_kernel<KA, KB, KC>), dim3(grid), dim3(SK_BLOCK), 0, stream, seq, len, seed, a, n_tiles, skip);
+    hipLaunchKernelGGL((sketch_dna_multi_kernel<KA, KB, KC>), dim3(sk_grid(t.n_tiles)), dim3(SK_BLOCK), 0, stream, t.seq, t.len, seed,
+                       a, t.n_tiles, t.skip);
     return hipGetLastError();
 }
 

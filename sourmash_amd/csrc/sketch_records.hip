@@ -108,7 +108,7 @@ hipError_t records_pairs_launch(const uint8_t* d_seq, uint64_t len, uint32_t k, 
                                 uint64_t* d_pos, unsigned long long* d_count, uint64_t cap, hipStream_t stream) {
     if (k == 0 || k > (uint32_t)SK_FAST_MAX_K) return hipErrorInvalidValue;
     if (len < k) return hipSuccess;
-    return records_launcher(k)(d_seq, len, seed, thr, d_hash, d_pos, d_count, cap, stream);
+    return launcher<RecordsLaunch>(k)(d_seq, len, seed, thr, d_hash, d_pos, d_count, cap, stream);
 }
 
 hipError_t records_check_starts_launch(const uint64_t* d_starts, uint64_t n_records, uint64_t len, unsigned long long* d_bad,

@@ -12,7 +12,6 @@
 // kernels by what the run-time addressing costs, not by an order of magnitude (profiles/r05_long_k.json).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <mutex>
 #include "kmer_words.hpp"
 #include "sketch_kernel.hpp"
 #include "device_api.hpp"
@@ -57,19 +56,7 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_words_kernel(
     const WwBad bad{s_bits, s_before};
     const WwLayout lay = ww_layout(g.n_chunks);
     if (tid == 0) s_cnt = 0;
-    auto flush = [&](unsigned int at_least) {                    // (called by every thread, between barriers)
-        __syncthreads();
-        const unsigned int cnt = s_cnt;
-        if (cnt < at_least || cnt == 0) return;
-        const unsigned int n = cnt < (unsigned)SK_OUT_CAP ? cnt : (unsigned)SK_OUT_CAP;
-        if (tid == 0) s_base = atomicAdd(out_count, (unsigned long long)n);
-        __syncthreads();
-        const unsigned long long b = s_base;
-        for (unsigned int i = (unsigned)tid; i < n; i += SK_BLOCK)
-            if (b + i < out_cap) out[b + i] = s_out[i];
-        __syncthreads();
-        if (tid == 0) s_cnt = 0;
-    };
+    const LdsSink<SK_OUT_CAP, SK_BLOCK> sink{{s_out}, &s_cnt, &s_base, {out}, out_count, out_cap};
 
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t base = tile * (uint64_t)WORDS_TILE;
@@ -78,15 +65,8 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_words_kernel(
         //      reverse complement, its dwords in reverse order (the slack behind the copies is read and masked away: left as it is) ----
         for (uint32_t c = (uint32_t)tid; c < g.n_chunks; c += SK_BLOCK) {
             const uint64_t off = base + (uint64_t)c * 16;
-            uint32_t w[4] = {0, 0, 0, 0};
-            if (off + 16 <= len) {
-                const uint4 v = *reinterpret_cast<const uint4*>(seq + off);
-                w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-            } else if (off < len) {
-                for (uint64_t b = off; b < len; ++b) w[(b - off) >> 2] |= (uint32_t)seq[b] << (8 * ((b - off) & 3));
-            }
-            if (off == 0 && skip)                                // blank the alignment prefix
-                for (uint32_t b = 0; b < skip; ++b) w[b >> 2] &= ~(0xffu << (8 * (b & 3)));
+            uint32_t w[4];
+            load_chunk(seq, off, len, skip, w);
             uint32_t nib = 0;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -134,19 +114,17 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_words_kernel(
                 if (keep && pos < out_cap) out[pos] = h;
                 continue;
             }
-            if (keep) {
-                const unsigned int idx = atomicAdd(&s_cnt, 1u);
-                if (idx < (unsigned)SK_OUT_CAP) {
-                    s_out[idx] = h;
-                } else {                                         // pathological density (scaled == 1): straight to HBM
-                    const unsigned long long at = atomicAdd(out_count, 1ull);
-                    if (at < out_cap) out[at] = h;
-                }
-            }
+            if (keep) sink.append(h);
         }
-        if (!dense) flush((unsigned)SK_OUT_CAP / 2);             // (the next stretch's first barrier orders the reset of s_cnt)
+        if (!dense) {
+            __syncthreads();
+            sink.flush(SK_OUT_CAP / 2);                          // (the next stretch's first barrier orders the reset of s_cnt)
+        }
     }
-    if (!dense) flush(1u);
+    if (!dense) {
+        __syncthreads();
+        sink.flush(1);
+    }
 }
 
 }  // namespace
@@ -155,26 +133,15 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_words_kernel(
 hipError_t sketch_dna_words_launch(const uint8_t* d_seq, uint64_t len, uint32_t k, uint64_t seed, uint64_t thr, uint64_t* d_out,
                                    unsigned long long* d_count, uint64_t cap, bool dense, hipStream_t stream) {
     if (k < 16u || k > WORDS_MAX_K) return hipErrorInvalidValue;
-    const uint32_t skip = (uint32_t)((uintptr_t)d_seq & 15);
-    d_seq -= skip;
-    len += skip;
-    const uint64_t n_tiles = (len + WORDS_TILE - 1) / WORDS_TILE;
-    if (n_tiles == 0) return hipSuccess;
+    const TileSpan t = align_to_tiles(d_seq, len, WORDS_TILE);
+    if (t.n_tiles == 0) return hipSuccess;
     if (k > sketch_dna_max_k()) return hipErrorInvalidValue;      // (the host entry points say so in words before they get here)
     const WordsGeom g = words_geometry(k);
-    if (g.lds > 48 * 1024) {                                     // more dynamic LDS than a kernel gets unasked: allow what the longest k of THIS device needs, once
-        static std::once_flag once;
-        static hipError_t allowed = hipSuccess;
-        std::call_once(once, [] {
-            allowed = hipFuncSetAttribute((const void*)sketch_dna_words_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)words_geometry(sketch_dna_max_k()).lds);
-        });
-        if (allowed != hipSuccess) return allowed;
-    }
-    const uint64_t max_blocks = 256ull * 8;
-    const unsigned grid = (unsigned)(n_tiles < max_blocks ? n_tiles : max_blocks);
-    hipLaunchKernelGGL(sketch_dna_words_kernel, dim3(grid), dim3(SK_BLOCK), g.lds, stream, d_seq, len, k, seed, thr, d_out, d_count, cap,
-                       n_tiles, skip, dense ? 1 : 0, g);
+    // (the most it is ever launched with: what the longest k of THIS device needs)
+    const hipError_t allowed = allow_dynamic_lds<&sketch_dna_words_kernel>(g.lds, words_geometry(sketch_dna_max_k()).lds);
+    if (allowed != hipSuccess) return allowed;
+    hipLaunchKernelGGL(sketch_dna_words_kernel, dim3(sk_grid(t.n_tiles)), dim3(SK_BLOCK), g.lds, stream, t.seq, t.len, k, seed, thr, d_out,
+                       d_count, cap, t.n_tiles, t.skip, dense ? 1 : 0, g);
     return hipGetLastError();
 }
 

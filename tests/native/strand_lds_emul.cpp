@@ -1,9 +1,9 @@
 // Host emulation of the appending sketch kernel with the per-byte work done at staging (test-only artefact).
 // Compiles sourmash_amd/csrc/kmer_core.hpp for the CPU and walks a buffer tile by tile exactly as sketch_dna_kernel<K, 16, false>
-// does: the alignment prefix (`skip` bytes in front of the caller's buffer, blanked), 16-byte chunks staged with load_chunk /
-// stage_chunk into an upper-cased and a complemented copy of the tile, zero fill past the end, the tile's dirty flag, and lanes
-// that read their windows from the two copies into process_lane_staged.  tests/test_strand_lds_cpu.py compares the result with
-// the oracle.
+// does: the alignment prefix (`skip` bytes in front of the caller's buffer, blanked), 16-byte chunks staged by the kernel's own
+// stage_tile into an upper-cased and a complemented copy of the tile, zero fill past the end, the tile's dirty flag, and lanes
+// that read their windows from the two copies (read_window) into process_lane_staged.  tests/test_strand_lds_cpu.py compares
+// the result with the oracle.
 #include <cstring>
 #include <utility>
 #include <vector>
@@ -27,18 +27,12 @@ static uint64_t run(const uint8_t* seq, uint64_t len, uint32_t skip, uint64_t se
     for (uint64_t tile = 0; tile < n_tiles; ++tile) {
         const uint64_t base = tile * (uint64_t)T::TILE;
         unsigned s_dirty = 0;
-        for (int c = 0; c < T::IN_CHUNKS; ++c) {
-            uint32_t w[4], cw[4];
-            smg::load_chunk(base_ptr, base + (uint64_t)c * 16, total, skip, w);
-            if (smg::stage_chunk(w, cw)) s_dirty = 1;
-            std::memcpy(&s_comp[c * 4], cw, 16);
-            std::memcpy(&s_in[c * 4], w, 16);
-        }
+        smg::stage_tile<T::IN_CHUNKS, true, BLOCK>(base_ptr, base, total, skip, s_in.data(), s_comp.data(), &s_dirty);
         *dirty_tiles += s_dirty;
         for (int tid = 0; tid < BLOCK; ++tid) {
             uint32_t U[T::LANE_RD], C[T::LANE_RD];
-            std::memcpy(U, &s_in[tid * (P / 4)], sizeof(U));
-            std::memcpy(C, &s_comp[tid * (P / 4)], sizeof(C));
+            smg::read_window<T::LANE_RD, P>(s_in.data(), tid, U);
+            smg::read_window<T::LANE_RD, P>(s_comp.data(), tid, C);
             smg::process_lane_staged<K, P>(U, C, s_dirty != 0, seed, thr, [&](int, uint64_t h) { if (n < cap) out[n] = h; ++n; });
         }
     }

@@ -11,8 +11,8 @@ Build the library twice (parent and change) with the remarks switched on and the
 then: python tools/kernel_resources.py before.log after.log [-o profiles/NAME.txt]
 
 Every kernel of every translation unit is compared (name demangled with c++filt when it is there).  The table lists the kernels
-whose VGPR count, occupancy, scratch or spill counts differ, then a summary; the exit status is 1 when any kernel lost a wave per
-SIMD, gained scratch or gained a spill."""
+whose VGPR count, occupancy, scratch, spill counts or LDS size differ, then a summary; the exit status is 1 when any kernel lost a
+wave per SIMD, gained scratch, gained a spill or changed its LDS size."""
 import re
 import shutil
 import subprocess
@@ -28,7 +28,7 @@ def parse(path):
         m = re.search(r"remark:\s+(.*?)\s*\[-Rpass-analysis", line)
         if not m:
             continue
-        t = m.group(1)
+        t = re.sub(r"^\S+:\d+:\d+:\s+", "", m.group(1))     # "remark: file:line:col: text" as well as "file:line:col: remark: text"
         if t.startswith("Function Name:"):
             cur = out.setdefault(t.split(":", 1)[1].strip(), {})
         elif cur is not None and ":" in t:
@@ -72,19 +72,19 @@ def main():
         if b is None or a is None:
             missing.append(nice[n] + (" (only after)" if b is None else " (only before)"))
             continue
-        if a["occ"] < b["occ"] or a["scratch"] > b["scratch"] or a["vspill"] > b["vspill"] or a["sspill"] > b["sspill"]:
+        if a["occ"] < b["occ"] or a["scratch"] > b["scratch"] or a["vspill"] > b["vspill"] or a["sspill"] > b["sspill"] or a["lds"] != b["lds"]:
             worse.append(nice[n])
-        if any(a[k] != b[k] for k in ("vgpr", "agpr", "occ", "scratch", "vspill", "sspill")):
+        if any(a[k] != b[k] for k in ("vgpr", "agpr", "occ", "scratch", "vspill", "sspill", "lds")):
             rows.append((nice[n], b, a))
-    lines = [f"kernels compared: {len(names) - len(missing)}; VGPR / occupancy / scratch / spill differ in {len(rows)}; "
-             f"lost a wave per SIMD, gained scratch or gained a spill: {len(worse)}",
+    lines = [f"kernels compared: {len(names) - len(missing)}; VGPR / occupancy / scratch / spill / LDS differ in {len(rows)}; "
+             f"lost a wave per SIMD, gained scratch, gained a spill or changed LDS: {len(worse)}",
              f"kernels with scratch: before {sum(1 for v in before.values() if v['scratch'])}, after {sum(1 for v in after.values() if v['scratch'])}; "
              f"with spills: before {sum(1 for v in before.values() if v['vspill'] or v['sspill'])}, "
              f"after {sum(1 for v in after.values() if v['vspill'] or v['sspill'])}", ""]
-    lines.append(f"{'kernel':<64} {'VGPR':>9} {'occ':>5} {'scratch':>9} {'v-spill':>8} {'s-spill':>8}")
+    lines.append(f"{'kernel':<64} {'VGPR':>9} {'occ':>5} {'scratch':>9} {'v-spill':>8} {'s-spill':>8} {'LDS':>13}")
     for name, b, a in rows:
         lines.append(f"{name:<64} {b['vgpr']:>4}>{a['vgpr']:<4} {b['occ']}>{a['occ']:<3} {b['scratch']:>4}>{a['scratch']:<4} "
-                     f"{b['vspill']:>3}>{a['vspill']:<4} {b['sspill']:>3}>{a['sspill']:<4}")
+                     f"{b['vspill']:>3}>{a['vspill']:<4} {b['sspill']:>3}>{a['sspill']:<4} {b['lds']:>6}>{a['lds']:<6}")
     lines += [""] + [f"WORSE: {w}" for w in worse] + [f"UNMATCHED: {m}" for m in missing]
     text = "\n".join(lines).rstrip() + "\n"
     if dest:
