@@ -360,7 +360,8 @@ uint64_t smgpu_sort_unique_raw(uint64_t *d_keys, uint64_t n, uint64_t *d_out, ui
  * DNA -- go to d_aa (capacity aa_capacity bytes: the residue count rounded up to 8 -- the window kernel reads whole aligned
  * 8-byte words; translated DNA needs 2 * len + 6 residues), every window of k_aa residues is hashed and
  * the hashes 1 <= h <= max_hash are appended unordered to d_out, their count added to *d_count (device u64, caller zeroes).
- * -> residues written to d_aa.  Fully asynchronous.  hash_function: 2 protein, 3 dayhoff, 4 hp. */
+ * -> residues written to d_aa (DNA of fewer than three bases: the six separators, and no window is hashed).  Fully asynchronous.
+ * hash_function: 2 protein, 3 dayhoff, 4 hp. */
 uint64_t smgpu_sketch_residues_kernels_raw(const uint8_t *d_seq, uint64_t len, uint32_t k_aa, uint32_t hash_function, uint64_t seed,
                                            uint64_t max_hash, bool translate, uint8_t *d_aa, uint64_t aa_capacity, uint64_t *d_out,
                                            uint64_t out_capacity, uint64_t *d_count, void *stream);

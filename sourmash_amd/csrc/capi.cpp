@@ -934,7 +934,8 @@ uint64_t smgpu_sketch_residues_kernels_raw(const uint8_t* d_seq, uint64_t len, u
         hipStream_t st = (hipStream_t)stream;
         if (translate) hip_check(translate_launch(d_seq, len, hash_function, d_aa, st), "translate");
         else hip_check(residues_launch(d_seq, len, hash_function, d_aa, st), "residues");
-        hip_check(residue_windows_launch(d_aa, n_aa, k_aa, seed, max_hash ? max_hash : ~0ull, d_out, (unsigned long long*)d_count, cap,
+        // (fewer than three bases: d_aa holds the six separators and no window; k_aa is still validated)
+        hip_check(residue_windows_launch(d_aa, translate && len < 3 ? 0 : n_aa, k_aa, seed, max_hash ? max_hash : ~0ull, d_out, (unsigned long long*)d_count, cap,
                                          false, st), "residue windows");
         return n_aa;
     });

@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void translate_kernel(const uint8_t* __restric
     __syncthreads();
     uint64_t start[7];
     start[0] = 0;
-    for (int s = 0; s < 6; ++s) start[s + 1] = start[s] + (len - (uint64_t)(s >> 1)) / 3 + 1;
+    for (int s = 0; s < 6; ++s) start[s + 1] = start[s] + frame_residues(len, s >> 1) + 1;
     for (uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (uint64_t)gridDim.x * blockDim.x) {
         int s = 0;
         while (o >= start[s + 1]) ++s;
@@ -218,11 +218,7 @@ unsigned grid_for(uint64_t n) {
 
 }  // namespace
 
-uint64_t translated_bytes(uint64_t len) {
-    uint64_t t = 0;
-    for (int s = 0; s < 6; ++s) t += (len - (uint64_t)(s >> 1)) / 3 + 1;
-    return t;
-}
+uint64_t translated_bytes(uint64_t len) { return translate_layout(len).start[6]; }
 
 hipError_t residues_launch(const uint8_t* d_seq, uint64_t len, uint32_t hash_function, uint8_t* d_aa, hipStream_t stream) {
     if (len == 0) return hipSuccess;
@@ -231,8 +227,7 @@ hipError_t residues_launch(const uint8_t* d_seq, uint64_t len, uint32_t hash_fun
 }
 
 hipError_t translate_launch(const uint8_t* d_seq, uint64_t len, uint32_t hash_function, uint8_t* d_aa, hipStream_t stream) {
-    if (len < 3) return hipErrorInvalidValue;
-    const uint64_t total = translated_bytes(len);
+    const uint64_t total = translated_bytes(len);                       // (len < 3: six separators, no base is read)
     if ((((uintptr_t)d_seq | (uintptr_t)d_aa) & 3) == 0)
         hipLaunchKernelGGL(translate_words_kernel, dim3(grid_for((total + 3) / 4)), dim3(256), 0, stream, d_seq, len, hash_function, d_aa, total);
     else

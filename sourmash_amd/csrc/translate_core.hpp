@@ -25,11 +25,14 @@ struct TranslateLayout {
     uint64_t len;
     uint64_t start[7];            // start[s]: first output byte of segment s; start[6] = total
 };
+// residues of a frame: a frame that starts at or past the end of the input holds none (len - frame must not wrap)
+SMG_HD uint64_t frame_residues(uint64_t len, int frame) { return len > (uint64_t)frame ? (len - (uint64_t)frame) / 3 : 0; }
+
 SMG_HD TranslateLayout translate_layout(uint64_t len) {
     TranslateLayout L;
     L.len = len;
     L.start[0] = 0;
-    for (int s = 0; s < 6; ++s) L.start[s + 1] = L.start[s] + (len - (uint64_t)(s >> 1)) / 3 + 1;
+    for (int s = 0; s < 6; ++s) L.start[s + 1] = L.start[s] + frame_residues(len, s >> 1) + 1;
     return L;
 }
 

@@ -103,3 +103,7 @@ extern "C" uint64_t emul_translate(const uint8_t* seq, uint64_t len, uint32_t hf
     for (uint64_t o = 0; o < total; ++o) out_naive[o] = smg::translate_one(s8, L, T, o);
     return total;
 }
+
+// bytes of the six-segment output (what protein.hip's translated_bytes returns), and the residues of one frame
+extern "C" uint64_t emul_translated_bytes(uint64_t len) { return smg::translate_layout(len).start[6]; }
+extern "C" uint64_t emul_frame_residues(uint64_t len, int frame) { return smg::frame_residues(len, frame); }

@@ -114,3 +114,26 @@ def test_translate_words_equal_the_per_byte_definition_and_the_oracle(emul):
     hashes = emul.fast(bytes(fast[:total]), 10)[1]
     want = oracle.seq_to_hashes_protein(bytes(s), 10, "protein", is_protein=False)
     assert np.array_equal(hashes, want)
+
+
+def test_inputs_shorter_than_a_codon_translate_to_six_separators(emul):
+    """A frame that starts at or past the end of the input holds zero residues (len - frame must not wrap in 64 bits): the layout,
+    the byte count the launcher sizes its buffers by, and both lane forms, for 0, 1 and 2 bases and on to 12."""
+    lib = C.CDLL(SO)
+    lib.emul_translate.restype = lib.emul_translated_bytes.restype = lib.emul_frame_residues.restype = C.c_uint64
+    lib.emul_translate.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.emul_translated_bytes.argtypes = [C.c_uint64]
+    lib.emul_frame_residues.argtypes = [C.c_uint64, C.c_int]
+    for n in range(0, 13):
+        per_frame = [len(range(f, n - 2, 3)) for f in (0, 1, 2)]      # codons that start at f, f + 3, ... and end inside the input
+        assert [lib.emul_frame_residues(n, f) for f in (0, 1, 2)] == per_frame, n
+        total = 2 * sum(per_frame) + 6
+        assert lib.emul_translated_bytes(n) == total, n
+        s = np.frombuffer(b"ACGTNacgtnAC"[:n], dtype=np.uint8).copy()
+        fast, naive = np.full(total + 8, 0x11, dtype=np.uint8), np.full(total + 8, 0x22, dtype=np.uint8)
+        got = lib.emul_translate(s.ctypes.data if n else None, n, 2, fast.ctypes.data, naive.ctypes.data)
+        assert got == total and np.array_equal(fast[:total], naive[:total]), n
+        assert np.all(fast[total:] == 0x11) and np.all(naive[total:] == 0x22), n
+        assert int((fast[:total] == 0xff).sum()) == 6, n
+        if n < 3:
+            assert total == 6 and np.all(fast[:6] == 0xff), n
