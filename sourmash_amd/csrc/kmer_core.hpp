@@ -323,15 +323,30 @@ SMG_HD void process_lane_staged(const uint32_t* U, const uint32_t* C, bool dirty
 // whether any staged byte is invalid.  A lane of a clean tile reads U and C as they are and does no validity work at all; a lane
 // of a dirty tile rebuilds its bad-byte mask from U (process_window).
 
-// Geometry of one tile of BLOCK lanes x P positions: what is staged, and what a lane reads back.
-template <int K, int P, int BLOCK>
+// Geometry of one tile: R consecutive windows ("rounds") of BLOCK lanes x P positions, staged together with one halo behind the
+// last of them.  What is staged, and what a lane reads back: in round r the lane tid reads the window of lane index
+// tid + r * BLOCK.  R = 1 is the tile every kernel but the appending staged sketch kernel walks.
+template <int K, int P, int BLOCK, int R = 1>
 struct TileGeom {
     using G = LaneGeom<K, P>;
-    static constexpr int TILE = BLOCK * P;                          // start positions per tile
+    static constexpr int WINDOW = BLOCK * P;                        // start positions per round
+    static constexpr int TILE = R * WINDOW;                         // start positions per tile
     static constexpr int LANE_RD = ((G::NW + 3) / 4) * 4;           // dwords each lane reads (whole 16-byte reads)
-    static constexpr int IN_DW = (BLOCK - 1) * (P / 4) + LANE_RD;   // dwords the tile needs in LDS
-    static constexpr int IN_CHUNKS = (IN_DW + 3) / 4;               // 16-byte chunks to stage
+    // 16-byte chunks to stage for a tile of `rounds` rounds: the dwords up to the end of the last lane's read
+    static constexpr int chunks(int rounds) { return ((rounds * BLOCK - 1) * (P / 4) + LANE_RD + 3) / 4; }
+    static constexpr int IN_DW = (R * BLOCK - 1) * (P / 4) + LANE_RD;   // dwords the tile needs in LDS
+    static constexpr int IN_CHUNKS = chunks(R);                     // 16-byte chunks to stage
 };
+
+// How many rounds a tile of the appending sketch kernel gets (sketch_kernel.hpp): r_max, unless the hashes a tile of r_max rounds
+// is expected to keep -- its positions times thr / 2^64 -- are more than a quarter of the cap entries its sink holds between two
+// flush checks; then 1, as for small `scaled` values and for num sketches (thr = 2^64 - 1).  window = positions per round.
+SMG_HD uint32_t sk_tile_rounds(uint64_t thr, uint32_t r_max, uint32_t window, uint32_t cap) {
+    if (r_max <= 1) return 1;
+    const uint64_t positions = (uint64_t)r_max * window;            // < 2^32
+    const uint64_t expected = (positions * (thr >> 32)) >> 32;      // floor(positions * floor(thr / 2^32) / 2^32)
+    return expected + 1 > cap / 4 ? 1u : r_max;
+}
 
 // The 16 bytes at seq + off as 4 little-endian dwords: zero past `len`, and the first `skip` (< 16) bytes of the buffer blanked.
 // seq + off is 16-byte aligned.
@@ -379,15 +394,16 @@ SMG_HD void store_chunk(uint32_t* dst, const uint32_t* w) {      // dst is 16-by
 // callers put a barrier on either side), on the host all of them.  STAGED: s_in upper-cased, s_comp its complement byte for
 // byte, and *s_dirty set where a staged byte is not ACGT (the caller has zeroed it in front of the barrier).  The unstaged forms of
 // sketch_dna_kernel and hll_dna_kernel keep the unstaged loop inline, for their registers' sake: sketch_kernel.hpp, hll_kernel.hpp.
+// n_chunks (<= IN_CHUNKS, which sizes the arrays): the chunks of this launch's tile where its rounds are a run-time value.
 template <int IN_CHUNKS, bool STAGED, int BLOCK>
 SMG_HD void stage_tile(const uint8_t* seq, uint64_t base, uint64_t len, uint32_t skip, uint32_t* s_in, uint32_t* s_comp,
-                       unsigned int* s_dirty) {
+                       unsigned int* s_dirty, int n_chunks = IN_CHUNKS) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const int first = threadIdx.x, step = BLOCK;
 #else
     const int first = 0, step = 1;
 #endif
-    for (int c = first; c < IN_CHUNKS; c += step) {
+    for (int c = first; c < n_chunks; c += step) {
         uint32_t w[4];
         load_chunk(seq, base + (uint64_t)c * 16, len, skip, w);
         if constexpr (STAGED) {

@@ -11,7 +11,10 @@
 // smg::process_lane (kmer_core.hpp).  The appending form does the per-byte work
 // (upper-casing, complement, validity) where the tile is staged: the tile goes
 // to LDS twice, upper-cased and complemented, with one dirty flag per tile, and
-// the lanes read both (process_lane_staged).  Kept hashes (about 1 in `scaled`) are
+// the lanes read both (process_lane_staged); from k = 19 on it stages three such
+// windows as one tile and takes the lanes through them in a rolled loop, so that
+// the tile's barriers and the wait for its global loads come once per 12,288
+// positions (sketch_kernel.hpp, SK_R_MAX).  Kept hashes (about 1 in `scaled`) are
 // appended to a per-workgroup LDS buffer and flushed to HBM with one global
 // atomic per flush, so the single output counter sees a few thousand atomics
 // per launch instead of one per kept hash.

@@ -29,6 +29,30 @@ constexpr bool sk_plain_mul(int k, bool dense) {
 // second copy's 4 KiB of LDS take the seventh workgroup of a CU, and k = 18, 20 and 30, which need a few registers more and
 // cross a step of the register file (profiles/strand_lds_kernel_resources.txt).
 constexpr bool sk_staged(int k) { return k > 11 && k != 18 && k != 20 && k != 30; }
+// The staged appending form walks tiles of several window rounds: R_MAX consecutive windows of SK_BLOCK x 16 positions are
+// staged together, behind one pair of barriers, one wait for the global loads and one halo, and a rolled loop takes the lanes
+// through them (`rounds`, a launch argument: 1 where the sink could overfill between two flush checks, kmer_core.hpp
+// sk_tile_rounds).  SK_R_MAX sizes the LDS copies: 2 with the 2,048-entry sink and 3 with a 1,024-entry one are about 33 KB at
+// k = 31, so that the four workgroups per CU the registers allow still fit in 160 KB.  An instantiation that runs more than four
+// workgroups per CU by its registers would lose one to the longer tile's LDS and stays at one round
+// (profiles/tile_rounds_kernel_resources.txt).
+#ifndef SMG_SK_R_MAX
+#define SMG_SK_R_MAX 3
+#endif
+constexpr int SK_R_MAX = SMG_SK_R_MAX;
+static_assert(SK_R_MAX >= 1 && SK_R_MAX <= 3, "four rounds do not fit four workgroups per CU");
+constexpr bool sk_one_round(int k) { return k <= 17; }      // k = 12, 13: six workgroups per CU, 14 .. 17: five
+constexpr int sk_rounds_max(int k, bool dense) { return !dense && sk_staged(k) && !sk_one_round(k) ? SK_R_MAX : 1; }
+constexpr int sk_out_cap(int r_max) { return r_max >= 3 ? SK_OUT_CAP / 2 : SK_OUT_CAP; }
+// Workgroups per CU a launch may ask for (tile_launch.hpp, sk_grid).  The long tiles are handed out by static stride like the
+// short ones, and with three times fewer of them the end of the launch weighs more: at k = 31 a step of the benchmark took
+// 29.2 ms with 2,048 workgroups, 28.2 with 4,096 and 27.7 with 8,192 (profiles/tile_rounds_bench.txt).  SMG_SK_GRID_PER_CU: a
+// variant build that measures another cap, for every instantiation.
+#ifdef SMG_SK_GRID_PER_CU
+constexpr unsigned sk_grid_per_cu(int) { return SMG_SK_GRID_PER_CU; }
+#else
+constexpr unsigned sk_grid_per_cu(int r_max) { return r_max > 1 ? 32 : 8; }
+#endif
 
 // DENSE == false: append kept hashes (unordered) to out, count in *out_count.
 // DENSE == true : out[i] = hash of the k-mer starting at i (out pre-zeroed by the
@@ -37,32 +61,37 @@ template <int K, int P, bool DENSE>
 __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
     const uint8_t* __restrict__ seq, uint64_t len, uint64_t seed, uint64_t thr,
     uint64_t* __restrict__ out, unsigned long long* __restrict__ out_count, uint64_t out_cap,
-    uint64_t n_tiles, uint32_t skip) {
+    uint64_t n_tiles, uint32_t skip, uint32_t rounds) {
     // seq is 16-byte aligned; its first `skip` (< 16) bytes precede the caller's buffer and are
     // treated as invalid.  len includes them.  DENSE positions are reported relative to seq + skip.
-    using T = TileGeom<K, P, SK_BLOCK>;
-    constexpr int TILE = T::TILE, LANE_RD = T::LANE_RD, IN_CHUNKS = T::IN_CHUNKS;
+    // A tile is `rounds` (1 .. R_MAX) windows of SK_BLOCK x P positions; n_tiles counts tiles of that length.
+    constexpr int R_MAX = sk_rounds_max(K, DENSE), OUT_CAP = sk_out_cap(R_MAX);
+    using T = TileGeom<K, P, SK_BLOCK, R_MAX>;
+    constexpr int WINDOW = T::WINDOW, LANE_RD = T::LANE_RD, IN_CHUNKS = T::IN_CHUNKS;
     constexpr bool STAGED = !DENSE && sk_staged(K);          // per-byte work at staging, U and C from LDS
+    static_assert(R_MAX == 1 || STAGED, "only the staged form walks several rounds");
+    const uint32_t n_rounds = R_MAX > 1 ? rounds : 1u;
 
     __shared__ __attribute__((aligned(16))) uint32_t s_in[IN_CHUNKS * 4];
     __shared__ __attribute__((aligned(16))) uint32_t s_comp[STAGED ? IN_CHUNKS * 4 : 4];   // complement of s_in, byte for byte
     __shared__ unsigned int s_dirty;                          // some staged byte of the tile is not ACGT
-    __shared__ uint64_t s_out[SK_OUT_CAP];
+    __shared__ uint64_t s_out[OUT_CAP];
     __shared__ unsigned int s_cnt;
     __shared__ unsigned long long s_base;
-    const LdsSink<SK_OUT_CAP, SK_BLOCK> sink{{s_out}, &s_cnt, &s_base, {out}, out_count, out_cap};
+    const LdsSink<OUT_CAP, SK_BLOCK> sink{{s_out}, &s_cnt, &s_base, {out}, out_count, out_cap};
 
     const int tid = threadIdx.x;
     if (tid == 0) s_cnt = 0;
 
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint64_t base = tile * (uint64_t)TILE;
+        const uint64_t base = tile * ((uint64_t)n_rounds * WINDOW);
         if constexpr (STAGED) {
             if (tid == 0) s_dirty = 0;   // its readers of the previous tile are behind that tile's flush barrier
         }
         __syncthreads();   // previous tile's readers are done with s_in; s_cnt reset visible
         if constexpr (STAGED) {
-            stage_tile<IN_CHUNKS, true, SK_BLOCK>(seq, base, len, skip, s_in, s_comp, &s_dirty);
+            if constexpr (R_MAX > 1) stage_tile<IN_CHUNKS, true, SK_BLOCK>(seq, base, len, skip, s_in, s_comp, &s_dirty, T::chunks((int)n_rounds));
+            else stage_tile<IN_CHUNKS, true, SK_BLOCK>(seq, base, len, skip, s_in, s_comp, &s_dirty);
         } else {
             // stage_tile<IN_CHUNKS, false> (kmer_core.hpp), kept inline: through the function, in either shape of its loader, the
             // dense k = 1 goes from 64 to 66 VGPRs, the dense k = 25 from 128 to 130, the appending k = 18 from 96 to 98 -- a wave
@@ -87,7 +116,7 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
         }
         __syncthreads();
         uint32_t raw[LANE_RD];
-        read_window<LANE_RD, P>(s_in, tid, raw);
+        if constexpr (R_MAX == 1) read_window<LANE_RD, P>(s_in, tid, raw);
         auto emit = [&](int o, uint64_t h) {
             if constexpr (DENSE) {
                 const uint64_t pos = base + (uint64_t)tid * P + (uint64_t)o - skip;   // valid k-mers never start in the prefix
@@ -99,15 +128,26 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
         if constexpr (STAGED) {
             static_assert(!STAGED || P == 16, "the staged form reads whole 16-byte groups");
             uint32_t comp[LANE_RD];
-            read_window<LANE_RD, P>(s_comp, tid, comp);
-            const bool dirty = __builtin_amdgcn_readfirstlane(s_dirty) != 0;
-            process_lane_staged<K, P, true, sk_plain_mul(K, false)>(raw, comp, dirty, seed, thr, emit);
+            if constexpr (R_MAX == 1) {
+                read_window<LANE_RD, P>(s_comp, tid, comp);
+                const bool dirty = __builtin_amdgcn_readfirstlane(s_dirty) != 0;
+                process_lane_staged<K, P, true, sk_plain_mul(K, false)>(raw, comp, dirty, seed, thr, emit);
+            } else {
+                // the rounds of the tile, rolled: the position code stays one copy, its registers and its size what they were
+                const bool dirty = __builtin_amdgcn_readfirstlane(s_dirty) != 0;   // one flag for the whole tile
+#pragma unroll 1
+                for (uint32_t r = 0; r < n_rounds; ++r) {
+                    read_window<LANE_RD, P>(s_in, tid + (int)r * SK_BLOCK, raw);
+                    read_window<LANE_RD, P>(s_comp, tid + (int)r * SK_BLOCK, comp);
+                    process_lane_staged<K, P, true, sk_plain_mul(K, false)>(raw, comp, dirty, seed, thr, emit);
+                }
+            }
         } else {
             process_lane<K, P, !DENSE, sk_plain_mul(K, DENSE)>(raw, seed, thr, emit);
         }
         if constexpr (DENSE) continue;
         __syncthreads();
-        sink.flush(SK_OUT_CAP / 2);
+        sink.flush(OUT_CAP / 2);
     }
     if constexpr (DENSE) return;
     __syncthreads();
@@ -125,10 +165,13 @@ struct SketchLaunch {
     template <int K>
     static hipError_t launch(const uint8_t* d_seq, uint64_t len, uint64_t seed, uint64_t thr, uint64_t* d_out,
                              unsigned long long* d_count, uint64_t cap, hipStream_t stream) {
-        const TileSpan t = align_to_tiles(d_seq, len, (uint64_t)SK_BLOCK * 16);
+        // the rounds first: the tile count and the grid are those of the tile length this launch walks
+        constexpr uint32_t WINDOW = (uint32_t)SK_BLOCK * 16, R_MAX = (uint32_t)sk_rounds_max(K, DENSE);
+        const uint32_t rounds = sk_tile_rounds(thr, R_MAX, WINDOW, (uint32_t)sk_out_cap((int)R_MAX));
+        const TileSpan t = align_to_tiles(d_seq, len, (uint64_t)rounds * WINDOW);
         if (t.n_tiles == 0) return hipSuccess;
-        hipLaunchKernelGGL((sketch_dna_kernel<K, 16, DENSE>), dim3(sk_grid(t.n_tiles)), dim3(SK_BLOCK), 0, stream, t.seq, t.len, seed,
-                           thr, d_out, d_count, cap, t.n_tiles, t.skip);
+        hipLaunchKernelGGL((sketch_dna_kernel<K, 16, DENSE>), dim3(sk_grid(t.n_tiles, sk_grid_per_cu((int)R_MAX))), dim3(SK_BLOCK), 0, stream,
+                           t.seq, t.len, seed, thr, d_out, d_count, cap, t.n_tiles, t.skip, rounds);
         return hipGetLastError();
     }
 };

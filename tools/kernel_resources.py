@@ -10,7 +10,7 @@ Build the library twice (parent and change) with the remarks switched on and the
 
 then: python tools/kernel_resources.py before.log after.log [-o profiles/NAME.txt]
 
-Every kernel of every translation unit is compared (name demangled with c++filt when it is there).  The table lists the kernels
+Every kernel of every translation unit is compared, matched by its name demangled with c++filt and without its argument list.  The table lists the kernels
 whose VGPR count, occupancy, scratch, spill counts or LDS size differ, then a summary; the exit status is 1 when any kernel lost a
 wave per SIMD, gained scratch, gained a spill or changed its LDS size."""
 import re
@@ -64,8 +64,11 @@ def main():
     if dest:
         args.remove(dest)
     before, after = parse(args[0]), parse(args[1])
+    # matched by the demangled name without its argument list: a kernel that gains an argument is still the same kernel
+    nice = demangle(sorted(set(before) | set(after)))
+    before, after = {nice[n]: v for n, v in before.items()}, {nice[n]: v for n, v in after.items()}
     names = sorted(set(before) | set(after))
-    nice = demangle(names)
+    nice = {n: n for n in names}
     rows, worse, missing = [], [], []
     for n in names:
         b, a = before.get(n), after.get(n)

@@ -5,7 +5,8 @@ bench.py turns the counter SQ_INSTS_VALU into "fraction of the SIMDs' issue cycl
 instruction MIX.  Round 1-3 carried that average as a constant (3.76) from a one-off count.  This tool derives it from the code:
 
   1. compiles csrc/sketch.hip for gfx950 to assembly (hipcc --cuda-device-only -S; no GPU needed),
-  2. takes the kernel's main loop (one tile of 256 lanes x 16 positions per trip) and splits it into the HOT path and the
+  2. takes the kernel's main loop (one window of 256 lanes x 16 positions per trip: the rolled loop over a tile's window rounds,
+     nested in the tile loop; what a tile does once -- staging, the flush check -- is outside it) and splits it into the HOT path and the
      blocks that a wave-level branch (s_cbranch_vccz / vccnz / scc0 / scc1 over a forward region: "some lane of the wave has a
      bad byte / a tie / a hash that can still pass") skips -- bad bytes and canonical ties do not occur on random DNA, the hash is
      finished in 1 wave-step of 16 at scaled = 1000 (kmer_core.hpp),
@@ -101,17 +102,21 @@ def main():
         elif not t.startswith("."):
             items.append(("inst", t))
     label_at = {t: i for i, (k, t) in enumerate(items) if k == "label"}
-    # the main loop: the backward branch that spans the most instructions
-    best = None
+    # the main loop: the backward branch that spans the most instructions -- the tile loop -- and from there inwards while a loop
+    # nested in it holds more than half of it: the rolled loop over a tile's window rounds is the trip of 16 positions per lane
+    loops = []
     for i, (k, t) in enumerate(items):
         m = re.match(r"s_cbranch_\w+\s+(\.LBB\d+_\d+)", t) if k == "inst" else None
         if not m:
             m = re.match(r"s_branch\s+(\.LBB\d+_\d+)", t) if k == "inst" else None
         if m and m.group(1) in label_at and label_at[m.group(1)] < i:
-            span = i - label_at[m.group(1)]
-            if best is None or span > best[1] - best[0]:
-                best = (label_at[m.group(1)], i)
-    lo, hi = best
+            loops.append((label_at[m.group(1)], i))
+    lo, hi = max(loops, key=lambda l: l[1] - l[0])
+    while True:
+        inner = [l for l in loops if lo <= l[0] and l[1] <= hi and l != (lo, hi) and 2 * (l[1] - l[0]) > hi - lo]
+        if not inner:
+            break
+        lo, hi = max(inner, key=lambda l: l[1] - l[0])
 
     def through(label):
         "the label a branch to `label` ends at: an out-of-line block holding only `s_branch X` is followed to X"
