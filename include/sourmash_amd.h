@@ -348,6 +348,11 @@ SourmashSignature **smgpu_sketch_file_singleton(const char *path, const Sourmash
  * count to *d_count (device u64, caller zeroes).  Fully asynchronous. */
 void smgpu_sketch_dna_kernel_raw(const uint8_t *d_seq, uint64_t len, uint32_t ksize, uint64_t seed, uint64_t max_hash,
                                  uint64_t *d_out, uint64_t out_capacity, uint64_t *d_count, void *stream);
+/* The same with a workgroup count: grid == 0 is the library's own choice, otherwise exactly `grid` workgroups (at most
+ * 1048576), which take the tiles behind their first from the launch's ticket counter wherever there are more tiles than
+ * workgroups.  For tests: many tiles per workgroup on a small input.  ksize <= 88; longer k-mers ignore `grid`. */
+void smgpu_sketch_dna_kernel_grid_raw(const uint8_t *d_seq, uint64_t len, uint32_t ksize, uint64_t seed, uint64_t max_hash,
+                                      uint64_t *d_out, uint64_t out_capacity, uint64_t *d_count, uint32_t grid, void *stream);
 /* Union of hash vectors on the device (the `merge` of flat scaled sketches, src/core/src/sketch/minhash.rs:432-516, for
  * vectors already in HBM -- e.g. the all-gathered per-rank sketches): d_keys[0, n) in any order, duplicates allowed ->
  * the sorted distinct values in d_out[0, m) (capacity n); *d_n_out (device u64) = m.  d_keys is used as scratch.  The

@@ -919,6 +919,15 @@ void smgpu_sketch_dna_kernel_raw(const uint8_t* d_seq, uint64_t len, uint32_t ks
                                     (unsigned long long*)d_count, cap, (hipStream_t)stream), "sketch_dna");
     });
 }
+void smgpu_sketch_dna_kernel_grid_raw(const uint8_t* d_seq, uint64_t len, uint32_t ksize, uint64_t seed, uint64_t max_hash,
+                                      uint64_t* d_out, uint64_t cap, uint64_t* d_count, uint32_t grid, void* stream) {
+    landing_void([&] {
+        check_dna_ksize(ksize);
+        if (grid > (1u << 20)) throw err_internal("grid: at most 1048576 workgroups");
+        hip_check(sketch_dna_launch_grid(d_seq, len, ksize, seed, max_hash ? max_hash : ~0ull, d_out,
+                                         (unsigned long long*)d_count, cap, grid, (hipStream_t)stream), "sketch_dna");
+    });
+}
 
 // The kernels behind protein / dayhoff / hp sketches on device-resident input (benchmarks; the object API goes through
 // DeviceCtx::protein_sketch_host): residues of a protein sequence, or the six-frame translation of DNA (signature.rs:307-393), into

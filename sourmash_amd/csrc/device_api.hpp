@@ -1,5 +1,5 @@
 // Internal C++ interface between the HIP translation units and the C-ABI layer.
-// Everything here takes raw device pointers and a stream and never allocates.
+// Everything here takes raw device pointers and a stream; what a launch needs besides comes from the arena in stream order.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,6 +14,9 @@ namespace smg {
 // (an unaligned start costs nothing: the kernel realigns and blanks the prefix).  Any byte outside ACGTacgt kills the k-mers covering it.
 hipError_t sketch_dna_launch(const uint8_t* d_seq, uint64_t len, uint32_t k, uint64_t seed, uint64_t thr,
                              uint64_t* d_out, unsigned long long* d_count, uint64_t cap, hipStream_t stream);
+// The same with `grid` workgroups exactly (0: the launcher's own number) where k <= 88; longer k-mers take their own kernel's grid.
+hipError_t sketch_dna_launch_grid(const uint8_t* d_seq, uint64_t len, uint32_t k, uint64_t seed, uint64_t thr,
+                                  uint64_t* d_out, unsigned long long* d_count, uint64_t cap, uint32_t grid, hipStream_t stream);
 // d_out[i] = hash of the canonical k-mer starting at i for i in [0, n_kmers) (0 for k-mers
 // covering a byte outside ACGTacgt).  d_out must be zeroed by the caller.
 // k-mers longer than the register-window kernel holds (sketch_words.hip): k = 129 .. sketch_dna_max_k(), any k >= 16 accepted

@@ -348,6 +348,14 @@ SMG_HD uint32_t sk_tile_rounds(uint64_t thr, uint32_t r_max, uint32_t window, ui
     return expected + 1 > cap / 4 ? 1u : r_max;
 }
 
+// Which tiles a workgroup of the appending sketch kernel walks when they are handed out by tickets (sketch_kernel.hpp): its first
+// tile is its own index, without a ticket; the tile behind ticket t of the launch's counter (0, 1, 2, .. in the order the
+// workgroups ask) is grid + t; a workgroup is done at the first index that is no tile.  Every tile of [0, n_tiles) is then walked
+// once whatever the order of the tickets, and each workgroup that had a tile takes exactly one ticket that fails.
+SMG_HD uint64_t tile_first(uint32_t workgroup) { return workgroup; }
+SMG_HD uint64_t tile_from_ticket(uint32_t grid, uint64_t ticket) { return (uint64_t)grid + ticket; }
+SMG_HD bool tile_end(uint64_t tile, uint64_t n_tiles) { return tile >= n_tiles; }
+
 // The 16 bytes at seq + off as 4 little-endian dwords: zero past `len`, and the first `skip` (< 16) bytes of the buffer blanked.
 // seq + off is 16-byte aligned.
 SMG_HD void load_chunk(const uint8_t* seq, uint64_t off, uint64_t len, uint32_t skip, uint32_t* w) {

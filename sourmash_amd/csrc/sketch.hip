@@ -14,7 +14,10 @@
 // the lanes read both (process_lane_staged); from k = 19 on it stages three such
 // windows as one tile and takes the lanes through them in a rolled loop, so that
 // the tile's barriers and the wait for its global loads come once per 12,288
-// positions (sketch_kernel.hpp, SK_R_MAX).  Kept hashes (about 1 in `scaled`) are
+// positions (sketch_kernel.hpp, SK_R_MAX).  A launch with more tiles than workgroups
+// starts as many workgroups as are resident at once and hands every tile behind a
+// workgroup's first out by a ticket from a counter of its own (sk_handout), so that
+// no workgroup's share is fixed at launch.  Kept hashes (about 1 in `scaled`) are
 // appended to a per-workgroup LDS buffer and flushed to HBM with one global
 // atomic per flush, so the single output counter sees a few thousand atomics
 // per launch instead of one per kept hash.
@@ -105,15 +108,15 @@ SMG_KMER_PART(SketchLaunch<false>, 3)
 
 static hipError_t sketch_any(const uint8_t* d_seq, uint64_t len, uint32_t k, uint64_t seed, uint64_t thr,
                              uint64_t* d_out, unsigned long long* d_count, uint64_t cap, bool dense,
-                             hipStream_t stream) {
+                             hipStream_t stream, uint32_t grid = 0) {
     if (len < k || k == 0) return hipSuccess;
     static const bool generic_only = [] { const char* e = getenv("SMG_SKETCH_GENERIC"); return e && *e == '1'; }();
     constexpr uint32_t words_from = (uint32_t)FAST_MAX_K + 1u;         // from this k on the run-time-k kernel is taken (it accepts any k >= 16)
     if (k >= words_from && !generic_only) return sketch_dna_words_launch(d_seq, len, k, seed, thr, d_out, d_count, cap, dense, stream);
     if (!dense && k <= (uint32_t)FAST_MAX_K && !generic_only)
-        return launcher<SketchLaunch<false>>(k)(d_seq, len, seed, thr, d_out, d_count, cap, stream);
+        return launcher<SketchLaunch<false>>(k)(d_seq, len, seed, thr, d_out, d_count, cap, grid, stream);
     if (dense && k <= (uint32_t)FAST_MAX_K && !generic_only)          // per-position output (seq_to_hashes): every k <= 88 (sketch_dense.hip)
-        return launcher<SketchLaunch<true>>(k)(d_seq, len, seed, thr, d_out, d_count, cap, stream);
+        return launcher<SketchLaunch<true>>(k)(d_seq, len, seed, thr, d_out, d_count, cap, 0, stream);
     // longer k-mers: 16 key bytes at a time from the staged stretch (sketch_words.hip); the byte loop below stays as the form the
     // others are tested against (SMG_SKETCH_GENERIC=1, k <= 256)
     if (!generic_only || k > (uint32_t)GENERIC_MAX_K) return sketch_dna_words_launch(d_seq, len, k, seed, thr, d_out, d_count, cap, dense, stream);
@@ -126,6 +129,11 @@ static hipError_t sketch_any(const uint8_t* d_seq, uint64_t len, uint32_t k, uin
 hipError_t sketch_dna_launch(const uint8_t* d_seq, uint64_t len, uint32_t k, uint64_t seed, uint64_t thr,
                              uint64_t* d_out, unsigned long long* d_count, uint64_t cap, hipStream_t stream) {
     return sketch_any(d_seq, len, k, seed, thr, d_out, d_count, cap, false, stream);
+}
+
+hipError_t sketch_dna_launch_grid(const uint8_t* d_seq, uint64_t len, uint32_t k, uint64_t seed, uint64_t thr,
+                                  uint64_t* d_out, unsigned long long* d_count, uint64_t cap, uint32_t grid, hipStream_t stream) {
+    return sketch_any(d_seq, len, k, seed, thr, d_out, d_count, cap, false, stream, grid);
 }
 
 hipError_t kmer_hashes_launch(const uint8_t* d_seq, uint64_t len, uint32_t k, uint64_t seed, uint64_t* d_out,

@@ -8,6 +8,7 @@
 #include <utility>
 #include "kmer_core.hpp"
 #include "tile_launch.hpp"
+#include "arena.hpp"
 
 namespace smg {
 
@@ -44,14 +45,27 @@ static_assert(SK_R_MAX >= 1 && SK_R_MAX <= 3, "four rounds do not fit four workg
 constexpr bool sk_one_round(int k) { return k <= 17; }      // k = 12, 13: six workgroups per CU, 14 .. 17: five
 constexpr int sk_rounds_max(int k, bool dense) { return !dense && sk_staged(k) && !sk_one_round(k) ? SK_R_MAX : 1; }
 constexpr int sk_out_cap(int r_max) { return r_max >= 3 ? SK_OUT_CAP / 2 : SK_OUT_CAP; }
-// Workgroups per CU a launch may ask for (tile_launch.hpp, sk_grid).  The long tiles are handed out by static stride like the
-// short ones, and with three times fewer of them the end of the launch weighs more: at k = 31 a step of the benchmark took
-// 29.2 ms with 2,048 workgroups, 28.2 with 4,096 and 27.7 with 8,192 (profiles/tile_rounds_bench.txt).  SMG_SK_GRID_PER_CU: a
-// variant build that measures another cap, for every instantiation.
-#ifdef SMG_SK_GRID_PER_CU
-constexpr unsigned sk_grid_per_cu(int) { return SMG_SK_GRID_PER_CU; }
+// The appending form hands its tiles out by tickets where a launch has more tiles than workgroups (tile_counter below): a
+// workgroup's share is then what it gets through, not a fixed 1 / grid of the tiles, and the launch ends within one tile's time
+// of its last workgroup, whatever the grid.  An instantiation that would run fewer waves per SIMD with the ticket's LDS word
+// stays on the static stride; none does (profiles/tile_handout_kernel_resources.txt).  SMG_SK_STATIC_WALK: a variant build
+// without tickets, for A/B runs.
+#ifdef SMG_SK_STATIC_WALK
+constexpr bool sk_handout(int) { return false; }
 #else
-constexpr unsigned sk_grid_per_cu(int r_max) { return r_max > 1 ? 32 : 8; }
+constexpr bool sk_handout(int) { return true; }
+#endif
+// Workgroups per CU a launch may ask for (tile_launch.hpp, sk_grid); 0: as many workgroups as are resident at once
+// (sk_resident_grid), which is what a launch with tickets takes -- at k = 31 a step of the benchmark took 27.04 ms with the 1,024
+// resident workgroups, 27.01 with 2,048 and 27.03 with 8,192, a tie, and the smallest grid has the fewest start-ups and partial
+// flushes (profiles/tile_handout_bench.txt).  On the static stride the long tiles want a large grid, for with three times fewer of
+// them the end of the launch weighs more: 29.2 ms with 2,048 workgroups, 28.2 with 4,096, 27.7 with 8,192
+// (profiles/tile_rounds_bench.txt), 27.5 with 16,384 and 27.3 with 32,768.  SMG_SK_GRID_PER_CU: a variant build that measures
+// another cap, for every instantiation.
+#ifdef SMG_SK_GRID_PER_CU
+constexpr unsigned sk_grid_per_cu(int, bool) { return SMG_SK_GRID_PER_CU; }
+#else
+constexpr unsigned sk_grid_per_cu(int r_max, bool handout) { return handout ? 0 : r_max > 1 ? 32 : 8; }
 #endif
 
 // DENSE == false: append kept hashes (unordered) to out, count in *out_count.
@@ -61,10 +75,12 @@ template <int K, int P, bool DENSE>
 __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
     const uint8_t* __restrict__ seq, uint64_t len, uint64_t seed, uint64_t thr,
     uint64_t* __restrict__ out, unsigned long long* __restrict__ out_count, uint64_t out_cap,
-    uint64_t n_tiles, uint32_t skip, uint32_t rounds) {
+    uint64_t n_tiles, uint32_t skip, uint32_t rounds, unsigned long long* __restrict__ tile_counter) {
     // seq is 16-byte aligned; its first `skip` (< 16) bytes precede the caller's buffer and are
     // treated as invalid.  len includes them.  DENSE positions are reported relative to seq + skip.
     // A tile is `rounds` (1 .. R_MAX) windows of SK_BLOCK x P positions; n_tiles counts tiles of that length.
+    // tile_counter (appending form only): null, and the workgroups walk the tiles by stride; or a zeroed counter of this launch
+    // alone, and every tile behind a workgroup's first is handed out by a ticket from it (kmer_core.hpp, tile_first).
     constexpr int R_MAX = sk_rounds_max(K, DENSE), OUT_CAP = sk_out_cap(R_MAX);
     using T = TileGeom<K, P, SK_BLOCK, R_MAX>;
     constexpr int WINDOW = T::WINDOW, LANE_RD = T::LANE_RD, IN_CHUNKS = T::IN_CHUNKS;
@@ -78,12 +94,15 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
     __shared__ uint64_t s_out[OUT_CAP];
     __shared__ unsigned int s_cnt;
     __shared__ unsigned long long s_base;
+    __shared__ unsigned long long s_next;                     // the tile behind this one, where tickets hand them out
+    const bool handout = !DENSE && sk_handout(K) && tile_counter != nullptr;
     const LdsSink<OUT_CAP, SK_BLOCK> sink{{s_out}, &s_cnt, &s_base, {out}, out_count, out_cap};
 
     const int tid = threadIdx.x;
     if (tid == 0) s_cnt = 0;
 
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    uint64_t tile = tile_first(blockIdx.x);
+    while (!tile_end(tile, n_tiles)) {
         const uint64_t base = tile * ((uint64_t)n_rounds * WINDOW);
         if constexpr (STAGED) {
             if (tid == 0) s_dirty = 0;   // its readers of the previous tile are behind that tile's flush barrier
@@ -115,6 +134,11 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
             }
         }
         __syncthreads();
+        if constexpr (!DENSE && sk_handout(K)) {
+            // The ticket for the next tile, taken early: its round trip lies behind this tile's hashing.  No workgroup waits for
+            // another.  s_next is read behind the sink barrier below; its next writer is then behind the next tile's two barriers.
+            if (handout && tid == 0) s_next = tile_from_ticket(gridDim.x, atomicAdd(tile_counter, 1ull));
+        }
         uint32_t raw[LANE_RD];
         if constexpr (R_MAX == 1) read_window<LANE_RD, P>(s_in, tid, raw);
         auto emit = [&](int o, uint64_t h) {
@@ -145,8 +169,15 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
         } else {
             process_lane<K, P, !DENSE, sk_plain_mul(K, DENSE)>(raw, seed, thr, emit);
         }
-        if constexpr (DENSE) continue;
+        if constexpr (DENSE) { tile += gridDim.x; continue; }
         __syncthreads();
+        if (handout) {                                        // read by every lane in front of the next tile's first barrier; kept scalar
+            const unsigned long long next = s_next;
+            tile = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(next >> 32)) << 32) |
+                   (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)next);
+        } else {
+            tile += gridDim.x;
+        }
         sink.flush(OUT_CAP / 2);
     }
     if constexpr (DENSE) return;
@@ -154,24 +185,62 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
     sink.flush(1);
 }
 
-typedef hipError_t (*sketch_launch_fn)(const uint8_t*, uint64_t, uint64_t, uint64_t, uint64_t*, unsigned long long*, uint64_t, hipStream_t);
+typedef hipError_t (*sketch_launch_fn)(const uint8_t*, uint64_t, uint64_t, uint64_t, uint64_t*, unsigned long long*, uint64_t, uint32_t, hipStream_t);
+// Workgroups that are resident at once: the runtime's occupancy figure for the instantiation times the device's CUs, asked once.
+template <int K, bool DENSE>
+unsigned sk_resident_grid() {
+    static const unsigned resident = [] {
+        int per_cu = 0, dev = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)sketch_dna_kernel<K, 16, DENSE>, SK_BLOCK, 0) != hipSuccess ||
+            hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            per_cu < 1 || cus < 1) {
+            (void)hipGetLastError();
+            return 2048u;
+        }
+        return (unsigned)per_cu * (unsigned)cus;
+    }();
+    return resident;
+}
 // The launchers of sketch_dna_kernel<K, 16, DENSE>, one per ksize (tile_launch.hpp: launcher<SketchLaunch<DENSE>>(k)).  DENSE ==
 // false, the appending form: parts 0 .. 3 (k = 1 .. 64) in sketch.hip, 4 and 5 in sketch_long.hip.  DENSE == true, the
 // per-position form (kmerminhash_seq_to_hashes: one hash per k-mer start, 0 for bad k-mers): six parts in sketch_dense.hip.
+// grid: 0, the launcher's own number of workgroups, or exactly that many (the appending form; a test's way to many tiles per
+// workgroup on a small input).
 template <bool DENSE>
 struct SketchLaunch {
     using fn = sketch_launch_fn;
     static constexpr int KMAX = SK_FAST_MAX_K;
     template <int K>
     static hipError_t launch(const uint8_t* d_seq, uint64_t len, uint64_t seed, uint64_t thr, uint64_t* d_out,
-                             unsigned long long* d_count, uint64_t cap, hipStream_t stream) {
+                             unsigned long long* d_count, uint64_t cap, uint32_t grid, hipStream_t stream) {
         // the rounds first: the tile count and the grid are those of the tile length this launch walks
         constexpr uint32_t WINDOW = (uint32_t)SK_BLOCK * 16, R_MAX = (uint32_t)sk_rounds_max(K, DENSE);
         const uint32_t rounds = sk_tile_rounds(thr, R_MAX, WINDOW, (uint32_t)sk_out_cap((int)R_MAX));
         const TileSpan t = align_to_tiles(d_seq, len, (uint64_t)rounds * WINDOW);
         if (t.n_tiles == 0) return hipSuccess;
-        hipLaunchKernelGGL((sketch_dna_kernel<K, 16, DENSE>), dim3(sk_grid(t.n_tiles, sk_grid_per_cu((int)R_MAX))), dim3(SK_BLOCK), 0, stream,
-                           t.seq, t.len, seed, thr, d_out, d_count, cap, t.n_tiles, t.skip, rounds);
+        constexpr unsigned per_cu = sk_grid_per_cu((int)R_MAX, !DENSE && sk_handout(K));
+        unsigned g;
+        if (grid && !DENSE) {
+            g = grid;
+        } else if constexpr (per_cu == 0) {                  // exactly the workgroups that are resident at once
+            const unsigned resident = sk_resident_grid<K, DENSE>();
+            g = (unsigned)(t.n_tiles < resident ? t.n_tiles : resident);
+        } else {
+            g = sk_grid(t.n_tiles, per_cu);
+        }
+        // Tickets only where some workgroup has a second tile.  The counter is this launch's own: 8 bytes of the arena, taken,
+        // zeroed and released in the order of `stream`, so that neither the launch in front of this one on the stream nor one
+        // in flight on another stream (whose block this is not, or whose release the arena has this stream wait for) sees it.
+        ArenaBuf counter;
+        if constexpr (!DENSE && sk_handout(K)) {
+            if (t.n_tiles > g) {
+                hipError_t e = counter.get(8, stream);
+                if (e == hipSuccess) e = hipMemsetAsync(counter.p, 0, 8, stream);
+                if (e != hipSuccess) return e;
+            }
+        }
+        hipLaunchKernelGGL((sketch_dna_kernel<K, 16, DENSE>), dim3(g), dim3(SK_BLOCK), 0, stream,
+                           t.seq, t.len, seed, thr, d_out, d_count, cap, t.n_tiles, t.skip, rounds, counter.as<unsigned long long>());
         return hipGetLastError();
     }
 };

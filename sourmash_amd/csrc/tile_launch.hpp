@@ -23,8 +23,8 @@ inline TileSpan align_to_tiles(const uint8_t* d_seq, uint64_t len, uint64_t tile
 }
 
 // workgroups for a launch: one per tile up to per_cu (8) for each of the 256 CUs, the rest by grid stride.  n_tiles counts tiles of
-// the length the launch walks (a tile of the staged sketch kernel is several window rounds and its launcher asks for more
-// workgroups per CU, sketch_kernel.hpp).
+// the length the launch walks (a tile of the staged sketch kernel is several window rounds; its launcher starts the resident
+// workgroups and hands the tiles out by tickets, or asks for more workgroups per CU on the static stride, sketch_kernel.hpp).
 inline unsigned sk_grid(uint64_t n_tiles, unsigned per_cu = 8) {
     const uint64_t max_blocks = 256ull * per_cu;
     return (unsigned)(n_tiles < max_blocks ? n_tiles : max_blocks);

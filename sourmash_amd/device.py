@@ -154,11 +154,12 @@ class DeviceSketcher:
         rustcall(lib.smgpu_sketch_records_kernel_raw, _ptr(seq), seq.numel(), self.ksize, self.seed, self.max_hash,
                  _ptr(out_hashes), _ptr(out_positions), min(out_hashes.numel(), out_positions.numel()), _ptr(count), _stream(torch))
 
-    def kernel_only(self, seq, out, count):
-        "Just the k-mer kernel (no sort): appends to `out`, adds to `count` (int64[1], caller zeroes)."
+    def kernel_only(self, seq, out, count, grid=0):
+        """Just the k-mer kernel (no sort): appends to `out`, adds to `count` (int64[1], caller zeroes).  grid: 0 for the
+        library's own number of workgroups, otherwise exactly that many (ksize <= 88)."""
         torch = self.torch
-        rustcall(lib.smgpu_sketch_dna_kernel_raw, _ptr(seq), seq.numel(), self.ksize, self.seed, self.max_hash,
-                 _ptr(out), out.numel(), _ptr(count), _stream(torch))
+        rustcall(lib.smgpu_sketch_dna_kernel_grid_raw, _ptr(seq), seq.numel(), self.ksize, self.seed, self.max_hash,
+                 _ptr(out), out.numel(), _ptr(count), int(grid), _stream(torch))
 
 
 def sort_unique(keys):
