@@ -339,6 +339,17 @@ uint64_t smgpu_sketch_records_raw(const uint8_t *d_seq, uint64_t len, const uint
  * first byte in d_seq to d_positions; the count is added to *d_count (device u64, caller zeroes).  Fully asynchronous. */
 void smgpu_sketch_records_kernel_raw(const uint8_t *d_seq, uint64_t len, uint32_t ksize, uint64_t seed, uint64_t max_hash,
                                      uint64_t *d_hashes, uint64_t *d_positions, uint64_t capacity, uint64_t *d_count, void *stream);
+/* The FASTA / FASTQ parser by itself (csrc/fastx.hip), for tests and for callers that hold file bytes in HBM: d_raw[0,len) is the
+ * next piece of a FASTA (fastq == 0) or four-line FASTQ (fastq != 0) file.  The sequence bytes and one separator byte per record --
+ * the first byte of its header line -- go to d_out in order (room for len bytes).  d_result (device, 2 x u64): [0] = bytes kept
+ * of THIS piece, [1] += header lines of this piece (the caller zeroes it in front of the first piece).  d_carry (device, 4 bytes,
+ * the caller's for the whole file): {1, 1, 0, 0} in front of a FASTA file's first piece, {3, 1, 0, 0} of a FASTQ file's; the
+ * state behind the piece ({line state, ended on LF}) is left in d_carry[2,4) and, unless last_piece, copied to d_carry[0,2) for
+ * the next piece.  An empty piece sets d_result[0] = 0 and touches nothing else.  d_record_starts (NULL: not wanted): entry j =
+ * the offset in d_out just behind the j-th kept header byte of this piece, for j < record_capacity.  d_raw must be 16-byte
+ * aligned: any other pointer is refused with an error before anything is launched.  Scratch is the library's.  Asynchronous. */
+void smgpu_fastx_compact_raw(const uint8_t *d_raw, uint64_t len, int32_t fastq, uint8_t *d_carry, uint8_t *d_out, uint64_t *d_result,
+                             uint64_t *d_record_starts, uint64_t record_capacity, int32_t last_piece, void *stream);
 /* Every record of a FASTA / FASTQ file (plain or gzip, at most 2 GiB of text, resident as a whole) as a signature of its own,
  * holding every sketch of `params` (DNA, scaled, ksizes 1 .. 88): the device parses the file and reports where the records
  * start, one kernel pass per sketch covers all records.  Names are the header lines behind '>' / '@'.  *n = records.  Returns

@@ -2069,6 +2069,21 @@ void smgpu_sketch_records_kernel_raw(const uint8_t* d_seq, uint64_t len, uint32_
     });
 }
 
+void smgpu_fastx_compact_raw(const uint8_t* d_raw, uint64_t len, int32_t fastq, uint8_t* d_carry, uint8_t* d_out, uint64_t* d_result,
+                             uint64_t* d_record_starts, uint64_t record_capacity, int32_t last_piece, void* stream) {
+    landing_void([&] {
+        if (!d_carry || !d_result || (len && (!d_raw || !d_out))) throw err_internal("smgpu_fastx_compact_raw: null pointer");
+        if (reinterpret_cast<uintptr_t>(d_raw) % FASTX_RAW_ALIGN)                  // before anything is launched: the lanes load 16 bytes at a time
+            throw err_internal("smgpu_fastx_compact_raw: d_raw must be " + std::to_string(FASTX_RAW_ALIGN) + "-byte aligned");
+        hipStream_t st = (hipStream_t)stream;
+        const size_t temp_bytes = d_record_starts ? fastx_records_temp_bytes(len ? len : 1) : fastx_temp_bytes(len ? len : 1);
+        AsyncBuf temp(temp_bytes, st);
+        unsigned long long* res = reinterpret_cast<unsigned long long*>(d_result);
+        hip_check(fastx_compact_launch(d_raw, len, fastq ? 1 : 0, d_carry, nullptr, d_out, res, res + 1, temp.p, temp_bytes, st, last_piece != 0,
+                                       reinterpret_cast<unsigned long long*>(d_record_starts), record_capacity), "fastx");
+    });
+}
+
 SmgpuSketchSet* smgpu_sketchset_sketch_records(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, uint64_t n_records, uint32_t ksize,
                                                uint64_t seed, uint64_t scaled) {
     return landing<SmgpuSketchSet*>([&]() -> SmgpuSketchSet* {

@@ -26,86 +26,13 @@
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include "fastx_api.hpp"
+#include "fastx_core.hpp"
 
 namespace smg {
 
 namespace {
 
-constexpr int FX_THREADS = 256;
-constexpr int FX_PER_THREAD = 32;                              // consecutive bytes per lane (two 16-byte loads)
-constexpr int FX_BLOCK_BYTES = FX_THREADS * FX_PER_THREAD;     // 8 KiB per workgroup
-
-// what a block does to the state that enters it, and what it keeps as a function of that state
-struct BlockSum {
-    uint32_t cnt[4];     // FASTA: [0] kept bytes whatever enters, [1] more if a sequence line enters; FASTQ: kept bytes by entry phase
-    uint32_t hdr[4];     // FASTA: [0] header lines; FASTQ: header lines by entry phase
-    uint32_t starts;     // FASTQ: line starts in the block
-    uint32_t last_kind;  // FASTA: kind of the block's last line start (0: none)
-};
-
-// A lane's 32 bytes.  ls / nl / gt: bit j = byte j starts a line / is CR or LF / is '>'; bits at and above the lane's valid bytes are 0.
-struct LaneBits { uint32_t ls, nl, gt, valid; };
-__device__ __forceinline__ LaneBits lane_bits(const uint8_t* __restrict__ raw, uint64_t base, uint64_t n, uint8_t prev_nl_at_0, uint8_t* bytes) {
-    LaneBits b{0, 0, 0, 0};
-    if (base >= n) return b;
-    if (base + FX_PER_THREAD <= n) {
-        const uint4 r0 = *reinterpret_cast<const uint4*>(raw + base), r1 = *reinterpret_cast<const uint4*>(raw + base + 16);
-        memcpy(bytes, &r0, 16); memcpy(bytes + 16, &r1, 16);
-        b.valid = 0xffffffffu;
-    } else {
-        const int lim = (int)(n - base);
-        for (int j = 0; j < FX_PER_THREAD; ++j) bytes[j] = j < lim ? raw[base + j] : (uint8_t)'\n';
-        b.valid = (1u << lim) - 1u;                              // lim in 1 .. 31
-    }
-    bool prev_nl = base ? raw[base - 1] == '\n' : prev_nl_at_0 != 0;
-#pragma unroll
-    for (int j = 0; j < FX_PER_THREAD; ++j) {
-        const uint8_t c = bytes[j];
-        b.ls |= prev_nl ? (1u << j) : 0u;
-        b.nl |= (c == '\n' || c == '\r') ? (1u << j) : 0u;
-        b.gt |= c == '>' ? (1u << j) : 0u;
-        prev_nl = c == '\n';
-    }
-    b.ls &= b.valid; b.nl &= b.valid; b.gt &= b.valid;
-    return b;
-}
-
-// FASTA: keep masks of a lane if a header line (m2) / a sequence line (m1) enters it; kind of its last line start (0: none)
-__device__ __forceinline__ void fasta_masks(const LaneBits& b, uint32_t* m1, uint32_t* m2, uint32_t* last_kind) {
-    uint32_t keep = 0, on_seq = 0;
-    bool seq = false;                                              // entering on a header line: nothing kept before the first line start
-#pragma unroll
-    for (int j = 0; j < FX_PER_THREAD; ++j) {
-        const uint32_t bit = 1u << j;
-        if (b.ls & bit) seq = !(b.gt & bit);
-        on_seq |= seq ? bit : 0u;
-    }
-    const uint32_t hs = b.ls & b.gt;
-    keep = hs | (on_seq & ~b.nl & b.valid);
-    const uint32_t before_first = b.ls ? ((b.ls & (0u - b.ls)) - 1u) : 0xffffffffu;    // bits below the first line start
-    *m2 = keep;
-    *m1 = keep | (before_first & ~b.nl & b.valid);
-    *last_kind = b.ls ? ((hs >> (31 - __clz(b.ls))) & 1u ? 2u : 1u) : 0u;
-}
-
-// FASTQ: M[t] = bytes whose line number within the lane is t mod 4 (counting the lane's own line starts up to and including the byte)
-__device__ __forceinline__ void fastq_classes(const LaneBits& b, uint32_t (&M)[4]) {
-    M[0] = M[1] = M[2] = M[3] = 0;
-    uint32_t c = 0;
-#pragma unroll
-    for (int j = 0; j < FX_PER_THREAD; ++j) {
-        const uint32_t bit = 1u << j;
-        c += (b.ls >> j) & 1u;
-        const uint32_t t = c & 3u;
-        M[0] |= t == 0 ? bit : 0u; M[1] |= t == 1 ? bit : 0u; M[2] |= t == 2 ? bit : 0u; M[3] |= t == 3 ? bit : 0u;
-    }
-}
-// keep mask / header starts of a lane entered in phase q (the state of the byte in front of it, mod 4)
-__device__ __forceinline__ uint32_t fastq_keep(const LaneBits& b, const uint32_t (&M)[4], uint32_t q, uint32_t* headers) {
-    const uint32_t hl = M[(4u - q) & 3u], sl = M[(5u - q) & 3u];       // header line: q + t = 0, sequence line: q + t = 1 (mod 4)
-    *headers = hl & b.ls;
-    return (hl & b.ls) | (sl & ~b.nl & b.valid);
-}
+// BlockSum, LaneBits, the per-lane masks, the fold rules and the per-block step: fastx_core.hpp (shared with the host emulation)
 
 // exclusive scan over the workgroup's lanes: FASTA "last non-zero", FASTQ sum.  *total: the inclusive value of the last lane.
 template <bool LASTNZ>
@@ -115,7 +42,7 @@ __device__ __forceinline__ uint32_t block_excl(uint32_t v, uint32_t* s_wave, uin
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const uint32_t o = __shfl_up(incl, d);
-        if (lane >= d) incl = LASTNZ ? (incl ? incl : o) : incl + o;
+        if (lane >= d) incl = fx_fold<LASTNZ>(o, incl);
     }
     if (lane == 63) s_wave[wave] = incl;
     __syncthreads();
@@ -123,13 +50,13 @@ __device__ __forceinline__ uint32_t block_excl(uint32_t v, uint32_t* s_wave, uin
 #pragma unroll
     for (int w = 0; w < FX_THREADS / 64; ++w) {
         const uint32_t x = s_wave[w];
-        if (w < wave) before = LASTNZ ? (x ? x : before) : before + x;
-        all = LASTNZ ? (x ? x : all) : all + x;
+        if (w < wave) before = fx_fold<LASTNZ>(before, x);
+        all = fx_fold<LASTNZ>(all, x);
     }
     *total = all;
     uint32_t prev = __shfl_up(incl, 1);                          // inclusive value of the lane in front
     if (lane == 0) prev = 0u;
-    return LASTNZ ? (prev ? prev : before) : before + prev;
+    return fx_fold<LASTNZ>(before, prev);
 }
 
 __device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* s_red) {        // -> thread 0 holds the sum
@@ -178,47 +105,46 @@ __global__ __launch_bounds__(FX_THREADS) void fx_summary_kernel(const uint8_t* _
 }
 
 // one workgroup: entry state and output offset of every block, totals, the next piece's carry
-__global__ __launch_bounds__(1024) void fx_offsets_kernel(const BlockSum* __restrict__ sums, unsigned n_blocks, int fastq,
+__global__ __launch_bounds__(FX_SPANS) void fx_offsets_kernel(const BlockSum* __restrict__ sums, unsigned n_blocks, int fastq,
                                                           const uint8_t* __restrict__ raw, uint64_t n, const uint8_t* __restrict__ carry,
                                                           uint8_t* __restrict__ carry_out, uint8_t* __restrict__ entry,
                                                           unsigned long long* __restrict__ block_off, unsigned long long* __restrict__ total,
                                                           unsigned long long* __restrict__ n_records,
                                                           unsigned long long* __restrict__ block_rec) {
-    __shared__ unsigned long long part[1024];
-    __shared__ uint32_t st[1024];
-    const unsigned per = (n_blocks + 1023) / 1024;
+    __shared__ unsigned long long part[FX_SPANS];
+    __shared__ uint32_t st[FX_SPANS];
+    const unsigned per = (n_blocks + FX_SPANS - 1) / FX_SPANS;
     const unsigned lo = threadIdx.x * per, hi = lo + per < n_blocks ? lo + per : n_blocks;
     // what this thread's span does to the state
     uint32_t eff = 0;
     for (unsigned i = lo; i < hi; ++i) {
-        if (fastq) eff += sums[i].starts;
-        else { const uint32_t k = sums[i].last_kind; eff = k ? k : eff; }
+        if (fastq) eff = fx_fold<false>(eff, sums[i].starts);
+        else eff = fx_fold<true>(eff, sums[i].last_kind);
     }
     st[threadIdx.x] = eff;
     __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {                         // Hillis-Steele inclusive scan of the spans' effects
+    for (int d = 1; d < FX_SPANS; d <<= 1) {                         // Hillis-Steele inclusive scan of the spans' effects
         const uint32_t mine = st[threadIdx.x];
         const uint32_t v = threadIdx.x >= (unsigned)d ? st[threadIdx.x - d] : 0;
         __syncthreads();
-        st[threadIdx.x] = fastq ? mine + v : (mine ? mine : v);
+        st[threadIdx.x] = fastq ? fx_fold<false>(v, mine) : fx_fold<true>(v, mine);
         __syncthreads();
     }
     const uint32_t before = threadIdx.x ? st[threadIdx.x - 1] : 0u;
-    uint32_t e = fastq ? (uint32_t)((carry[0] + before) & 3u) : (before ? before : (uint32_t)carry[0]);
+    uint32_t e = fx_entry_state(fastq, carry, before);
     unsigned long long kept = 0, recs = 0;
-    for (unsigned i = lo; i < hi; ++i) {                          // (the summary is indexed in memory: a local copy indexed by the phase lands in scratch)
+    for (unsigned i = lo; i < hi; ++i) {                          // the per-block step (fastx_core.hpp)
         const BlockSum* s = sums + i;
         entry[i] = (uint8_t)e;
-        if (fastq) { kept += s->cnt[e & 3u]; recs += s->hdr[e & 3u]; e = (e + s->starts) & 3u; }
-        else { const uint32_t lk = s->last_kind; kept += s->cnt[0] + (e == 1u ? s->cnt[1] : 0u); recs += s->hdr[0]; e = lk ? lk : e; }
+        if (fastq) fx_block_step<true>(s, e, kept, recs); else fx_block_step<false>(s, e, kept, recs);
     }
     if (hi == n_blocks && lo < hi) {                             // the thread that owns the last block: the carry
         carry_out[0] = (uint8_t)e;
-        carry_out[1] = raw[n - 1] == '\n';
+        carry_out[1] = fx_ended_on_lf(raw[n - 1]);
     }
     part[threadIdx.x] = kept;
     __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
+    for (int d = 1; d < FX_SPANS; d <<= 1) {
         const unsigned long long v = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0;
         __syncthreads();
         part[threadIdx.x] += v;
@@ -229,14 +155,14 @@ __global__ __launch_bounds__(1024) void fx_offsets_kernel(const BlockSum* __rest
         const BlockSum* s = sums + i;
         const uint32_t ei = entry[i];
         block_off[i] = run;
-        run += fastq ? s->cnt[ei & 3u] : s->cnt[0] + (ei == 1u ? s->cnt[1] : 0u);
+        run += fx_block_kept(s, fastq, ei);
     }
-    if (threadIdx.x == 1023) *total = part[1023];
+    if (threadIdx.x == FX_SPANS - 1) *total = part[FX_SPANS - 1];
     // records: a sum over the threads through the same scratch
     __syncthreads();
     part[threadIdx.x] = recs;
     __syncthreads();
-    for (int d = 512; d > 0; d >>= 1) {
+    for (int d = FX_SPANS / 2; d > 0; d >>= 1) {
         if (threadIdx.x < (unsigned)d) part[threadIdx.x] += part[threadIdx.x + d];
         __syncthreads();
     }
@@ -246,7 +172,7 @@ __global__ __launch_bounds__(1024) void fx_offsets_kernel(const BlockSum* __rest
     __syncthreads();
     part[threadIdx.x] = recs;
     __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
+    for (int d = 1; d < FX_SPANS; d <<= 1) {
         const unsigned long long v = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0;
         __syncthreads();
         part[threadIdx.x] += v;
@@ -255,7 +181,7 @@ __global__ __launch_bounds__(1024) void fx_offsets_kernel(const BlockSum* __rest
     unsigned long long ord = threadIdx.x ? part[threadIdx.x - 1] : 0;
     for (unsigned i = lo; i < hi; ++i) {
         block_rec[i] = ord;
-        ord += fastq ? sums[i].hdr[entry[i] & 3u] : sums[i].hdr[0];
+        ord += fx_block_records(sums + i, fastq, entry + i);
     }
 }
 
@@ -294,7 +220,7 @@ __global__ __launch_bounds__(FX_THREADS) void fx_scatter_kernel(const uint8_t* _
         const unsigned long long at = block_off[blockIdx.x] + pos;
         for (uint32_t h = hdr; h; h &= h - 1u, ++ord) {
             const uint32_t below = (h & (0u - h)) - 1u;
-            if (ord < rec_cap) rec_starts[ord] = at + __popc(mask & below) + 1u;
+            if (ord < rec_cap) rec_starts[ord] = fx_record_start(at, mask, below);
         }
     }
 #pragma unroll
@@ -343,7 +269,7 @@ hipError_t fastx_compact_launch(const uint8_t* d_raw, uint64_t n, int fastq, uin
     unsigned long long* block_rec = d_record_starts ? reinterpret_cast<unsigned long long*>((char*)d_temp + fastx_temp_bytes(n)) : nullptr;
     // the carry is read (first byte) and rewritten (last byte) by the same launches: go through a second slot
     hipLaunchKernelGGL(fx_summary_kernel, dim3((unsigned)n_blocks), dim3(FX_THREADS), 0, stream, d_raw, n, fastq, d_carry, sums);
-    hipLaunchKernelGGL(fx_offsets_kernel, dim3(1), dim3(1024), 0, stream, (const BlockSum*)sums, (unsigned)n_blocks, fastq, d_raw, n, d_carry,
+    hipLaunchKernelGGL(fx_offsets_kernel, dim3(1), dim3(FX_SPANS), 0, stream, (const BlockSum*)sums, (unsigned)n_blocks, fastq, d_raw, n, d_carry,
                        d_carry + 2, entry, block_off, d_n_out, d_n_records, block_rec);
     hipLaunchKernelGGL(fx_scatter_kernel, dim3((unsigned)n_blocks), dim3(FX_THREADS), 0, stream, d_raw, n, fastq, d_carry, (const uint8_t*)entry,
                        (const unsigned long long*)block_off, d_out, (const unsigned long long*)block_rec, d_record_starts, record_cap);

@@ -6,9 +6,14 @@
 
 namespace smg {
 
+// d_raw of fastx_compact_launch is aligned to this many bytes: every lane loads its 32 bytes as two 16-byte words.  All callers
+// pass the start of an arena block, of a 256-byte aligned slice of one, or a multiple of the ingest chunk behind one (ingest.hpp
+// keeps that chunk a multiple of 16 bytes); smgpu_fastx_compact_raw refuses anything else.
+constexpr size_t FASTX_RAW_ALIGN = 16;
+
 // scratch for one fastx_compact_launch over at most max_chunk bytes
 size_t fastx_temp_bytes(uint64_t max_chunk);
-// d_raw[0,n): the next piece of a FASTA (fastq == 0) or 4-line FASTQ (fastq == 1) file.  Sequence bytes and one
+// d_raw[0,n), FASTX_RAW_ALIGN-aligned: the next piece of a FASTA (fastq == 0) or 4-line FASTQ (fastq == 1) file.  Sequence bytes and one
 // separator byte per record go to d_out in order, their number to *d_n_out; *d_n_records += header lines seen.
 // d_carry: 4 bytes chaining consecutive pieces (initialise to {1, 1, 0, 0} for FASTA, {3, 1, 0, 0} for FASTQ);
 // d_state: unused since round 6 (may be null).  last_piece: nothing follows this piece -- the carry is left in d_carry[2, 4) and

@@ -442,10 +442,14 @@ inline void sketch_file_with(IngestWorker& w, std::vector<KmerMinHash*>& mhs, co
     auto stage = [&](int64_t seq) -> Staged {
         Staged c;
         if (d_plain) {
-            const uint64_t off = (uint64_t)seq * CHUNK;
+            // slices of the inflated block are parsed in place, and the parser wants its input FASTX_RAW_ALIGN-aligned
+            // (fastx_api.hpp): an odd SMG_INGEST_CHUNK (a test knob; the built-in sizes are powers of two) is rounded down to a
+            // multiple of 16 bytes here.  Chunks copied up from the host start at the head of raw[b] and keep their size.
+            const uint64_t slice = CHUNK & ~(uint64_t)(FASTX_RAW_ALIGN - 1);
+            const uint64_t off = (uint64_t)seq * slice;
             if (off >= plain_len) return c;
             c.ok = true;
-            c.len = (size_t)std::min<uint64_t>(CHUNK, plain_len - off);
+            c.len = (size_t)std::min<uint64_t>(slice, plain_len - off);
             c.dev = static_cast<const uint8_t*>(d_plain) + off;
             return c;
         }

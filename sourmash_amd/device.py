@@ -57,6 +57,28 @@ def synth_dna(n, seed=42, record_len=0, start=0, device="cuda", out=None):
     return out
 
 
+def fastx_carry(fastq, device="cuda"):
+    "the 4-byte parser carry in front of a file's first piece: {1, 1, 0, 0} for FASTA, {3, 1, 0, 0} for FASTQ"
+    torch = _torch()
+    return torch.tensor([3 if fastq else 1, 1, 0, 0], dtype=torch.uint8, device=device)
+
+
+def fastx_compact(raw, fastq, carry, out, result, record_starts=None, last_piece=False):
+    """The FASTA / FASTQ parser by itself (smgpu_fastx_compact_raw, csrc/fastx.hip) on the next piece of a file held in HBM.
+
+    raw: uint8 tensor, 16-byte aligned (any other pointer raises before anything is launched); carry: the file's 4 bytes
+    (fastx_carry); out: uint8, room for raw.numel() bytes; result: int64[2], [0] = bytes kept of this piece, [1] += its header
+    lines; record_starts: int64 tensor or None, entry j = offset in `out` just behind the j-th kept header byte of this piece.
+    Asynchronous on the current stream."""
+    torch = _torch()
+    assert raw.dtype == torch.uint8 and out.dtype == torch.uint8 and carry.dtype == torch.uint8 and carry.numel() >= 4
+    assert result.dtype == torch.int64 and result.numel() >= 2 and out.numel() >= raw.numel()
+    assert record_starts is None or record_starts.dtype == torch.int64
+    rustcall(lib.smgpu_fastx_compact_raw, _ptr(raw), raw.numel(), 1 if fastq else 0, _ptr(carry), _ptr(out), _ptr(result),
+             _ptr(record_starts) if record_starts is not None else None, record_starts.numel() if record_starts is not None else 0,
+             1 if last_piece else 0, _stream(torch))
+
+
 def _records_error(code, message):
     "the exception of a failed per-record call: starts the library refuses are the caller's ValueError"
     if "record starts" in message:
