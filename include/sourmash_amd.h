@@ -350,6 +350,20 @@ void smgpu_sketch_records_kernel_raw(const uint8_t *d_seq, uint64_t len, uint32_
  * aligned: any other pointer is refused with an error before anything is launched.  Scratch is the library's.  Asynchronous. */
 void smgpu_fastx_compact_raw(const uint8_t *d_raw, uint64_t len, int32_t fastq, uint8_t *d_carry, uint8_t *d_out, uint64_t *d_result,
                              uint64_t *d_record_starts, uint64_t record_capacity, int32_t last_piece, void *stream);
+/* The signature JSON array parser by itself (csrc/sigjson.hip), for tests: d_text[0, text_len) is a block of JSON text in HBM,
+ * docs (host) n_docs pairs {off, len} of documents inside it.  The span scan runs on all documents, the `mins` arrays of every
+ * document with nothing odd become the jobs of ONE parse launch -- planned by the function the collection loader plans with
+ * (csrc/sigjson_api.hpp: sj_plan) -- and their values go to d_values (device, value_capacity entries) side by side in job order.
+ * To the host: spans_out, n_docs x 8 records {u64 begin, end; u32 n_values, kind (0 mins, 1 abundances), flags (1 odd), pad}, of
+ * which the first doc_flags & 0xff are written; flags_out, n_docs x u32 (bit 31: the document is odd); parsed_out, one record
+ * {u32 n_kept, flags (1: not plain ascending numbers)} per job, parsed_capacity records; counts_out[0] = jobs, [1] = values.
+ * The parse kernel loads whole 16-byte lines: smgpu_sigjson_text_pad() bytes behind d_text[text_len) must be readable (the
+ * device inflater's output has them).  Refused with an error before anything is launched: a null pointer, a document that
+ * reaches outside the text.  An error after the span scan: more jobs or values than the capacities.  Synchronises the stream. */
+uint64_t smgpu_sigjson_text_pad(void);
+void smgpu_sigjson_parse_raw(const uint8_t *d_text, uint64_t text_len, const uint64_t *docs, uint32_t n_docs, uint64_t keep_max,
+                             void *spans_out, uint32_t *flags_out, uint64_t *d_values, uint64_t value_capacity, void *parsed_out,
+                             uint64_t parsed_capacity, uint64_t *counts_out, void *stream);
 /* Every record of a FASTA / FASTQ file (plain or gzip, at most 2 GiB of text, resident as a whole) as a signature of its own,
  * holding every sketch of `params` (DNA, scaled, ksizes 1 .. 88): the device parses the file and reports where the records
  * start, one kernel pass per sketch covers all records.  Names are the header lines behind '>' / '@'.  *n = records.  Returns

@@ -2084,6 +2084,47 @@ void smgpu_fastx_compact_raw(const uint8_t* d_raw, uint64_t len, int32_t fastq, 
     });
 }
 
+uint64_t smgpu_sigjson_text_pad(void) { return SJ_TEXT_PAD; }
+
+void smgpu_sigjson_parse_raw(const uint8_t* d_text, uint64_t text_len, const uint64_t* docs, uint32_t n_docs, uint64_t keep_max, void* spans_out,
+                             uint32_t* flags_out, uint64_t* d_values, uint64_t value_capacity, void* parsed_out, uint64_t parsed_capacity,
+                             uint64_t* counts_out, void* stream) {
+    landing_void([&] {
+        if (!counts_out) throw err_internal("smgpu_sigjson_parse_raw: null pointer");
+        counts_out[0] = counts_out[1] = 0;
+        if (n_docs == 0) return;
+        if (!d_text || !docs || !spans_out || !flags_out || !d_values || !parsed_out) throw err_internal("smgpu_sigjson_parse_raw: null pointer");
+        std::vector<SjDoc> dv(n_docs);
+        for (uint32_t d = 0; d < n_docs; ++d) {
+            dv[d] = SjDoc{docs[2 * d], docs[2 * d + 1]};
+            if (dv[d].off > text_len || dv[d].len > text_len - dv[d].off) throw err_internal("smgpu_sigjson_parse_raw: document " + std::to_string(d) + " reaches outside the text");
+        }
+        hipStream_t st = (hipStream_t)stream;
+        AsyncBuf d_docs(dv.size() * sizeof(SjDoc), st), d_spans(dv.size() * SJ_MAX_SPANS * sizeof(SjSpan), st), d_flags(dv.size() * 4, st);
+        hip_check(hipMemcpyAsync(d_docs.p, dv.data(), dv.size() * sizeof(SjDoc), hipMemcpyHostToDevice, st), "H2D");
+        hip_check(sj_spans_launch(d_text, d_docs.as<SjDoc>(), n_docs, d_spans.as<SjSpan>(), d_flags.as<uint32_t>(), st), "sj_spans");
+        std::vector<SjSpan> spans(dv.size() * SJ_MAX_SPANS);
+        hip_check(hipMemcpyAsync(spans.data(), d_spans.p, spans.size() * sizeof(SjSpan), hipMemcpyDeviceToHost, st), "D2H");
+        hip_check(hipMemcpyAsync(flags_out, d_flags.p, dv.size() * 4, hipMemcpyDeviceToHost, st), "D2H");
+        hip_check(hipStreamSynchronize(st), "sync");
+        SjSpan* so = static_cast<SjSpan*>(spans_out);                  // (the records a document does not have stay the caller's)
+        for (size_t d = 0; d < dv.size(); ++d)
+            for (uint32_t s = 0; s < (flags_out[d] & 0xffu) && s < SJ_MAX_SPANS; ++s) so[d * SJ_MAX_SPANS + s] = spans[d * SJ_MAX_SPANS + s];
+        SjPlan planned;
+        sj_plan(dv, spans.data(), flags_out, planned);
+        counts_out[0] = planned.jobs.size(); counts_out[1] = planned.n_values;
+        if (planned.jobs.size() > parsed_capacity || planned.n_values > value_capacity || planned.jobs.size() > 0x7fffffffull)
+            throw err_internal("smgpu_sigjson_parse_raw: " + std::to_string(planned.jobs.size()) + " jobs with " + std::to_string(planned.n_values) +
+                               " values do not fit the capacities");
+        if (planned.jobs.empty()) return;
+        AsyncBuf d_jobs(planned.jobs.size() * sizeof(SjParse), st), d_parsed(planned.jobs.size() * sizeof(SjParsed), st);
+        hip_check(hipMemcpyAsync(d_jobs.p, planned.jobs.data(), planned.jobs.size() * sizeof(SjParse), hipMemcpyHostToDevice, st), "H2D");
+        hip_check(sj_parse_launch(d_text, d_jobs.as<SjParse>(), (uint32_t)planned.jobs.size(), d_values, d_parsed.as<SjParsed>(), keep_max, st), "sj_parse");
+        hip_check(hipMemcpyAsync(parsed_out, d_parsed.p, planned.jobs.size() * sizeof(SjParsed), hipMemcpyDeviceToHost, st), "D2H");
+        hip_check(hipStreamSynchronize(st), "sync");
+    });
+}
+
 SmgpuSketchSet* smgpu_sketchset_sketch_records(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, uint64_t n_records, uint32_t ksize,
                                                uint64_t seed, uint64_t scaled) {
     return landing<SmgpuSketchSet*>([&]() -> SmgpuSketchSet* {

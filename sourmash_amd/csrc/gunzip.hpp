@@ -38,6 +38,7 @@ inline GunzipCounters& gunzip_counters() { static GunzipCounters c; return c; }
 
 // Bytes the device buffer of the files must have behind total_bytes (zeroed): the scan reads whole words past the end.
 constexpr size_t GUNZIP_PAD = 1024;       // (the block walk keeps 128 words in flight behind its position)
+constexpr size_t GUNZIP_OUT_PAD = 256;    // bytes allocated behind the inflated text: its readers load whole lines (sigjson_core.hpp: SJ_TEXT_PAD)
 
 // h_files / d_files: the same total_bytes on the host and on the device; d_files 8-byte aligned with GUNZIP_PAD zero bytes behind.
 // *d_out: an arena block (the caller releases it with arena_free(*d_out, stream)) or nullptr when no member inflated.
@@ -196,7 +197,7 @@ inline void gunzip_device(const uint8_t* h_files, const uint8_t* d_files, uint64
     // ---- pass 2, tails, resolve, crc ----
     t0 = clk::now();
     void* out = nullptr;
-    hip_check(arena_alloc(&out, total_out + 256, stream), "arena_alloc");
+    hip_check(arena_alloc(&out, total_out + GUNZIP_OUT_PAD, stream), "arena_alloc");
     struct FreeOut { void*& p; hipStream_t st; bool keep = false; ~FreeOut() { if (p && !keep) { arena_free(p, st); p = nullptr; } } } free_out{out, stream};
     {
         AsyncBuf sym(total_out * 2 + 256, stream);

@@ -15,14 +15,18 @@
 //   sj_take_u64       the kept prefix of every selected array -> its row of the CSR
 // Anything unusual in an array (a float, a minus sign, unsorted or repeated values, more arrays than slots) flags the document
 // and the host parses it as before: the result is the host's result or an error, never something else.
+//
+// The rules of both kernels -- the key match, the tile tallies, the chunk geometry, the number parser with its overflow and
+// termination rules, the order pass -- are in sigjson_core.hpp, which also compiles for the host; here are the thread indices, the
+// ballots, the prefix sum and the reduction.  tests/sigjson_cases.py holds a reference written from the rules and the named
+// cases at every seam (lane, chunk, look-ahead, alignment, 2^64, keep_max, tile bits); tests/test_sigjson_core_cpu.py runs them
+// through a host emulation (tests/native/sigjson_emul.cpp), tests/test_gpu_sigjson_edges.py through smgpu_sigjson_parse_raw.
 #include <hip/hip_runtime.h>
 #include "sigjson_api.hpp"
 
 namespace smg {
 
 namespace {
-
-__device__ __forceinline__ bool is_ws(uint32_t c) { return c == ' ' || c == '\n' || c == '\r' || c == '\t'; }
 
 // first position >= from (< len) whose byte satisfies pred, by 64-byte tiles; len if none.  Uniform result.
 template <class Pred>
@@ -37,12 +41,6 @@ __device__ __forceinline__ uint64_t find_first(const uint8_t* t, uint64_t from, 
     return len;
 }
 
-__device__ __forceinline__ bool starts_with(const uint8_t* t, uint64_t i, uint64_t len, const char* key, uint32_t klen) {
-    if (i + klen > len) return false;
-    for (uint32_t k = 0; k < klen; ++k) if (t[i + k] != (uint8_t)key[k]) return false;
-    return true;
-}
-
 __global__ __launch_bounds__(64) void sj_spans_kernel(const uint8_t* __restrict__ base, const SjDoc* __restrict__ docs, uint32_t n_docs,
                                                       SjSpan* __restrict__ spans, uint32_t* __restrict__ doc_flags) {
     const uint32_t d = blockIdx.x;
@@ -55,42 +53,23 @@ __global__ __launch_bounds__(64) void sj_spans_kernel(const uint8_t* __restrict_
     uint64_t pos = 0;
     while (pos < len) {
         // the next key that opens an array we take: "mins" or "abundances"
-        const uint64_t m = find_first(t, pos, len, [&](uint64_t i) {
-            return t[i] == '"' && (starts_with(t, i, len, "\"mins\"", 6) || starts_with(t, i, len, "\"abundances\"", 12));
-        });
+        const uint64_t m = find_first(t, pos, len, [&](uint64_t i) { return sj_key_at(t, i, len); });
         if (m >= len) break;
-        const uint32_t kind = t[m + 1] == 'm' ? SJ_MINS : SJ_ABUND;
-        uint64_t q = m + (kind == SJ_MINS ? 6 : 12);
-        while (q < len && is_ws(t[q])) ++q;
-        if (q >= len || t[q] != ':') { pos = m + 1; continue; }
-        ++q;
-        while (q < len && is_ws(t[q])) ++q;
-        if (q >= len || t[q] != '[') { pos = m + 1; continue; }       // (abundances may be null)
-        const uint64_t s = q + 1;
+        const uint32_t kind = sj_key_kind(t, m);
+        const uint64_t s = sj_array_begin(t, m + sj_key_len(kind), len);
+        if (s > len) { pos = m + 1; continue; }
         // its end, its commas, and whether it holds anything but digits, commas and white space
         uint64_t e = len;
-        uint32_t commas = 0, odd = 0, digits = 0;
+        SjTally tally = {0, 0, 0};
         for (uint64_t p = s; p < len; p += 64) {
-            const uint64_t i = p + lane;
-            const uint32_t c = i < len ? t[i] : (uint32_t)']';
-            const uint64_t close = __builtin_amdgcn_ballot_w64(c == ']');
-            const uint64_t upto = close ? (1ull << __builtin_ctzll(close)) - 1ull : ~0ull;     // lanes in front of the first ']'
-            commas += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(c == ',') & upto);
-            digits |= (__builtin_amdgcn_ballot_w64(c >= '0' && c <= '9') & upto) != 0ull;
-            odd |= (__builtin_amdgcn_ballot_w64(!(c == ',' || (c >= '0' && c <= '9') || is_ws(c) || c == ']')) & upto) != 0ull;
+            const SjByteClass c = sj_class_at(t, p + lane, len);
+            const uint64_t close = __builtin_amdgcn_ballot_w64(c.close);
+            sj_tile_fold(close, __builtin_amdgcn_ballot_w64(c.comma), __builtin_amdgcn_ballot_w64(c.digit), __builtin_amdgcn_ballot_w64(c.odd), tally);
             if (close) { e = p + (uint64_t)__builtin_ctzll(close); break; }
         }
         if (e >= len) { flags |= SJ_DOC_ODD; break; }                 // no closing bracket
         if (n >= SJ_MAX_SPANS) { flags |= SJ_DOC_ODD; break; }
-        if (lane == 0) {
-            SjSpan sp;
-            sp.begin = s; sp.end = e;
-            sp.n_values = digits ? commas + 1u : 0u;
-            sp.kind = kind;
-            sp.flags = (odd ? SJ_SPAN_ODD : 0u) | (!digits && commas ? SJ_SPAN_ODD : 0u);
-            sp.pad = 0;
-            spans[(uint64_t)d * SJ_MAX_SPANS + n] = sp;
-        }
+        if (lane == 0) spans[(uint64_t)d * SJ_MAX_SPANS + n] = sj_span_record(s, e, kind, tally);
         ++n;
         pos = e + 1;
     }
@@ -102,11 +81,9 @@ __global__ __launch_bounds__(64) void sj_spans_kernel(const uint8_t* __restrict_
 // [64 l, 64 l + 64) of the chunk, counts its commas, a prefix sum gives every number its index, and the
 // lane parses the numbers that begin behind its commas -- they may run on into the next lane's bytes or the 64 bytes read
 // beyond the chunk.  Order and the down-sampling count are taken from the written values afterwards.
-constexpr uint32_t SJ_CHUNK = 4096, SJ_AHEAD = 64;
-
 __global__ __launch_bounds__(64) void sj_parse_kernel(const uint8_t* __restrict__ base, const SjParse* __restrict__ jobs, uint32_t n_jobs,
                                                       uint64_t* __restrict__ values, SjParsed* __restrict__ results, uint64_t keep_max) {
-    __shared__ uint4 buf4[(SJ_CHUNK + SJ_AHEAD + 16) / 16 + 1];
+    __shared__ uint4 buf4[SJ_BUF_LINES];
     uint8_t* buf = reinterpret_cast<uint8_t*>(buf4);
     const uint32_t j = blockIdx.x;
     if (j >= n_jobs) return;
@@ -120,53 +97,24 @@ __global__ __launch_bounds__(64) void sj_parse_kernel(const uint8_t* __restrict_
     for (uint64_t c0 = 0; c0 < len; c0 += SJ_CHUNK) {
         // bytes [c0, c0 + SJ_CHUNK + SJ_AHEAD) of the array -> buf[shift ...], from the 16-byte line they begin in
         const uintptr_t addr = reinterpret_cast<uintptr_t>(t + c0);
-        const uint32_t shift = (uint32_t)(addr & 15u);
-        const uint4* src = reinterpret_cast<const uint4*>(addr - shift);
-        const uint64_t avail = len - c0;                              // bytes of the array from c0 on
-        const uint32_t want = (uint32_t)(avail < SJ_CHUNK + SJ_AHEAD ? avail : SJ_CHUNK + SJ_AHEAD);
-        const uint32_t lines = (shift + want + 15u) / 16u;
+        const SjChunkGeom g = sj_chunk_geom(addr, c0, len);
+        const uint4* src = reinterpret_cast<const uint4*>(addr - g.shift);
         __syncthreads();
-        for (uint32_t l = lane; l < lines; l += 64u) buf4[l] = src[l];
+        for (uint32_t l = lane; l < g.lines; l += 64u) buf4[l] = src[l];
         __syncthreads();
-        const uint8_t* b = buf + shift;                               // b[i] = byte c0 + i of the array, i < want
-        const uint32_t in_chunk = (uint32_t)(avail < SJ_CHUNK ? avail : SJ_CHUNK);
-        const uint32_t p0 = lane * 64u, p1 = p0 + 64u < in_chunk ? p0 + 64u : in_chunk;
-        uint32_t commas = 0;
-        for (uint32_t i = p0; i < p1; ++i) commas += b[i] == ',';
+        const uint8_t* b = buf + g.shift;                             // b[i] = byte c0 + i of the array, i < want
+        const uint32_t commas = sj_lane_commas(b, sj_lane_begin(lane), sj_lane_end(lane, g.in_chunk));
         uint32_t incl = commas;
         for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(incl, o); if (lane >= (uint32_t)o) incl += u; }
         const uint32_t chunk_commas = __shfl(incl, 63);
-        uint64_t k = index + (incl - commas);                         // commas in front of this lane's bytes = index of the number open there
-        auto number = [&](uint32_t from, uint64_t idx) {              // the number that begins at b[from] (white space allowed around it)
-            uint32_t i = from;
-            while (i < want && is_ws(b[i])) ++i;
-            uint64_t v = 0;
-            uint32_t nd = 0;
-            while (i < want && b[i] >= '0' && b[i] <= '9') {
-                if (nd >= 19 && (v > 1844674407370955161ull || (v == 1844674407370955161ull && b[i] > '5'))) bad = 1;   // beyond 2^64 - 1
-                v = v * 10 + (uint64_t)(b[i] - '0');
-                ++nd;
-                ++i;
-            }
-            while (i < want && is_ws(b[i])) ++i;
-            if (nd == 0 || nd > 20) bad = 1;
-            if (i < want ? b[i] != ',' : c0 + i < len) bad = 1;       // ends at a comma, or at the end of the array (not at the end of what was read)
-            if (idx < job.n_values) out[idx] = v;
-        };
-        if (c0 == 0 && lane == 0 && job.n_values) number(0, 0);
-        for (uint32_t i = p0; i < p1; ++i)
-            if (b[i] == ',') { ++k; number(i + 1, k); }
-        index += chunk_commas;
+        const SjChunkIndex ix = sj_chunk_index(index, incl, commas, chunk_commas);
+        sj_parse_lane(b, g, lane, c0, len, ix.lane_first, job.n_values, out, bad);
+        index = ix.next;
     }
-    // order (ascending, no repeats: minhash.rs:161-171 would sort -- such an array is the host's) and the down-sampling count
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __syncthreads();
     uint32_t kept = 0;
-    for (uint64_t i = lane; i < job.n_values; i += 64u) {
-        const uint64_t v = out[i];
-        kept += v <= keep_max;
-        if (i + 1 < job.n_values && out[i + 1] <= v) bad = 1;
-    }
+    sj_order_lane(out, job.n_values, lane, keep_max, kept, bad);
     for (int o = 32; o; o >>= 1) { kept += __shfl_xor(kept, o); bad |= __shfl_xor(bad, o); }
     if (lane == 0) {
         SjParsed r;

@@ -135,6 +135,7 @@ inline void CollectionLoader::run_device(hipStream_t st, DeviceResult& out) {
         void* d_text = nullptr;
         gunzip_device(host.p, d_files.as<uint8_t>(), total, gm, &d_text, st, trace ? &gstats : nullptr);
         t_inflate = now() - t_g0 - t_read;
+        static_assert(GUNZIP_OUT_PAD >= SJ_TEXT_PAD, "the number parser loads whole 16-byte lines: up to 15 bytes past an array");
         struct FreeText { void*& p; hipStream_t st; ~FreeText() { if (p) arena_free(p, st); } } free_text{d_text, st};
         std::vector<SjDoc> docs;
         std::vector<size_t> doc_item;                                 // docs[d] is item i0 + doc_item[d]
@@ -155,36 +156,13 @@ inline void CollectionLoader::run_device(hipStream_t st, DeviceResult& out) {
         hip_check(hipStreamSynchronize(st), "sync");
         t_spans = now() - t_g0 - t_read - t_inflate;
         // ---- the numbers of every `mins` array; what lies outside the arrays, packed for the host ----
-        std::vector<SjParse> jobs;
-        std::vector<SjPiece> rest;                                    // pieces of text outside the arrays
-        struct DocPlan { size_t job0 = 0, rest0 = 0, rest1 = 0; uint64_t rest_off = 0; bool take = false; };
-        std::vector<DocPlan> plan(docs.size());
-        uint64_t n_values = 0, rest_bytes = 0;
-        for (size_t d = 0; d < docs.size(); ++d) {
-            const uint32_t ns = flags[d] & 0xffu;
-            bool odd = (flags[d] & SJ_DOC_ODD) != 0;
-            for (uint32_t s = 0; s < ns && !odd; ++s) odd = (spans[d * SJ_MAX_SPANS + s].flags & SJ_SPAN_ODD) != 0;
-            if (odd) { by_host[i0 + doc_item[d]] = 1; continue; }
-            DocPlan& pl = plan[d];
-            pl.take = true;
-            pl.job0 = jobs.size();
-            pl.rest0 = rest.size();
-            pl.rest_off = rest_bytes;
-            uint64_t at = 0;
-            for (uint32_t s = 0; s < ns; ++s) {
-                const SjSpan& sp = spans[d * SJ_MAX_SPANS + s];
-                rest.push_back(SjPiece{docs[d].off + at, rest_bytes, sp.begin - at});
-                rest_bytes += sp.begin - at;
-                at = sp.end;
-                if (sp.kind == SJ_MINS) {
-                    jobs.push_back(SjParse{docs[d].off + sp.begin, sp.end - sp.begin, n_values, sp.n_values});
-                    n_values += sp.n_values;
-                }
-            }
-            rest.push_back(SjPiece{docs[d].off + at, rest_bytes, docs[d].len - at});
-            rest_bytes += docs[d].len - at;
-            pl.rest1 = rest.size();
-        }
+        SjPlan planned;
+        sj_plan(docs, spans.data(), flags.data(), planned);
+        const std::vector<SjParse>& jobs = planned.jobs;
+        const std::vector<SjPiece>& rest = planned.rest;
+        const std::vector<SjDocPlan>& plan = planned.docs;
+        const uint64_t n_values = planned.n_values, rest_bytes = planned.rest_bytes;
+        for (size_t d = 0; d < docs.size(); ++d) if (!plan[d].take) by_host[i0 + doc_item[d]] = 1;
         if (jobs.size() > 0x7fffffffull || rest.size() > 0x7fffffffull) throw err_internal("collection group too large");
         value_blocks[g].reset(new AsyncBuf((size_t)n_values * 8 + 256, st));
         AsyncBuf d_jobs(jobs.size() * sizeof(SjParse) + 8, st), d_parsed(jobs.size() * sizeof(SjParsed) + 8, st);
@@ -206,7 +184,7 @@ inline void CollectionLoader::run_device(hipStream_t st, DeviceResult& out) {
         t_parse = now() - t_g0 - t_read - t_inflate - t_spans;
         // ---- the metadata, by the host's scanner on the remainder (every array replaced by its index) ----
         parallel(docs.size(), [&](size_t d) {
-            const DocPlan& pl = plan[d];
+            const SjDocPlan& pl = plan[d];
             if (!pl.take) return;
             const size_t item = i0 + doc_item[d];
             const uint32_t ns = flags[d] & 0xffu;

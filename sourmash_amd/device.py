@@ -79,6 +79,38 @@ def fastx_compact(raw, fastq, carry, out, result, record_starts=None, last_piece
              1 if last_piece else 0, _stream(torch))
 
 
+def sigjson_parse(text, text_len, docs, keep_max, values, spans=None, parsed_capacity=None):
+    """The signature JSON array parser by itself (smgpu_sigjson_parse_raw, csrc/sigjson.hip) on a block of JSON text held in HBM.
+
+    text: uint8 tensor holding text_len bytes of text and at least sigjson_text_pad() readable bytes behind them; docs: the
+    documents as (off, len) pairs; values: int64 tensor that takes the values of every parsed `mins` array side by side (u64 bit
+    patterns; what lies behind them is not touched); spans: a numpy array of len(docs) * 8 span records to fill in place (a new
+    one, zeroed, if None).  -> (spans, doc_flags uint32[len(docs)], parsed: n_jobs records {n_kept, flags}, n_values), all numpy
+    on the host.  The jobs are every `mins` array, in order, of every document with no odd bit and no odd array.  Synchronous."""
+    import numpy as np
+    torch = _torch()
+    span_t = np.dtype([("begin", "<u8"), ("end", "<u8"), ("n_values", "<u4"), ("kind", "<u4"), ("flags", "<u4"), ("pad", "<u4")])
+    parsed_t = np.dtype([("n_kept", "<u4"), ("flags", "<u4")])
+    assert text.dtype == torch.uint8 and values.dtype == torch.int64 and text.numel() >= int(text_len) + int(lib.smgpu_sigjson_text_pad())
+    d = np.ascontiguousarray(np.asarray(docs, dtype=np.uint64).reshape(-1, 2))
+    n = len(d)
+    if spans is None:
+        spans = np.zeros(n * 8, dtype=span_t)
+    assert spans.dtype == span_t and len(spans) >= n * 8 and spans.flags.c_contiguous
+    flags = np.zeros(n, dtype=np.uint32)
+    cap = n * 8 if parsed_capacity is None else int(parsed_capacity)
+    parsed = np.zeros(cap, dtype=parsed_t)
+    counts = np.zeros(2, dtype=np.uint64)
+    rustcall(lib.smgpu_sigjson_parse_raw, _ptr(text), int(text_len), d.ctypes.data, n, int(keep_max), spans.ctypes.data, flags.ctypes.data,
+             _ptr(values), values.numel(), parsed.ctypes.data, cap, counts.ctypes.data, _stream(torch))
+    return spans, flags, parsed[:int(counts[0])], int(counts[1])
+
+
+def sigjson_text_pad():
+    "readable bytes sigjson_parse needs behind the text (the parse kernel loads whole 16-byte lines)"
+    return int(lib.smgpu_sigjson_text_pad())
+
+
 def _records_error(code, message):
     "the exception of a failed per-record call: starts the library refuses are the caller's ValueError"
     if "record starts" in message:
