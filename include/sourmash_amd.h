@@ -553,6 +553,54 @@ SmgpuSketchSet *smgpu_sketchset_sketch_records(const uint8_t *d_seq, uint64_t le
 /* The records of a FASTA / FASTQ file (plain or gzip, at most 2 GiB of text) as such a set; the manifest rows carry each
  * record's name and the file name. */
 SmgpuSketchSet *smgpu_sketchset_sketch_file(const char *path, uint32_t ksize, uint64_t seed, uint64_t scaled);
+/* ---- a sketch's k-mers in sequences (csrc/sketch_find.hip; `sourmash sig kmers`, src/sourmash/sig/__main__.py:1087-1310) ----
+ * The way back from a sketch to the sequences it came from: every position of a buffer or a file whose k-mer hashes into a
+ * query, by record.  The query is the union of n compatible flat scaled DNA sketches, merged as the reference merges them
+ * (:1113-1135: the first one's copy_and_clear, abundances off, merge of each -- an incompatible sketch raises what
+ * kmerminhash_merge raises).  Refused with an error: no sketch, no hash, a num sketch, a protein / dayhoff / hp sketch.  The
+ * handle is made on the host; its hashes and their bucket directory go to the device when it is first used there. */
+typedef struct SmgpuKmerQuery SmgpuKmerQuery;
+typedef struct SmgpuKmerMatches SmgpuKmerMatches;
+SmgpuKmerQuery *smgpu_kmerquery_new(const SourmashKmerMinHash *const *mhs, uintptr_t n);
+void smgpu_kmerquery_free(SmgpuKmerQuery *ptr);
+uint64_t smgpu_kmerquery_len(const SmgpuKmerQuery *ptr);
+/* Scratch size of smgpu_find_kmers_raw for a capacity of matched (hash, position) pairs. */
+uint64_t smgpu_find_kmers_workspace_bytes(uint64_t pair_capacity, uint64_t n_records);
+/* d_seq[0,len) ASCII (any alignment), records as for smgpu_sketch_records_raw -> one row per position i whose k-mer
+ * d_seq[i, i + k) holds only ACGTacgt, lies inside one record and whose canonical hash is a member of the query; a k-mer that
+ * occurs at several positions, or on both strands, is a row at each.  Rows are ordered by position, so by record:
+ * d_positions (absolute in d_seq), d_hashes, d_kmers (NULL: not wanted; row * k bytes, the window as it stands, upper-cased);
+ * the rows of record r are [d_offsets[r], d_offsets[r + 1]).  The query's ksize must be 1 .. 88.  capacity: rows the three
+ * arrays hold and matched pairs the workspace holds; d_offsets: n_records + 1 entries.  d_result (device, 4 x u64): [0]
+ * matched pairs, [1] rows, [3] non-zero when the starts are refused.  Synchronises the stream three times: refused starts
+ * launch nothing behind the check, and the sort needs the matched count.  Returns the rows, or
+ * UINT64_MAX with an error set: starts not ascending or ending behind len; ksize above 88; or more pairs matched than
+ * capacity -- the error says so and names the count (also in d_result[0]), and the caller retries with a larger buffer. */
+uint64_t smgpu_find_kmers_raw(const SmgpuKmerQuery *query, const uint8_t *d_seq, uint64_t len, const uint64_t *d_starts,
+                              uint64_t n_records, uint64_t *d_positions, uint64_t *d_hashes, uint8_t *d_kmers,
+                              uint64_t capacity, uint64_t *d_offsets, uint64_t *d_result, void *d_workspace,
+                              uint64_t workspace_bytes, void *stream);
+/* Only its k-mer kernel (no assign, no sort): every matched hash appended unordered to d_hashes and the position of its
+ * k-mer's first byte in d_seq to d_positions; the count is added to *d_count (device u64, caller zeroes).  grid == 0 is the
+ * library's own number of workgroups, otherwise exactly `grid` (at most 1048576; for tests: many tiles per workgroup on a
+ * small input).  Asynchronous once the query is on the device. */
+void smgpu_find_kmers_kernel_raw(const SmgpuKmerQuery *query, const uint8_t *d_seq, uint64_t len, uint64_t *d_hashes,
+                                 uint64_t *d_positions, uint64_t capacity, uint64_t *d_count, uint32_t grid, void *stream);
+/* The records of a FASTA / FASTQ file (plain or gzip, at most 2 GiB of text; the files smgpu_sketchset_sketch_file takes)
+ * searched in one pass.  The accessors borrow from the handle: offsets (n_records + 1), positions (relative to the row's
+ * record), hashes, kmers (n_rows * ksize bytes); a record's name; the sequence of a record that has rows (NULL otherwise). */
+SmgpuKmerMatches *smgpu_find_kmers_file(const SmgpuKmerQuery *query, const char *path);
+void smgpu_kmermatches_free(SmgpuKmerMatches *ptr);
+uint64_t smgpu_kmermatches_n_records(const SmgpuKmerMatches *ptr);
+uint64_t smgpu_kmermatches_n_rows(const SmgpuKmerMatches *ptr);
+uint64_t smgpu_kmermatches_n_bases(const SmgpuKmerMatches *ptr);
+const uint64_t *smgpu_kmermatches_offsets(const SmgpuKmerMatches *ptr);
+const uint64_t *smgpu_kmermatches_positions(const SmgpuKmerMatches *ptr);
+const uint64_t *smgpu_kmermatches_hashes(const SmgpuKmerMatches *ptr);
+const uint8_t *smgpu_kmermatches_kmers(const SmgpuKmerMatches *ptr);
+const uint64_t *smgpu_kmermatches_record_lengths(const SmgpuKmerMatches *ptr);
+SourmashStr smgpu_kmermatches_record_name(const SmgpuKmerMatches *ptr, uint64_t record);
+const uint8_t *smgpu_kmermatches_record_sequence(const SmgpuKmerMatches *ptr, uint64_t record, uint64_t *len);
 /* rows[0..n) of a loaded set as a new set: row gather on the device, manifest rows follow.  Replaces the object loop of
  * Index.counter_gather (src/sourmash/index/__init__.py:302-320: `for result in self.prefetch(...): counter.add(
  * result.signature, ...)`): the rows that pass the prefetch become the counter's database without leaving HBM. */

@@ -15,6 +15,7 @@ from .signature import (SourmashSignature, FrozenSourmashSignature, load_signatu
                         load_one_signature_from_json, save_signatures_to_json)
 from .hll import HLL  # noqa: E402
 from .nodegraph import Nodegraph  # noqa: E402
+from .kmers import KmerQuery, KmerMatches, find_kmers  # noqa: E402
 
 DEFAULT_SEED = get_minhash_default_seed()
 MAX_HASH = get_minhash_max_hash()
@@ -26,5 +27,5 @@ def gpu_available():
 
 
 __all__ = ["MinHash", "FrozenMinHash", "HLL", "Nodegraph", "SourmashSignature", "FrozenSourmashSignature", "hash_murmur",
-           "load_signatures_from_json", "load_one_signature_from_json", "save_signatures_to_json",
+           "load_signatures_from_json", "load_one_signature_from_json", "save_signatures_to_json", "KmerQuery", "KmerMatches", "find_kmers",
            "gpu_available", "DEFAULT_SEED", "MAX_HASH", "VERSION"]

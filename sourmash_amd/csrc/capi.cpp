@@ -2190,6 +2190,239 @@ SourmashSignature** smgpu_sketch_file_singleton(const char* path, const Sourmash
     });
 }
 
+// ---- a sketch's k-mers in sequences (sketch_find.hip; `sourmash sig kmers`, src/sourmash/sig/__main__.py:1087-1310) ----------
+namespace {
+
+// The query: the merged sketch on the host; its hashes and their bucket directory (find_core.hpp) go to the device when a find
+// first needs them, on the library's stream, and stay there for the life of the handle.
+struct KmerQuery {
+    KmerMinHash mh;
+    std::mutex mu;
+    bool on_device = false;
+    DevBuf d_q, d_dir;
+    FindQuery dev{nullptr, nullptr, 0, 0};
+};
+
+const char* moltype_name(uint32_t hf) { return hf == HF_PROTEIN ? "protein" : hf == HF_DAYHOFF ? "dayhoff" : hf == HF_HP ? "hp" : "DNA"; }
+
+FindQuery query_on_device(const KmerQuery* cq) {
+    KmerQuery* q = const_cast<KmerQuery*>(cq);
+    DeviceCtx& ctx = DeviceCtx::get();
+    std::lock_guard<std::recursive_mutex> g(ctx.mutex());          // the context first, then the query: the file entry holds the context
+    std::lock_guard<std::mutex> own(q->mu);
+    if (q->on_device) return q->dev;
+    hipStream_t st = ctx.stream();
+    const uint64_t n = q->mh.mins.size();
+    if (n > FIND_MAX_QUERY) throw err_internal("query of more than 2^32 - 2 hashes");
+    const uint32_t shift = find_dir_shift(n, q->mh.max_hash);
+    const uint64_t nb = find_dir_buckets(q->mh.max_hash, shift);
+    q->d_q.reserve(n * 8 + 16, st);
+    q->d_dir.reserve((nb + 1) * 4 + 16, st);
+    hip_check(hipMemcpyAsync(q->d_q.p, q->mh.mins.data(), n * 8, hipMemcpyHostToDevice, st), "H2D");
+    hip_check(find_dir_launch(q->d_q.as<uint64_t>(), n, shift, nb, q->d_dir.as<uint32_t>(), st), "find_dir");
+    hip_check(hipStreamSynchronize(st), "sync");                    // any stream may use it from here on
+    q->dev = FindQuery{q->d_q.as<uint64_t>(), q->d_dir.as<uint32_t>(), q->mh.max_hash, shift};
+    q->on_device = true;
+    return q->dev;
+}
+
+inline size_t find_al256(size_t x) { return (x + 255) / 256 * 256; }
+
+// d_result: 4 x u64 -- [0] matched (hash, position) pairs, [1] rows, [2] unused, [3] what is wrong with the starts.
+// *exceeded (may be null): instead of raising, report the pairs matched when they outnumber `cap`.
+uint64_t find_kmers_run(const KmerQuery* q, const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, uint64_t n_records,
+                        uint64_t* d_positions, uint64_t* d_hashes, uint8_t* d_kmers, uint64_t cap, uint64_t* d_offsets, uint64_t* d_result,
+                        void* d_ws, uint64_t ws_bytes, hipStream_t st, uint64_t* exceeded) {
+    if (!q) throw err_internal("null query");
+    const uint32_t ksize = q->mh.ksize;
+    if (ksize < 1 || ksize > 88) throw err_internal("k-mer finding takes ksize 1 .. 88, not " + std::to_string(ksize));
+    if (!d_starts) throw err_internal("record starts: null (n_records + 1 ascending offsets are needed)");
+    if (n_records > 0xfffffffeull) throw err_internal("record starts: too many records");
+    if (cap > 0xffffffffull) throw err_internal("pair capacity above 2^32 - 1");
+    if (ws_bytes < smgpu_find_kmers_workspace_bytes(cap, n_records)) throw err_internal("workspace too small (smgpu_find_kmers_workspace_bytes)");
+    const FindQuery dev = query_on_device(q);
+    uint64_t* d_pair_hash = (uint64_t*)d_ws;
+    uint64_t* d_pair_pos = (uint64_t*)((char*)d_ws + find_al256(cap * 8));
+    void* d_tmp = (char*)d_ws + 2 * find_al256(cap * 8);
+    const size_t tmp_bytes = (size_t)(ws_bytes - 2 * find_al256(cap * 8));
+    hip_check(hipMemsetAsync(d_result, 0, 32, st), "memset");
+    hip_check(records_check_starts_launch(d_starts, n_records, len, (unsigned long long*)d_result + 3, st), "record starts");
+    unsigned long long head[4] = {0, 0, 0, 0};
+    hip_check(hipMemcpyAsync(head, d_result, 32, hipMemcpyDeviceToHost, st), "D2H");
+    hip_check(hipStreamSynchronize(st), "sync");
+    if (head[3] & 2) throw err_internal("record starts: the last offset lies behind the end of the buffer (" + std::to_string(len) + " bytes)");
+    if (head[3] & 1) throw err_internal("record starts: the offsets are not ascending");
+    hip_check(find_pairs_launch(d_seq, len, ksize, q->mh.seed, dev, d_pair_hash, d_pair_pos, (unsigned long long*)d_result, cap, 0, st), "find_kmers");
+    hip_check(hipMemcpyAsync(head, d_result, 8, hipMemcpyDeviceToHost, st), "D2H");
+    hip_check(hipStreamSynchronize(st), "sync");
+    if (head[0] > cap) {
+        if (exceeded) { *exceeded = head[0]; return ~0ull; }
+        throw err_internal("output capacity too small: " + std::to_string(head[0]) + " matched pairs > capacity " + std::to_string(cap));
+    }
+    hip_check(find_rows_launch(d_seq, len, d_pair_hash, d_pair_pos, head[0], d_starts, n_records, ksize, d_positions, d_hashes, d_kmers, d_offsets,
+                               d_result + 1, d_tmp, tmp_bytes, st), "find_rows");
+    unsigned long long n = 0;
+    hip_check(hipMemcpyAsync(&n, d_result + 1, 8, hipMemcpyDeviceToHost, st), "D2H");
+    hip_check(hipStreamSynchronize(st), "sync");
+    return n;
+}
+
+// what a file's search leaves on the host
+struct KmerMatches {
+    uint32_t ksize = 0;
+    uint64_t n_records = 0, n_rows = 0, n_bases = 0;
+    std::vector<uint64_t> offsets, positions, hashes, starts, lengths;
+    std::vector<uint8_t> kmers, seq;                                // seq: the parsed sequence bytes, kept only when there are rows
+    std::vector<std::string> names;
+};
+
+}  // namespace
+
+SmgpuKmerQuery* smgpu_kmerquery_new(const SourmashKmerMinHash* const* mhs, uintptr_t n) {
+    return landing<SmgpuKmerQuery*>([&]() -> SmgpuKmerQuery* {
+        if (!mhs || n == 0) throw Error(E_EMPTY_SIGNATURE, "no query signatures");
+        for (uintptr_t i = 0; i < n; ++i)
+            if (!mhs[i]) throw err_internal("null sketch");
+        const KmerMinHash& first = *MH(mhs[0]);
+        if (first.hash_function != HF_DNA)
+            throw Error(E_MISMATCH_DNA_PROT, std::string("k-mer finding takes DNA sketches, not ") + moltype_name(first.hash_function));
+        std::unique_ptr<KmerQuery> q(new KmerQuery());
+        q->mh = KmerMinHash(first.scaled(), first.ksize, first.hash_function, first.seed, false, first.num);   // copy_and_clear, flat
+        q->mh.max_hash = first.max_hash;
+        for (uintptr_t i = 0; i < n; ++i) {
+            const KmerMinHash& m = *MH(mhs[i]);
+            if (m.num != 0 || m.max_hash == 0) throw Error(E_MISMATCH_NUM, "k-mer finding takes scaled sketches, not num sketches");
+            q->mh.merge(m);
+        }
+        if (q->mh.mins.empty()) throw Error(E_EMPTY_SIGNATURE, "no hashes in query signature");
+        return reinterpret_cast<SmgpuKmerQuery*>(q.release());
+    });
+}
+
+void smgpu_kmerquery_free(SmgpuKmerQuery* p) {
+    KmerQuery* q = reinterpret_cast<KmerQuery*>(p);
+    if (!q) return;
+    if (q->on_device) {
+        if (DeviceCtx* ctx = DeviceCtx::peek()) {
+            std::lock_guard<std::recursive_mutex> g(ctx->mutex());
+            delete q;
+            return;
+        }
+    }
+    delete q;
+}
+
+uint64_t smgpu_kmerquery_len(const SmgpuKmerQuery* p) { return p ? reinterpret_cast<const KmerQuery*>(p)->mh.mins.size() : 0; }
+
+uint64_t smgpu_find_kmers_workspace_bytes(uint64_t pair_capacity, uint64_t n_records) {
+    (void)n_records;                                                // (the offsets are the caller's; the scratch depends on the pairs alone)
+    return 2 * find_al256(pair_capacity * 8) + find_rows_temp_bytes(pair_capacity) + 512;
+}
+
+uint64_t smgpu_find_kmers_raw(const SmgpuKmerQuery* query, const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, uint64_t n_records,
+                              uint64_t* d_positions, uint64_t* d_hashes, uint8_t* d_kmers, uint64_t capacity, uint64_t* d_offsets,
+                              uint64_t* d_result, void* d_workspace, uint64_t workspace_bytes, void* stream) {
+    uint64_t ret = ~0ull;
+    landing_void([&] {
+        ret = ~0ull;
+        ret = find_kmers_run(reinterpret_cast<const KmerQuery*>(query), d_seq, len, d_starts, n_records, d_positions, d_hashes, d_kmers, capacity,
+                             d_offsets, d_result, d_workspace, workspace_bytes, (hipStream_t)stream, nullptr);
+    });
+    return ret;
+}
+
+void smgpu_find_kmers_kernel_raw(const SmgpuKmerQuery* query, const uint8_t* d_seq, uint64_t len, uint64_t* d_hashes, uint64_t* d_positions,
+                                 uint64_t capacity, uint64_t* d_count, uint32_t grid, void* stream) {
+    landing_void([&] {
+        const KmerQuery* q = reinterpret_cast<const KmerQuery*>(query);
+        if (!q) throw err_internal("null query");
+        if (q->mh.ksize < 1 || q->mh.ksize > 88) throw err_internal("k-mer finding takes ksize 1 .. 88, not " + std::to_string(q->mh.ksize));
+        if (grid > (1u << 20)) throw err_internal("grid above 1048576 workgroups");
+        const FindQuery dev = query_on_device(q);
+        hip_check(find_pairs_launch(d_seq, len, q->mh.ksize, q->mh.seed, dev, d_hashes, d_positions, (unsigned long long*)d_count, capacity, grid,
+                                    (hipStream_t)stream), "find_kmers");
+    });
+}
+
+SmgpuKmerMatches* smgpu_find_kmers_file(const SmgpuKmerQuery* query, const char* path) {
+    return landing<SmgpuKmerMatches*>([&]() -> SmgpuKmerMatches* {
+        const KmerQuery* q = reinterpret_cast<const KmerQuery*>(query);
+        if (!q || !path) throw err_internal("null argument");
+        const uint32_t k = q->mh.ksize;
+        if (k < 1 || k > 88) throw err_internal("k-mer finding takes ksize 1 .. 88, not " + std::to_string(k));
+        DeviceCtx& ctx = DeviceCtx::get();
+        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+        hipStream_t st = ctx.stream();
+        ParsedRecords pr;
+        parse_records_file(path, pr, st);
+        std::unique_ptr<KmerMatches> m(new KmerMatches());
+        m->ksize = k;
+        m->n_records = pr.n_records;
+        m->names = std::move(pr.names);
+        m->offsets.assign(pr.n_records + 1, 0);
+        m->starts.assign(pr.n_records + 1, 0);
+        m->lengths.assign(pr.n_records, 0);
+        hip_check(hipMemcpyAsync(m->starts.data(), pr.starts.p, (pr.n_records + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
+        // pairs the buffer is expected to match: the sketch's share of its positions, never more than the query could place
+        AsyncBuf result(64, st), d_offsets((pr.n_records + 1) * 8 + 16, st);
+        uint64_t cap = records_pair_estimate(pr.len, q->mh.max_hash);
+        AsyncBuf d_pos, d_hash, d_kmers;
+        for (int attempt = 0;; ++attempt) {
+            d_pos.reset(cap * 8 + 16, st); d_hash.reset(cap * 8 + 16, st); d_kmers.reset(cap * k + 16, st);
+            const uint64_t ws_bytes = smgpu_find_kmers_workspace_bytes(cap, pr.n_records);
+            AsyncBuf ws((size_t)ws_bytes, st);
+            uint64_t exceeded = 0;
+            const uint64_t n = find_kmers_run(q, pr.comp.as<uint8_t>(), pr.len, pr.starts.as<uint64_t>(), pr.n_records, d_pos.as<uint64_t>(),
+                                              d_hash.as<uint64_t>(), d_kmers.as<uint8_t>(), cap, d_offsets.as<uint64_t>(), result.as<uint64_t>(),
+                                              ws.p, ws_bytes, st, attempt == 0 ? &exceeded : nullptr);
+            if (n != ~0ull) { m->n_rows = n; break; }
+            cap = exceeded;                                          // repetitive input beat the estimate: once more with the count
+        }
+        m->positions.resize(m->n_rows); m->hashes.resize(m->n_rows); m->kmers.resize(m->n_rows * k);
+        hip_check(hipMemcpyAsync(m->offsets.data(), d_offsets.p, (pr.n_records + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
+        if (m->n_rows) {
+            hip_check(hipMemcpyAsync(m->positions.data(), d_pos.p, m->n_rows * 8, hipMemcpyDeviceToHost, st), "D2H");
+            hip_check(hipMemcpyAsync(m->hashes.data(), d_hash.p, m->n_rows * 8, hipMemcpyDeviceToHost, st), "D2H");
+            hip_check(hipMemcpyAsync(m->kmers.data(), d_kmers.p, m->n_rows * k, hipMemcpyDeviceToHost, st), "D2H");
+            m->seq.resize(pr.len);
+            if (pr.len) hip_check(hipMemcpyAsync(m->seq.data(), pr.comp.p, pr.len, hipMemcpyDeviceToHost, st), "D2H");
+        }
+        hip_check(hipStreamSynchronize(st), "sync");
+        // a record's bytes end in front of the next record's separator byte (fastx.hip keeps one per header line)
+        for (uint64_t r = 0; r < pr.n_records; ++r) {
+            const uint64_t span = m->starts[r + 1] - m->starts[r];
+            m->lengths[r] = r + 1 < pr.n_records && span ? span - 1 : span;
+            m->n_bases += m->lengths[r];
+            for (uint64_t i = m->offsets[r]; i < m->offsets[r + 1]; ++i) m->positions[i] -= m->starts[r];
+        }
+        return reinterpret_cast<SmgpuKmerMatches*>(m.release());
+    });
+}
+
+void smgpu_kmermatches_free(SmgpuKmerMatches* p) { delete reinterpret_cast<KmerMatches*>(p); }
+uint64_t smgpu_kmermatches_n_records(const SmgpuKmerMatches* p) { return reinterpret_cast<const KmerMatches*>(p)->n_records; }
+uint64_t smgpu_kmermatches_n_rows(const SmgpuKmerMatches* p) { return reinterpret_cast<const KmerMatches*>(p)->n_rows; }
+uint64_t smgpu_kmermatches_n_bases(const SmgpuKmerMatches* p) { return reinterpret_cast<const KmerMatches*>(p)->n_bases; }
+const uint64_t* smgpu_kmermatches_offsets(const SmgpuKmerMatches* p) { return reinterpret_cast<const KmerMatches*>(p)->offsets.data(); }
+const uint64_t* smgpu_kmermatches_positions(const SmgpuKmerMatches* p) { return reinterpret_cast<const KmerMatches*>(p)->positions.data(); }
+const uint64_t* smgpu_kmermatches_hashes(const SmgpuKmerMatches* p) { return reinterpret_cast<const KmerMatches*>(p)->hashes.data(); }
+const uint8_t* smgpu_kmermatches_kmers(const SmgpuKmerMatches* p) { return reinterpret_cast<const KmerMatches*>(p)->kmers.data(); }
+const uint64_t* smgpu_kmermatches_record_lengths(const SmgpuKmerMatches* p) { return reinterpret_cast<const KmerMatches*>(p)->lengths.data(); }
+SourmashStr smgpu_kmermatches_record_name(const SmgpuKmerMatches* p, uint64_t record) {
+    return landing<SourmashStr>([&]() -> SourmashStr {
+        const KmerMatches* m = reinterpret_cast<const KmerMatches*>(p);
+        if (record >= m->n_records) throw err_internal("record " + std::to_string(record) + " of " + std::to_string(m->n_records));
+        return make_str(m->names[record]);
+    });
+}
+const uint8_t* smgpu_kmermatches_record_sequence(const SmgpuKmerMatches* p, uint64_t record, uint64_t* len) {
+    const KmerMatches* m = reinterpret_cast<const KmerMatches*>(p);
+    if (len) *len = 0;
+    if (record >= m->n_records || m->offsets[record] == m->offsets[record + 1] || m->seq.empty()) return nullptr;
+    if (len) *len = m->lengths[record];
+    return m->seq.data() + m->starts[record];
+}
+
 SmgpuCounter* smgpu_counter_new(const SmgpuSketchSet* set, const SourmashKmerMinHash* query) {
     return landing<SmgpuCounter*>([&]() -> SmgpuCounter* {
         const SketchSet* s = reinterpret_cast<const SketchSet*>(set);

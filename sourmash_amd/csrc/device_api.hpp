@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "find_core.hpp"
 
 namespace smg {
 
@@ -109,6 +110,23 @@ size_t records_csr_temp_bytes(uint64_t n_pairs);
 hipError_t records_csr_launch(uint64_t* d_pair_hash, uint64_t* d_pair_pos, uint64_t n_pairs, const uint64_t* d_starts, uint64_t n_records,
                               uint32_t k, uint64_t max_hash, uint64_t* d_hashes, uint64_t* d_abunds, uint64_t* d_offsets, uint64_t* d_n_out,
                               void* d_temp, size_t temp_bytes, hipStream_t stream);
+
+// ---- sketch_find.hip (a query sketch's k-mers in a buffer: rows of (position, hash), by record) ----------------------------------
+// d_dir[b] = first index of the sorted d_q[0,n) with d_q[i] >> shift >= b, for b = 0 .. n_buckets (find_core.hpp)
+hipError_t find_dir_launch(const uint64_t* d_q, uint64_t n, uint32_t shift, uint64_t n_buckets, uint32_t* d_dir, hipStream_t stream);
+// Every k-mer (1 <= k <= 88) of d_seq[0,len) whose canonical hash is a member of the query: the hash appended to d_hash, the
+// position of the k-mer's first byte to d_pos (unordered); *d_count += pairs (keeps counting past `cap`, pairs past cap are
+// dropped).  grid: 0, the launcher's own number of workgroups, or exactly that many.
+hipError_t find_pairs_launch(const uint8_t* d_seq, uint64_t len, uint32_t k, uint64_t seed, const FindQuery& query, uint64_t* d_hash,
+                             uint64_t* d_pos, unsigned long long* d_count, uint64_t cap, uint32_t grid, hipStream_t stream);
+size_t find_rows_temp_bytes(uint64_t n_pairs);
+// n_pairs matched (hash, position) pairs -> rows ordered by position, without the pairs whose k-mer lies in no record
+// (records_core.hpp: rec_assign): d_positions / d_hashes (room for n_pairs), d_kmers (may be null; n_pairs * k bytes) the k-mers'
+// upper-cased text, d_offsets[0 .. n_records] the first row of every record, *d_n_out = rows.  The pair arrays are clobbered.
+// Asynchronous: no size is read back.
+hipError_t find_rows_launch(const uint8_t* d_seq, uint64_t len, uint64_t* d_pair_hash, uint64_t* d_pair_pos, uint64_t n_pairs,
+                            const uint64_t* d_starts, uint64_t n_records, uint32_t k, uint64_t* d_positions, uint64_t* d_hashes,
+                            uint8_t* d_kmers, uint64_t* d_offsets, uint64_t* d_n_out, void* d_temp, size_t temp_bytes, hipStream_t stream);
 
 // ---- synth.hip --------------------------------------------------------------------
 hipError_t synth_dna_launch(uint8_t* d_out, uint64_t start, uint64_t n, uint64_t seed, uint64_t record_len,
