@@ -307,14 +307,17 @@ void smgpu_sigload_counters(uint64_t *out);
  * after the device refused them. */
 void smgpu_gunzip_counters(uint64_t *out);
 
-/* Scratch size needed by smgpu_sketch_dna_raw for an output capacity. */
+/* Scratch size needed by smgpu_sketch_dna_raw for an output capacity: the unordered kept hashes, and the larger of the two
+ * sorts' scratch (the uniform sort's regions, csrc/uniform_sort.hip; the general sort reuses them when it takes over). */
 uint64_t smgpu_sketch_workspace_bytes(uint64_t out_capacity);
 /* Device-resident sketching: d_seq[0,len) ASCII (any alignment) -> sorted unique
  * kept hashes (1 <= h <= max_hash; max_hash 0 = keep all) in d_out[0, n).
  * d_result (device, 2 x u64): [0] kept k-mer occurrences, [1] unique hashes n.
- * Synchronises the stream once (the sort needs the kept count).  Returns n, or
- * UINT64_MAX with an error set; if kept > out_capacity the error says so and the
- * caller retries with a larger buffer. */
+ * The kept count stays on the device: the sort for uniformly spread keys (csrc/uniform_sort.hip) reads it there, and the
+ * call synchronises the stream once, behind the sort.  Kept hashes that do not spread like hashes (one k-mer repeated, a
+ * short period) go through the general radix sort behind that, with a second synchronisation; the result is the same.
+ * Returns n, or UINT64_MAX with an error set; if kept > out_capacity the error says so, d_result[0] holds the count, and
+ * the caller retries with a larger buffer. */
 uint64_t smgpu_sketch_dna_raw(const uint8_t *d_seq, uint64_t len, uint32_t ksize, uint64_t seed, uint64_t max_hash,
                               uint64_t *d_out, uint64_t out_capacity, uint64_t *d_result, void *d_workspace,
                               uint64_t workspace_bytes, void *stream);
@@ -385,6 +388,19 @@ void smgpu_sketch_dna_kernel_grid_raw(const uint8_t *d_seq, uint64_t len, uint32
  * Synchronises the stream once.  Returns m, or UINT64_MAX with an error set. */
 uint64_t smgpu_sort_unique_raw(uint64_t *d_keys, uint64_t n, uint64_t *d_out, uint64_t *d_n_out, void *d_workspace,
                                uint64_t workspace_bytes, void *stream);
+/* The same for keys that are uniform on [0, thr] (hashes kept under a sketch's max_hash), with the number of keys on the device
+ * (csrc/uniform_sort.hip): d_keys[0, min(*d_n, n_max)) -> the sorted distinct values in d_out[0, m) (capacity n_max), their
+ * multiplicities in d_counts (NULL: not wanted); *d_result (device u64) = m.  Up to 16,384 keys one workgroup sorts whatever
+ * they are; above, keys that do not spread uniformly are noticed on the device and go through the general radix sort, with the
+ * same result.  The workspace is smgpu_sort_unique_uniform_workspace_bytes(n_max, counts wanted) bytes.  Synchronises the stream
+ * once (twice when the general sort takes over).  Returns m, or UINT64_MAX with an error set. */
+uint64_t smgpu_sort_unique_uniform_workspace_bytes(uint64_t n_max, int32_t counts);
+uint64_t smgpu_sort_unique_uniform_raw(uint64_t *d_keys, const uint64_t *d_n, uint64_t n_max, uint64_t thr, uint64_t *d_out,
+                                       uint64_t *d_counts, uint64_t *d_result, void *d_workspace, uint64_t workspace_bytes,
+                                       void *stream);
+/* out[0]: calls of smgpu_sketch_dna_raw / smgpu_sort_unique_uniform_raw since the library was loaded whose result the bucket
+ * form of the uniform sort gave, out[1]: its one-workgroup form, out[2]: calls that fell back to the general sort. */
+void smgpu_sort_counters(uint64_t *out);
 /* The kernels of protein / dayhoff / hp sketches on device-resident input (src/core/src/signature.rs:307-393,
  * src/core/src/encodings.rs:103-368): the residues of a protein sequence -- or, translate = true, the six-frame translation of
  * DNA -- go to d_aa (capacity aa_capacity bytes: the residue count rounded up to 8 -- the window kernel reads whole aligned

@@ -10,6 +10,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdio.h>
 #include <string.h>
+#include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <fstream>
@@ -28,6 +30,7 @@
 #include "ingest.hpp"
 #include "sigload.hpp"
 #include "murmur3.hpp"
+#include "uniform_sort_core.hpp"
 #include "residues.hpp"
 #include "signature_host.hpp"
 #include "hll_host.hpp"
@@ -863,8 +866,46 @@ uint64_t smgpu_minhash_add_file(SourmashKmerMinHash* p, const char* path, uint64
     });
 }
 
+// Workspace of a sketch call: [unordered kept hashes: cap u64][a report of three words and the fall-back flag: 256 bytes][the sort's
+// scratch: the uniform sort's regions (uniform_sort.hip), which the general sort reuses when it has to take over]
+static size_t sketch_ws_raw_bytes(uint64_t cap) { return (size_t)((cap * 8 + 255) / 256) * 256; }
+static size_t sketch_ws_sort_bytes(uint64_t cap, bool counts) {
+    return std::max(sort_unique_temp_bytes(cap), sort_unique_uniform_temp_bound(cap, counts));
+}
 uint64_t smgpu_sketch_workspace_bytes(uint64_t out_capacity) {
-    return (uint64_t)out_capacity * 8 + sort_unique_temp_bytes(out_capacity) + 512;
+    return (uint64_t)sketch_ws_raw_bytes(out_capacity) + 256 + sketch_ws_sort_bytes(out_capacity, false) + 512;
+}
+
+struct SortCounters { std::atomic<uint64_t> bucket{0}, small{0}, fellback{0}; };
+static SortCounters& sort_counters() { static SortCounters c; return c; }
+void smgpu_sort_counters(uint64_t* out) {
+    if (!out) return;
+    out[0] = sort_counters().bucket.load();
+    out[1] = sort_counters().small.load();
+    out[2] = sort_counters().fellback.load();
+}
+
+// The uniform sort on d_keys[0, min(*d_n, n_max)), then ONE copy to the host and ONE synchronisation: -> {*d_n, distinct, fell back}
+// as the device left them.  d_head: 256 bytes of workspace (report and flag).
+static void uniform_sort_and_report(const uint64_t* d_keys, const unsigned long long* d_n, uint64_t n_max, uint64_t thr, uint64_t* d_out,
+                                    uint64_t* d_counts, uint64_t* d_n_out, void* d_head, void* d_tmp, size_t tmp_bytes, hipStream_t st,
+                                    uint64_t report[3]) {
+    uint64_t* d_report = (uint64_t*)d_head;
+    uint32_t* d_flag = (uint32_t*)((char*)d_head + 64);
+    hip_check(sort_unique_uniform(d_keys, d_n, n_max, thr, d_out, d_counts, d_n_out, d_flag, d_tmp, tmp_bytes, st), "sort_unique_uniform");
+    hip_check(sort_report_launch(d_n, d_n_out, d_flag, d_report, st), "sort_report");
+    hip_check(hipMemcpyAsync(report, d_report, 24, hipMemcpyDeviceToHost, st), "D2H");
+    hip_check(hipStreamSynchronize(st), "sync");
+}
+static void count_sort_call(uint64_t n_max, uint64_t thr, size_t tmp_bytes, bool counts, bool fellback) {
+    if (fellback) ++sort_counters().fellback;
+    else if (sort_unique_uniform_form(n_max, thr, tmp_bytes, counts) == US_SMALL) ++sort_counters().small;
+    else ++sort_counters().bucket;
+}
+static int key_bits(uint64_t thr) {
+    int bits = 64;
+    if (thr != ~0ull) { bits = 1; while (bits < 64 && (thr >> bits)) ++bits; }
+    return bits;
 }
 
 uint64_t smgpu_sketch_dna_raw(const uint8_t* d_seq, uint64_t len, uint32_t ksize, uint64_t seed, uint64_t max_hash,
@@ -875,22 +916,54 @@ uint64_t smgpu_sketch_dna_raw(const uint8_t* d_seq, uint64_t len, uint32_t ksize
         hipStream_t st = (hipStream_t)stream;
         if (ws_bytes < smgpu_sketch_workspace_bytes(cap)) throw err_internal("workspace too small (smgpu_sketch_workspace_bytes)");
         uint64_t* d_raw = (uint64_t*)d_ws;                                   // unordered kept hashes
-        void* d_tmp = (char*)d_ws + ((cap * 8 + 255) / 256) * 256;
-        const size_t tmp_bytes = (size_t)(ws_bytes - ((cap * 8 + 255) / 256) * 256);
+        void* d_head = (char*)d_ws + sketch_ws_raw_bytes(cap);
+        void* d_tmp = (char*)d_head + 256;
+        const size_t tmp_bytes = (size_t)(ws_bytes - sketch_ws_raw_bytes(cap) - 256);
         const uint64_t thr = max_hash ? max_hash : ~0ull;
         check_dna_ksize(ksize);
         hip_check(hipMemsetAsync(d_result, 0, 16, st), "memset");
         hip_check(sketch_dna_launch(d_seq, len, ksize, seed, thr, d_raw, (unsigned long long*)d_result, cap, st), "sketch_dna");
-        unsigned long long kept = 0;
-        hip_check(hipMemcpyAsync(&kept, d_result, 8, hipMemcpyDeviceToHost, st), "D2H");
-        hip_check(hipStreamSynchronize(st), "sync");
+        // the kept count stays on the device: the sort reads it there, and the one synchronisation of the call is behind the sort
+        uint64_t report[3] = {0, 0, 0};
+        uniform_sort_and_report(d_raw, (const unsigned long long*)d_result, cap, thr, d_out, nullptr, d_result + 1, d_head, d_tmp, tmp_bytes,
+                                st, report);
+        const uint64_t kept = report[0];
         if (kept > cap)
             throw err_internal("output capacity too small: " + std::to_string(kept) + " kept hashes > capacity " + std::to_string(cap));
-        int bits = 64;
-        if (thr != ~0ull) { bits = 1; while (bits < 64 && (thr >> bits)) ++bits; }
-        hip_check(sort_unique(d_raw, kept, d_out, nullptr, d_result + 1, d_tmp, tmp_bytes, bits, st), "sort_unique");
+        count_sort_call(cap, thr, tmp_bytes, false, report[2] != 0);
+        if (report[2] == 0) { ret = report[1]; return; }
+        // the keys did not spread like hashes (one k-mer repeated, a short period): the general sort, on the kept hashes as they were
+        hip_check(sort_unique(d_raw, kept, d_out, nullptr, d_result + 1, d_tmp, tmp_bytes, key_bits(thr), st), "sort_unique");
         unsigned long long nu = 0;
         hip_check(hipMemcpyAsync(&nu, d_result + 1, 8, hipMemcpyDeviceToHost, st), "D2H");
+        hip_check(hipStreamSynchronize(st), "sync");
+        ret = nu;
+    });
+    return ret;
+}
+
+uint64_t smgpu_sort_unique_uniform_workspace_bytes(uint64_t n_max, int32_t counts) {
+    return 256 + (uint64_t)sketch_ws_sort_bytes(n_max, counts != 0) + 512;
+}
+
+uint64_t smgpu_sort_unique_uniform_raw(uint64_t* d_keys, const uint64_t* d_n, uint64_t n_max, uint64_t thr, uint64_t* d_out, uint64_t* d_counts,
+                                       uint64_t* d_result, void* d_ws, uint64_t ws_bytes, void* stream) {
+    uint64_t ret = ~0ull;
+    landing_void([&] {
+        hipStream_t st = (hipStream_t)stream;
+        if (!d_keys || !d_n || !d_out || !d_result || !d_ws) throw err_internal("null pointer");
+        if (ws_bytes < smgpu_sort_unique_uniform_workspace_bytes(n_max, d_counts != nullptr))
+            throw err_internal("workspace too small (smgpu_sort_unique_uniform_workspace_bytes)");
+        void* d_tmp = (char*)d_ws + 256;
+        const size_t tmp_bytes = (size_t)(ws_bytes - 256);
+        uint64_t report[3] = {0, 0, 0};
+        uniform_sort_and_report(d_keys, (const unsigned long long*)d_n, n_max, thr, d_out, d_counts, d_result, d_ws, d_tmp, tmp_bytes, st, report);
+        count_sort_call(n_max, thr, tmp_bytes, d_counts != nullptr, report[2] != 0);
+        if (report[2] == 0) { ret = report[1]; return; }
+        const uint64_t n = std::min(report[0], n_max);
+        hip_check(sort_unique(d_keys, n, d_out, d_counts, d_result, d_tmp, tmp_bytes, 64, st), "sort_unique");
+        unsigned long long nu = 0;
+        hip_check(hipMemcpyAsync(&nu, d_result, 8, hipMemcpyDeviceToHost, st), "D2H");
         hip_check(hipStreamSynchronize(st), "sync");
         ret = nu;
     });

@@ -87,6 +87,23 @@ hipError_t tag_gather_launch(const uint64_t* d_src, const TagSegment* d_segs, ui
 hipError_t sort_unique(uint64_t* d_keys, uint64_t n, uint64_t* d_out, uint64_t* d_counts, uint64_t* d_n_out,
                        void* d_temp, size_t temp_bytes, int bits, hipStream_t stream);
 
+// ---- uniform_sort.hip (uniform_sort_core.hpp: the plan and its rules) ---------------------------------------------------------------
+// The same result for keys that are uniform on [0, thr], without a size on the host: d_keys[0, min(*d_n, n_max)) -> sorted unique
+// in d_out[0, *d_n_out), multiplicities in d_counts (may be null).  Grids come from n_max; nothing synchronises; d_keys is not
+// modified.  *d_fellback = 0 when the result stands, 1 when the keys did not spread as planned (or the plan declines n_max / thr /
+// temp_bytes): then nothing else is valid and the caller runs sort_unique on the untouched d_keys.
+hipError_t sort_unique_uniform(const uint64_t* d_keys, const unsigned long long* d_n, uint64_t n_max, uint64_t thr, uint64_t* d_out,
+                               uint64_t* d_counts, uint64_t* d_n_out, uint32_t* d_fellback, void* d_temp, size_t temp_bytes,
+                               hipStream_t stream);
+// workspace of that call; and a bound of it over every thr
+size_t sort_unique_uniform_temp_bytes(uint64_t n_max, uint64_t thr, bool counts);
+size_t sort_unique_uniform_temp_bound(uint64_t n_max, bool counts);
+// the form the call takes (UsForm: 0 declines, 1 one workgroup, 2 / 3 one / two scatter passes)
+uint32_t sort_unique_uniform_form(uint64_t n_max, uint64_t thr, size_t temp_bytes, bool counts);
+// d_report[0 .. 3) = {*d_n, *d_n_out, *d_fellback}: what the host wants to know of such a call, in one place for one copy
+hipError_t sort_report_launch(const unsigned long long* d_n, const uint64_t* d_n_out, const uint32_t* d_fellback, uint64_t* d_report,
+                              hipStream_t stream);
+
 // (key, value) pairs sorted by the low `bits` bits of the key (stable), and runs of equal (a, b) pairs with their lengths
 size_t sort_pairs_temp_bytes(uint64_t n);
 hipError_t sort_pairs(const uint64_t* d_keys_in, uint64_t* d_keys_out, const uint64_t* d_vals_in, uint64_t* d_vals_out, uint64_t n,

@@ -231,6 +231,35 @@ def sort_unique(keys):
     return out[:m]
 
 
+def sort_unique_uniform(keys, max_hash, n=None, counts=False):
+    """The same for keys that are uniform on [0, max_hash] (max_hash 0: all 64 bits), e.g. kept hashes, through the sort that
+    uses it (smgpu_sort_unique_uniform_raw, csrc/uniform_sort.hip): the number of keys is read on the device -- `n` (default
+    len(keys)) is put there, and anything above len(keys) counts as len(keys).  `keys` is not modified unless the keys turn
+    out not to be uniform and the general sort takes over (sort_counters() tells).  -> the sorted distinct values, with
+    counts=True also their multiplicities; new tensors."""
+    torch = _torch()
+    assert keys.dtype == torch.int64 and keys.is_cuda and keys.is_contiguous()
+    n_max = keys.numel()
+    out = _u64(torch, max(n_max, 1), keys.device)
+    cnt = _u64(torch, max(n_max, 1), keys.device) if counts else None
+    d_n = torch.tensor([n_max if n is None else int(n)], dtype=torch.int64, device=keys.device)
+    result = torch.zeros(1, dtype=torch.int64, device=keys.device)
+    ws = torch.empty(int(lib.smgpu_sort_unique_uniform_workspace_bytes(n_max, int(counts))), dtype=torch.uint8, device=keys.device)
+    thr = int(max_hash) if max_hash else 0xFFFFFFFFFFFFFFFF
+    m = rustcall(lib.smgpu_sort_unique_uniform_raw, _ptr(keys) if n_max else _ptr(out), _ptr(d_n), n_max, thr, _ptr(out),
+                 _ptr(cnt) if counts else None, _ptr(result), _ptr(ws), ws.numel(), _stream(torch))
+    return (out[:m], cnt[:m]) if counts else out[:m]
+
+
+def sort_counters():
+    """{"bucket", "small", "fellback"}: sketch / sort_unique_uniform calls since the library was loaded that the uniform sort's
+    bucket form served, its one-workgroup form, and calls that fell back to the general sort (smgpu_sort_counters)."""
+    import ctypes
+    out = (ctypes.c_uint64 * 3)()
+    lib.smgpu_sort_counters(out)
+    return {"bucket": int(out[0]), "small": int(out[1]), "fellback": int(out[2])}
+
+
 def pack_csr(sketches, device="cuda"):
     "list of sorted u64 numpy arrays -> (hashes int64 tensor, offsets int64 tensor) on device."
     import numpy as np
