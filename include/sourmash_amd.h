@@ -621,6 +621,45 @@ const uint8_t *smgpu_kmermatches_record_sequence(const SmgpuKmerMatches *ptr, ui
  * Index.counter_gather (src/sourmash/index/__init__.py:302-320: `for result in self.prefetch(...): counter.add(
  * result.signature, ...)`): the rows that pass the prefetch become the counter's database without leaving HBM. */
 SmgpuSketchSet *smgpu_sketchset_subset(const SmgpuSketchSet *set, const uint64_t *rows, uintptr_t n);
+/* A set from a CSR in device memory (row r = d_hashes[d_offsets[r] .. d_offsets[r + 1]) ascending; n + 1 offsets): the rows are
+ * copied.  ksize in residues of the molecule; names / filenames: NULL or one C string per row for the manifest. */
+SmgpuSketchSet *smgpu_sketchset_from_csr(const uint64_t *d_hashes, const uint64_t *d_offsets, uint64_t n, uint32_t ksize,
+                                         uint32_t hash_function, uint64_t seed, uint64_t max_hash, uint64_t num,
+                                         const char *const *names, const char *const *filenames);
+/* names / filenames: NULL (left as they are) or one C string per row: the names the set's manifest rows carry and its signatures
+ * are written with (a set built from sketch handles has none until they are given). */
+void smgpu_sketchset_set_names(SmgpuSketchSet *set, const char *const *names, const char *const *filenames);
+/* The signature writer: a set's rows as signature JSON, MD5 identities and gzip members, produced on the device (csrc/sigwrite.hpp).
+ * md5sums: out[16 r .. 16 r + 16) = the MD5 of row r (the `md5sum` of its sketch).
+ * to_json: the JSON array of the rows' signatures (rows NULL: all n rows of the set), byte for byte what signatures_save_buffer gives
+ * for the same signatures at compression 0; above 0 the array as one gzip member.  Freed with nodegraph_buffer_free. */
+void smgpu_sketchset_md5sums(const SmgpuSketchSet *set, uint8_t *out);
+const uint8_t *smgpu_sketchset_to_json(const SmgpuSketchSet *set, const uint64_t *rows, uintptr_t n, uint8_t compression, uintptr_t *size);
+/* A file written from the device; the suffix of the path chooses the form: .zip (gzip members signatures/<md5>.sig.gz, stored, and
+ * SOURMASH-MANIFEST.csv last), .gz (the JSON array as one gzip member), anything else the JSON array.  Several sets may be added;
+ * names / filenames: NULL or one C string per row.  The file exists once close has returned without an error, and not otherwise. */
+typedef struct SmgpuSigWriter SmgpuSigWriter;
+SmgpuSigWriter *smgpu_sigwriter_new(const char *path, uint8_t compression);
+void smgpu_sigwriter_add(SmgpuSigWriter *writer, const SmgpuSketchSet *set, const char *const *names, const char *const *filenames);
+void smgpu_sigwriter_close(SmgpuSigWriter *writer);
+void smgpu_sigwriter_free(SmgpuSigWriter *writer);
+/* out[0 .. 7): ms in lengths, md5, text, crc, pack, device-to-host copies, file writes since the last reset; out[7 .. 12): rows,
+ * hashes, bytes of text, bytes written, rows whose MD5 the host computed. */
+void smgpu_sigwrite_stats(double *out, int32_t reset);
+/* The writer's kernels on caller-owned device buffers.  md5: 16 bytes a row into d_md5, rows whose message exceeds long_row_bound
+ * bytes on the host (0: the library's bound) -> rows the host did.  json: the rows' documents into d_text (per_doc: one `[{...}]` per
+ * row on 16-byte lines; else one array), params = ksize, hash_function, seed, max_hash, num, docs_out = offset, length per row
+ * -> bytes of text.  deflate: every document (offset, length; offsets multiples of 16, d_text itself 16-byte aligned) of d_text as a gzip member in d_out,
+ * compression 0 stored blocks, else literal-only Huffman blocks packed `chunk` bytes a workgroup (0: the default) -> bytes of output.
+ * json and deflate write nothing when the result exceeds the capacity. */
+uint64_t smgpu_sigwrite_md5_raw(const uint64_t *d_hashes, const uint64_t *d_offsets, uint64_t n_rows, uint32_t ksize, uint64_t long_row_bound,
+                                uint8_t *d_md5, void *stream);
+uint64_t smgpu_sigwrite_json_raw(const uint64_t *d_hashes, const uint64_t *d_offsets, uint64_t n_rows, const uint64_t *params,
+                                 const char *const *names, const char *const *filenames, int32_t per_doc, uint8_t *d_text, uint64_t capacity,
+                                 uint64_t *docs_out, void *stream);
+uint64_t smgpu_deflate_literals_raw(const uint8_t *d_text, uint64_t text_len, const uint64_t *docs, uint32_t n_docs, uint8_t compression,
+                                    uint32_t chunk, uint8_t *d_out, uint64_t capacity, uint64_t *members_out, void *stream);
+
 uint64_t smgpu_sketchset_total_hashes(const SmgpuSketchSet *ptr);
 uint64_t smgpu_sketchset_skipped(const SmgpuSketchSet *ptr);
 /* One manifest row per CSR row, in the reference's CSV manifest format (manifest.py:29-41,128-146). */

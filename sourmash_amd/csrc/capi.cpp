@@ -29,6 +29,7 @@
 #include "pargz.hpp"
 #include "ingest.hpp"
 #include "sigload.hpp"
+#include "sigwrite.hpp"
 #include "murmur3.hpp"
 #include "uniform_sort_core.hpp"
 #include "residues.hpp"
@@ -1699,6 +1700,18 @@ SmgpuSketchSet* smgpu_sketchset_new(const SourmashKmerMinHash* const* mhs, uintp
         std::vector<uint64_t> off(n + 1, 0);
         for (uintptr_t i = 0; i < n; ++i) off[i + 1] = off[i] + MH(mhs[i])->size();
         s->n = n; s->total = off[n];
+        {   // the sketches' shared parameters, if they share them (what a writer needs to know; ksize stays 0 otherwise)
+            bool same = n > 0 && !MH(mhs[0])->track_abundance;      // (a set is flat: a set of abundance sketches is not for the writer)
+            for (uintptr_t i = 1; i < n && same; ++i) {
+                const KmerMinHash *a = MH(mhs[0]), *b = MH(mhs[i]);
+                same = !b->track_abundance && a->ksize == b->ksize && a->hash_function == b->hash_function && a->seed == b->seed && a->max_hash == b->max_hash && a->num == b->num;
+            }
+            if (same) {
+                const KmerMinHash* a = MH(mhs[0]);
+                s->hash_function = a->hash_function; s->ksize = a->ksize / (a->hash_function == HF_DNA ? 1u : 3u);
+                s->seed = a->seed; s->max_hash = a->max_hash; s->num = a->num;
+            }
+        }
         hipStream_t st = ctx.stream();
         s->hashes.reserve(s->total * 8 + 16, st);
         s->offsets.reserve((n + 1) * 8, st);
@@ -2219,6 +2232,348 @@ SmgpuSketchSet* smgpu_sketchset_sketch_file(const char* path, uint32_t ksize, ui
         for (uint64_t r = 0; r < pr.n_records; ++r) { s->rows[r].name = pr.names[r]; s->rows[r].filename = path; }
         return reinterpret_cast<SmgpuSketchSet*>(s.release());
     });
+}
+
+// ---- signature writer (sigwrite.hpp): a set's rows as .sig / .sig.gz / .zip, written from the device ---------------------------
+namespace {
+
+// a set as the writer's source; `off`: room for the offsets of a set that keeps none on the host
+void sw_source_of(const SketchSet* s, std::vector<uint64_t>& off, hipStream_t st, SwSource& src) {
+    src.d_hashes = s->hashes.as<uint64_t>();
+    src.d_offsets = s->offsets.as<uint64_t>();
+    if (s->host_offsets.size() == s->n + 1) src.h_offsets = s->host_offsets.data();
+    else {
+        off.assign(s->n + 1, 0);
+        hip_check(hipMemcpyAsync(off.data(), s->offsets.p, (s->n + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
+        hip_check(hipStreamSynchronize(st), "sync");
+        src.h_offsets = off.data();
+    }
+    src.n = s->n;
+    src.ksize = s->ksize; src.hash_function = s->hash_function; src.seed = s->seed; src.max_hash = s->max_hash; src.num = s->num;
+    src.rows = &s->rows;
+}
+
+// every row's message length, for the MD5 hand-out
+void sw_message_lengths(const SwSource& src, hipStream_t st, std::vector<uint64_t>& msg_len) {
+    msg_len.assign(src.n, 0);
+    if (src.n == 0) return;
+    const uint64_t h0 = src.h_offsets[0], nh = src.h_offsets[src.n] - h0;
+    const size_t tmp_bytes = sw_positions_temp_bytes(nh);
+    AsyncBuf d_pos((nh + 2) * 8, st), d_tmp(tmp_bytes, st), d_text_len(src.n * 8, st), d_msg_len(src.n * 8, st);
+    hip_check(sw_positions_launch(src.d_hashes, h0, nh, d_pos.as<uint64_t>(), d_tmp.p, tmp_bytes, st), "sw_positions");
+    hip_check(sw_row_lengths_launch(src.d_offsets, src.n, d_pos.as<uint64_t>(), sw_digit_count(src.json_ksize()), d_text_len.as<uint64_t>(),
+                                    d_msg_len.as<uint64_t>(), st), "sw_row_lengths");
+    hip_check(hipMemcpyAsync(msg_len.data(), d_msg_len.p, src.n * 8, hipMemcpyDeviceToHost, st), "D2H");
+    hip_check(hipStreamSynchronize(st), "sync");
+}
+
+struct SigWriterHandle {
+    std::unique_ptr<SigWriter> w;
+};
+
+}  // namespace
+
+// A set from a CSR the caller holds in HBM (torch tensors): n flat sketches of shared parameters, row r = d_hashes[d_offsets[r] ..
+// d_offsets[r + 1]) ascending.  The rows are copied (device to device) on the library's stream; names / filenames: NULL or one C
+// string per row for the manifest.  ksize: in residues of the molecule (amino acids for protein sketches).
+SmgpuSketchSet* smgpu_sketchset_from_csr(const uint64_t* d_hashes, const uint64_t* d_offsets, uint64_t n, uint32_t ksize, uint32_t hash_function,
+                                         uint64_t seed, uint64_t max_hash, uint64_t num, const char* const* names, const char* const* filenames) {
+    return landing<SmgpuSketchSet*>([&]() -> SmgpuSketchSet* {
+        if (!d_offsets || ksize == 0) throw err_internal("smgpu_sketchset_from_csr: offsets and a ksize are needed");
+        if (hash_function < HF_DNA || hash_function > HF_HP) throw err_internal("smgpu_sketchset_from_csr: unknown hash function");
+        DeviceCtx& ctx = DeviceCtx::get();
+        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+        hipStream_t st = ctx.stream();
+        std::unique_ptr<SketchSet> s(new SketchSet());
+        s->host_offsets.assign(n + 1, 0);
+        hip_check(hipMemcpyAsync(s->host_offsets.data(), d_offsets, (n + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
+        hip_check(hipStreamSynchronize(st), "sync");
+        const uint64_t base = s->host_offsets[0];
+        for (uint64_t r = 0; r < n; ++r)
+            if (s->host_offsets[r + 1] < s->host_offsets[r]) throw err_internal("smgpu_sketchset_from_csr: offsets must ascend");
+        for (uint64_t r = 0; r <= n; ++r) s->host_offsets[r] -= base;
+        s->n = n; s->total = s->host_offsets[n];
+        if (s->total && !d_hashes) throw err_internal("smgpu_sketchset_from_csr: null pointer");
+        s->ksize = ksize; s->hash_function = hash_function; s->seed = seed; s->max_hash = max_hash; s->num = num;
+        s->hashes.reserve(s->total * 8 + 16, st);
+        s->offsets.reserve((n + 1) * 8, st);
+        if (s->total) hip_check(hipMemcpyAsync(s->hashes.p, d_hashes + base, s->total * 8, hipMemcpyDeviceToDevice, st), "D2D");
+        hip_check(hipMemcpyAsync(s->offsets.p, s->host_offsets.data(), (n + 1) * 8, hipMemcpyHostToDevice, st), "H2D");
+        hip_check(hipStreamSynchronize(st), "sync");
+        s->rows.resize(n);
+        for (uint64_t r = 0; r < n; ++r) {
+            ManifestRow& m = s->rows[r];
+            m.ksize = ksize; m.moltype = molecule_name(hash_function); m.num = num;
+            m.scaled = max_hash ? scaled_for_max_hash(max_hash) : 0;
+            m.n_hashes = s->host_offsets[r + 1] - s->host_offsets[r];
+            if (names && names[r]) m.name = names[r];
+            if (filenames && filenames[r]) m.filename = filenames[r];
+        }
+        return reinterpret_cast<SmgpuSketchSet*>(s.release());
+    });
+}
+
+// the names and file names of the set's rows (its manifest rows; made here for a set that has none)
+void smgpu_sketchset_set_names(SmgpuSketchSet* p, const char* const* names, const char* const* filenames) {
+    landing_void([&] {
+        SketchSet* s = reinterpret_cast<SketchSet*>(p);
+        if (!s) throw err_internal("null pointer");
+        if (s->rows.size() != s->n) {
+            std::vector<uint64_t> off = s->host_offsets;
+            if (off.size() != s->n + 1) {
+                off.assign(s->n + 1, 0);
+                DeviceCtx& ctx = DeviceCtx::get();
+                std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+                hip_check(hipMemcpyAsync(off.data(), s->offsets.p, (s->n + 1) * 8, hipMemcpyDeviceToHost, ctx.stream()), "D2H");
+                hip_check(hipStreamSynchronize(ctx.stream()), "sync");
+            }
+            s->rows.assign(s->n, ManifestRow());
+            for (uint64_t r = 0; r < s->n; ++r) {
+                ManifestRow& m = s->rows[r];
+                m.ksize = s->ksize; m.moltype = molecule_name(s->hash_function); m.num = s->num;
+                m.scaled = s->max_hash ? scaled_for_max_hash(s->max_hash) : 0;
+                m.n_hashes = off[r + 1] - off[r];
+            }
+        }
+        for (uint64_t r = 0; r < s->n; ++r) {
+            if (names) s->rows[r].name = names[r] ? names[r] : "";
+            if (filenames) s->rows[r].filename = filenames[r] ? filenames[r] : "";
+        }
+    });
+}
+
+// out[16 r .. 16 r + 16): the MD5 of row r (minhash.rs:290-307), computed on the device
+void smgpu_sketchset_md5sums(const SmgpuSketchSet* p, uint8_t* out) {
+    landing_void([&] {
+        const SketchSet* s = reinterpret_cast<const SketchSet*>(p);
+        if (s->n == 0) return;
+        if (s->ksize == 0) throw err_internal("the set's sketches do not share one set of parameters");
+        DeviceCtx& ctx = DeviceCtx::get();
+        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+        hipStream_t st = ctx.stream();
+        std::vector<uint64_t> off;
+        SwSource src;
+        sw_source_of(s, off, st, src);
+        // in runs of rows like the writer's batches (the scan's positions take 8 bytes a hash)
+        const std::vector<uint64_t> cut = sw_batches(src);
+        for (size_t b = 0; b + 1 < cut.size(); ++b) {
+            const uint64_t r0 = cut[b], n = cut[b + 1] - r0;
+            if (n == 0) continue;
+            SwSource part = src;
+            part.d_offsets += r0; part.h_offsets += r0; part.n = n;
+            std::vector<uint64_t> msg_len;
+            sw_message_lengths(part, st, msg_len);
+            AsyncBuf d_md5(n * 16, st);
+            sigwrite_stats().md5_host_rows += sw_md5_rows(part.d_hashes, part.d_offsets, part.h_offsets, n, src.json_ksize(), msg_len, SW_MD5_HOST_BOUND,
+                                                          d_md5.as<uint8_t>(), st);
+            hip_check(hipMemcpyAsync(out + 16 * r0, d_md5.p, n * 16, hipMemcpyDeviceToHost, st), "D2H");
+            hip_check(hipStreamSynchronize(st), "sync");
+        }
+    });
+}
+
+// The JSON array of the set's signatures (rows: these rows in this order; NULL: all n rows of the set), the bytes
+// signatures_save_buffer gives for the same signatures at compression 0; above 0 the array as one gzip member.
+// Freed with nodegraph_buffer_free.
+const uint8_t* smgpu_sketchset_to_json(const SmgpuSketchSet* p, const uint64_t* rows, uintptr_t n, uint8_t compression, uintptr_t* size) {
+    return landing<const uint8_t*>([&]() -> const uint8_t* {
+        const SketchSet* s = reinterpret_cast<const SketchSet*>(p);
+        if (!size) throw err_internal("null pointer");
+        if (s->n && s->ksize == 0) throw err_internal("the set's sketches do not share one set of parameters, or track abundance: it cannot be written");
+        DeviceCtx& ctx = DeviceCtx::get();
+        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+        hipStream_t st = ctx.stream();
+        std::vector<uint64_t> off;
+        SwSource src;
+        sw_source_of(s, off, st, src);
+        // a selection: its rows gathered into a CSR of their own (device to device), their names beside them
+        DevBuf sub_hashes, sub_offsets;
+        std::vector<uint64_t> sub_off;
+        std::vector<std::string> names, filenames;
+        std::vector<const char*> name_ptrs, filename_ptrs;
+        if (rows) {
+            sub_off.assign(n + 1, 0);
+            for (uintptr_t i = 0; i < n; ++i) {
+                if (rows[i] >= s->n) throw err_internal("sketch index out of range");
+                sub_off[i + 1] = sub_off[i] + (src.h_offsets[rows[i] + 1] - src.h_offsets[rows[i]]);
+                names.push_back(src.name(rows[i]));
+                filenames.push_back(src.filename(rows[i]));
+            }
+            for (uintptr_t i = 0; i < n; ++i) { name_ptrs.push_back(names[i].c_str()); filename_ptrs.push_back(filenames[i].c_str()); }
+            sub_hashes.reserve((sub_off[n] + 1) * 8, st);
+            sub_offsets.reserve((n + 1) * 8, st);
+            DevBuf d_rows;
+            d_rows.reserve((n + 1) * 8, st);
+            hip_check(hipMemcpyAsync(sub_offsets.p, sub_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, st), "H2D");
+            if (n) hip_check(hipMemcpyAsync(d_rows.p, rows, n * 8, hipMemcpyHostToDevice, st), "H2D");
+            hip_check(copy_rows_launch(src.d_hashes, src.d_offsets, d_rows.as<uint64_t>(), n, sub_offsets.as<uint64_t>(), sub_hashes.as<uint64_t>(), st),
+                      "copy_rows");
+            hip_check(hipStreamSynchronize(st), "sync");
+            src.d_hashes = sub_hashes.as<uint64_t>(); src.d_offsets = sub_offsets.as<uint64_t>(); src.h_offsets = sub_off.data();
+            src.n = n; src.rows = nullptr;
+            src.names = name_ptrs.data(); src.filenames = filename_ptrs.data();
+        }
+        std::string bytes;
+        auto sink = [&](const void* q, size_t k) { bytes.append(static_cast<const char*>(q), k); };
+        SwGzStream gz;
+        gz.compression = compression;
+        bool any_rows = false;
+        sw_array_add(src, compression ? &gz : nullptr, any_rows, sink, st);
+        sw_array_close(compression ? &gz : nullptr, any_rows, sink, st);
+        *size = bytes.size();
+        uint8_t* out = (uint8_t*)malloc(bytes.size() ? bytes.size() : 1);
+        if (!out) throw err_internal("out of memory");
+        memcpy(out, bytes.data(), bytes.size());
+        return out;
+    });
+}
+
+// A signature file written from the device.  The path's suffix chooses the form as the reference does (save_load.py:543-549):
+// .zip -- an uncompressed zip of gzip members signatures/<md5>.sig.gz with SOURMASH-MANIFEST.csv last; .gz -- the JSON array as
+// one gzip member; anything else -- the JSON array.  compression 0: stored blocks.  The file appears under its name when
+// smgpu_sigwriter_close returns without an error, and not at all otherwise.
+SmgpuSigWriter* smgpu_sigwriter_new(const char* path, uint8_t compression) {
+    return landing<SmgpuSigWriter*>([&]() -> SmgpuSigWriter* {
+        if (!path) throw err_internal("null path");
+        std::unique_ptr<SigWriterHandle> h(new SigWriterHandle());
+        h->w.reset(new SigWriter(path, compression));
+        return reinterpret_cast<SmgpuSigWriter*>(h.release());
+    });
+}
+// names / filenames: NULL, or one C string per row of the set (in place of the set's manifest rows)
+void smgpu_sigwriter_add(SmgpuSigWriter* w, const SmgpuSketchSet* p, const char* const* names, const char* const* filenames) {
+    landing_void([&] {
+        SigWriterHandle* h = reinterpret_cast<SigWriterHandle*>(w);
+        const SketchSet* s = reinterpret_cast<const SketchSet*>(p);
+        if (!h || !h->w || !s) throw err_internal("null pointer");
+        DeviceCtx& ctx = DeviceCtx::get();
+        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+        hipStream_t st = ctx.stream();
+        std::vector<uint64_t> off;
+        SwSource src;
+        sw_source_of(s, off, st, src);
+        src.names = names; src.filenames = filenames;
+        h->w->add(src, st);
+    });
+}
+void smgpu_sigwriter_close(SmgpuSigWriter* w) {
+    landing_void([&] {
+        SigWriterHandle* h = reinterpret_cast<SigWriterHandle*>(w);
+        if (!h || !h->w) throw err_internal("null pointer");
+        DeviceCtx& ctx = DeviceCtx::get();
+        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+        h->w->close(ctx.stream());
+    });
+}
+void smgpu_sigwriter_free(SmgpuSigWriter* w) { delete reinterpret_cast<SigWriterHandle*>(w); }
+
+// out[0 .. 7): milliseconds spent in lengths, md5, text, crc, pack, device-to-host copies and file writes since the last reset;
+// out[7 .. 12): rows, hashes, bytes of text, bytes written, rows whose MD5 the host computed.  reset != 0: zeroed afterwards.
+void smgpu_sigwrite_stats(double* out, int32_t reset) {
+    DeviceCtx* ctx = DeviceCtx::peek();                             // (no context: nothing has been written, nobody else is counting)
+    std::unique_lock<std::recursive_mutex> g;
+    if (ctx) g = std::unique_lock<std::recursive_mutex>(ctx->mutex());
+    SwStats& s = sigwrite_stats();
+    if (out) {
+        const double v[12] = {s.lengths_ms, s.md5_ms, s.text_ms, s.crc_ms, s.pack_ms, s.d2h_ms, s.write_ms,
+                              (double)s.rows, (double)s.hashes, (double)s.text_bytes, (double)s.out_bytes, (double)s.md5_host_rows};
+        memcpy(out, v, sizeof v);
+    }
+    if (reset) s = SwStats();
+}
+
+// The kernels on caller-owned device buffers (torch tensors).  d_offsets: n_rows + 1 positions in d_hashes.
+// MD5 of every row into d_md5 (16 bytes a row); rows whose message is longer than long_row_bound bytes are hashed by the host
+// (0: the library's bound).  -> rows the host did.
+uint64_t smgpu_sigwrite_md5_raw(const uint64_t* d_hashes, const uint64_t* d_offsets, uint64_t n_rows, uint32_t ksize, uint64_t long_row_bound,
+                                uint8_t* d_md5, void* stream) {
+    uint64_t ret = ~0ull;
+    landing_void([&] {
+        if (n_rows == 0) { ret = 0; return; }
+        if (!d_offsets || !d_md5) throw err_internal("smgpu_sigwrite_md5_raw: null pointer");
+        DeviceCtx& ctx = DeviceCtx::get();                          // (the pinned ring, the writer's tables and counters are the context's)
+        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+        hipStream_t st = (hipStream_t)stream;
+        std::vector<uint64_t> off(n_rows + 1);
+        hip_check(hipMemcpyAsync(off.data(), d_offsets, (n_rows + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
+        hip_check(hipStreamSynchronize(st), "sync");
+        for (uint64_t r = 0; r < n_rows; ++r) if (off[r + 1] < off[r]) throw err_internal("smgpu_sigwrite_md5_raw: offsets must ascend");
+        SwSource src;
+        src.d_hashes = d_hashes; src.d_offsets = d_offsets; src.h_offsets = off.data(); src.n = n_rows; src.ksize = ksize;
+        std::vector<uint64_t> msg_len;
+        sw_message_lengths(src, st, msg_len);
+        ret = sw_md5_rows(d_hashes, d_offsets, off.data(), n_rows, ksize, msg_len, long_row_bound ? long_row_bound : SW_MD5_HOST_BOUND, d_md5, st);
+    });
+    return ret;
+}
+
+// The documents of the rows into d_text (capacity bytes): per_doc != 0 one `[{...}]` per row, each on a 16-byte line; otherwise
+// one array of all rows.  params: ksize (as the JSON says it), hash_function, seed, max_hash, num.  names / filenames: NULL or one
+// C string per row.  docs_out: offset and length of every row's document (2 n_rows values).  -> bytes of text (nothing is written
+// when they exceed the capacity).
+uint64_t smgpu_sigwrite_json_raw(const uint64_t* d_hashes, const uint64_t* d_offsets, uint64_t n_rows, const uint64_t* params, const char* const* names,
+                                 const char* const* filenames, int32_t per_doc, uint8_t* d_text, uint64_t capacity, uint64_t* docs_out, void* stream) {
+    uint64_t ret = ~0ull;
+    landing_void([&] {
+        if (!params || (n_rows && (!d_offsets || !docs_out))) throw err_internal("smgpu_sigwrite_json_raw: null pointer");
+        DeviceCtx& ctx = DeviceCtx::get();                          // (the pinned ring, the writer's tables and counters are the context's)
+        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+        hipStream_t st = (hipStream_t)stream;
+        std::vector<uint64_t> off(n_rows + 1, 0);
+        if (n_rows) hip_check(hipMemcpyAsync(off.data(), d_offsets, (n_rows + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
+        hip_check(hipStreamSynchronize(st), "sync");
+        for (uint64_t r = 0; r < n_rows; ++r) if (off[r + 1] < off[r]) throw err_internal("smgpu_sigwrite_json_raw: offsets must ascend");
+        SwSource src;
+        src.d_hashes = d_hashes; src.d_offsets = d_offsets; src.h_offsets = off.data(); src.n = n_rows;
+        src.hash_function = (uint32_t)params[1];
+        src.ksize = (uint32_t)params[0] / (src.hash_function == HF_DNA ? 1u : 3u);
+        src.seed = params[2]; src.max_hash = params[3]; src.num = params[4];
+        src.names = names; src.filenames = filenames;
+        SwBatch batch;
+        sw_build_batch(src, 0, n_rows, per_doc != 0, true, true, SW_MD5_HOST_BOUND, batch, st);
+        for (uint64_t r = 0; r < n_rows; ++r) { docs_out[2 * r] = batch.doc_off[r]; docs_out[2 * r + 1] = batch.doc_len[r]; }
+        ret = batch.text_bytes;
+        if (batch.text_bytes && batch.text_bytes <= capacity) {
+            if (!d_text) throw err_internal("smgpu_sigwrite_json_raw: null pointer");
+            hip_check(hipMemcpyAsync(d_text, batch.text.p, batch.text_bytes, hipMemcpyDeviceToDevice, st), "D2D");
+            hip_check(hipStreamSynchronize(st), "sync");
+        }
+    });
+    return ret;
+}
+
+// Every document docs[2 d] .. + docs[2 d + 1] of d_text (offsets: multiples of 16) as a gzip member of its own in d_out: compression
+// 0 stored blocks, otherwise one dynamic-Huffman block of literals, packed `chunk` bytes a workgroup (0: the library's chunk).
+// members_out: offset and length of every member in d_out.  -> bytes of output (nothing is written when they exceed the capacity).
+uint64_t smgpu_deflate_literals_raw(const uint8_t* d_text, uint64_t text_len, const uint64_t* docs, uint32_t n_docs, uint8_t compression, uint32_t chunk,
+                                    uint8_t* d_out, uint64_t capacity, uint64_t* members_out, void* stream) {
+    uint64_t ret = ~0ull;
+    landing_void([&] {
+        if (n_docs == 0) { ret = 0; return; }
+        if (!docs || !members_out) throw err_internal("smgpu_deflate_literals_raw: null pointer");
+        std::vector<uint64_t> off(n_docs), len(n_docs);
+        for (uint32_t d = 0; d < n_docs; ++d) {
+            off[d] = docs[2 * d]; len[d] = docs[2 * d + 1];
+            if (off[d] > text_len || len[d] > text_len - off[d]) throw err_internal("smgpu_deflate_literals_raw: document " + std::to_string(d) + " reaches outside the text");
+            if (off[d] % SW_DOC_ALIGN) throw err_internal("smgpu_deflate_literals_raw: document offsets must be multiples of " + std::to_string(SW_DOC_ALIGN));
+            if (len[d] && !d_text) throw err_internal("smgpu_deflate_literals_raw: null pointer");
+            if (len[d] && reinterpret_cast<uintptr_t>(d_text) % SW_DOC_ALIGN)      // before anything is launched: the CRC kernel loads 16 bytes a lane
+                throw err_internal("smgpu_deflate_literals_raw: d_text must be " + std::to_string(SW_DOC_ALIGN) + "-byte aligned");
+        }
+        DeviceCtx& ctx = DeviceCtx::get();                          // (the pinned ring, the writer's tables and counters are the context's)
+        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+        hipStream_t st = (hipStream_t)stream;
+        SwPacked packed;
+        sw_deflate_docs(d_text, off, len, compression, chunk ? chunk : SW_PACK_CHUNK, packed, st);
+        for (uint32_t d = 0; d < n_docs; ++d) { members_out[2 * d] = packed.off[d]; members_out[2 * d + 1] = packed.len[d]; }
+        ret = packed.out_bytes;
+        if (packed.out_bytes <= capacity) {
+            if (!d_out) throw err_internal("smgpu_deflate_literals_raw: null pointer");
+            hip_check(hipMemcpyAsync(d_out, packed.out.p, packed.out_bytes, hipMemcpyDeviceToDevice, st), "D2D");
+            hip_check(hipStreamSynchronize(st), "sync");
+        }
+    });
+    return ret;
 }
 
 SourmashSignature** smgpu_sketch_file_singleton(const char* path, const SourmashComputeParameters* params, uintptr_t* n) {

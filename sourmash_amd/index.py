@@ -26,7 +26,7 @@ from .search import calc_threshold_from_bp, make_containment_query, make_jaccard
 from .signature import SourmashSignature, load_signatures_from_json, save_signatures_to_json
 from .utils import RustObject, decode_str, objptr_array, rustcall
 
-__all__ = ["IndexSearchResult", "Collection", "SketchSet", "select_signature", "Index", "LinearIndex", "CounterGather"]
+__all__ = ["IndexSearchResult", "Collection", "SketchSet", "SketchSetWriter", "select_signature", "Index", "LinearIndex", "CounterGather"]
 
 IndexSearchResult = namedtuple("Result", "score, signature, location")
 
@@ -146,6 +146,30 @@ class SketchSet(RustObject):
                                          moltype.encode() if moltype else None, int(scaled or 0), int(threads)))
 
     @classmethod
+    def from_csr(cls, hashes, offsets, *, ksize, scaled=0, num=0, seed=42, moltype="DNA", names=None, filenames=None):
+        """n flat sketches from device tensors (smgpu_sketchset_from_csr): row r = hashes[offsets[r]:offsets[r + 1]], ascending.
+        hashes: int64 / uint64 device tensor (the bits are the hashes); offsets: int64 device tensor of n + 1 positions.  The rows
+        are copied.  names / filenames: one string per row for the manifest."""
+        from .device import _ptr, _torch
+        from .minhash import _get_max_hash_for_scaled
+        torch = _torch()
+        assert hashes.is_cuda and hashes.is_contiguous() and hashes.element_size() == 8
+        assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and offsets.numel() >= 1
+        n = offsets.numel() - 1
+
+        def strings(values):
+            if values is None:
+                return None
+            values = [v.encode("utf-8") if isinstance(v, str) else bytes(v) for v in values]
+            if len(values) != n:
+                raise ValueError("one string per row is needed")
+            return (C.c_char_p * max(n, 1))(*values)
+        hf = {"DNA": 1, "PROTEIN": 2, "DAYHOFF": 3, "HP": 4}[moltype.upper()]
+        torch.cuda.current_stream().synchronize()                   # the library works on its own stream
+        return cls._from_objptr(rustcall(lib.smgpu_sketchset_from_csr, _ptr(hashes), _ptr(offsets), n, int(ksize), hf, int(seed),
+                                         _get_max_hash_for_scaled(int(scaled)) if scaled else 0, int(num), strings(names), strings(filenames)))
+
+    @classmethod
     def sketch_records(cls, seq, starts, *, ksize, scaled, seed=42):
         """One flat scaled DNA sketch per record of a device buffer, in one pass (smgpu_sketchset_sketch_records).
 
@@ -183,6 +207,7 @@ class SketchSet(RustObject):
             mhs.append(mh)
             names.append(name)
         out = cls(mhs)
+        out.set_names(names, [path] * len(names))                   # (what to_json / save write; the manifest below says the same)
         sizes = out.sizes
         out._manifest = [dict(internal_location="", md5="", md5short="", ksize=int(ksize), moltype="DNA", num=0, scaled=int(scaled),
                               n_hashes=int(sizes[i]), with_abundance=False, name=names[i], filename=path) for i in range(len(names))]
@@ -224,6 +249,47 @@ class SketchSet(RustObject):
     def minhash(self, row):
         from .minhash import MinHash
         return MinHash._from_objptr(self._methodcall(lib.smgpu_sketchset_get, int(row)))
+
+    def set_names(self, names=None, filenames=None):
+        """One name / file name per row: what the set's signatures are written with (to_json, save, SketchSetWriter) and what its
+        manifest rows say.  A set built from MinHash objects has none until they are given.  None leaves them as they are."""
+        def strings(values):
+            if values is None:
+                return None
+            values = [v.encode("utf-8") if isinstance(v, str) else bytes(v) for v in values]
+            if len(values) != len(self):
+                raise ValueError("one string per row of the set is needed")
+            return (C.c_char_p * max(len(values), 1))(*values)
+        self._methodcall(lib.smgpu_sketchset_set_names, strings(names), strings(filenames))
+        if self._keep == ():
+            self._manifest = None                                   # (a loaded set: read the rows again)
+
+    def md5sums(self):
+        "the md5sum of every row's sketch as hex strings, computed on the device (smgpu_sketchset_md5sums)"
+        n = len(self)
+        out = np.zeros(max(16 * n, 1), dtype=np.uint8)
+        self._methodcall(lib.smgpu_sketchset_md5sums, out.ctypes.data_as(C.c_void_p))
+        raw = out.tobytes()
+        return [raw[16 * i:16 * i + 16].hex() for i in range(n)]
+
+    def to_json(self, rows=None, compression=0):
+        """The rows' signatures as the bytes save_signatures_to_json gives for [self.signature(r) for r in rows] (rows None: every
+        row), written on the device (smgpu_sketchset_to_json).  compression > 0: the array as one gzip member."""
+        size = C.c_size_t(0)
+        if rows is None:
+            raw = self._methodcall(lib.smgpu_sketchset_to_json, None, len(self), int(compression), C.byref(size))
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.uint64)
+            raw = self._methodcall(lib.smgpu_sketchset_to_json, rows.ctypes.data_as(C.c_void_p), len(rows), int(compression), C.byref(size))
+        try:
+            return C.string_at(raw, size.value)
+        finally:
+            lib.nodegraph_buffer_free(raw, size.value)
+
+    def save(self, path, *, compression=1):
+        "write the set to `path`: .zip, .sig.gz (any .gz) or .sig (anything else), as SketchSetWriter does"
+        with SketchSetWriter(path, compression=compression) as w:
+            w.add(self)
 
     def subset(self, rows):
         "the given rows of a loaded set as a new set (device-side row gather; the manifest rows follow)"
@@ -329,6 +395,46 @@ def _check_select_parameters(**kw):
         v = kw.get(key)
         if v is not None and not isinstance(v, bool):
             raise ValueError(f"{key} value '{v}' must be a bool, is: {type(v)}")
+
+
+class SketchSetWriter(RustObject):
+    """Signature file written from the device (smgpu_sigwriter_*): the counterpart of SketchSet.load and of the reference's
+    SaveSignaturesToLocation (save_load.py:406-540).  The suffix of `path` chooses the form: `.zip` (gzip members
+    `signatures/<md5>.sig.gz` and `SOURMASH-MANIFEST.csv`), `.gz` (the JSON array as one gzip member), anything else the JSON
+    array.  Several sets may be added (k = 21, 31, 51 of one file); the file appears when the writer is closed without an error.
+
+        with SketchSetWriter("out.zip") as w:
+            w.add(set21)
+            w.add(set31)"""
+    __dealloc_func__ = lib.smgpu_sigwriter_free
+
+    def __init__(self, path, compression=1):
+        self._objptr = rustcall(lib.smgpu_sigwriter_new, os.fsencode(os.fspath(path)), int(compression))
+        self._closed = False
+
+    def add(self, sketchset, names=None, filenames=None):
+        "the rows of a SketchSet; names / filenames: one string per row, in place of the set's manifest rows"
+        def strings(values):
+            if values is None:
+                return None
+            values = [v.encode("utf-8") if isinstance(v, str) else bytes(v) for v in values]
+            if len(values) != len(sketchset):
+                raise ValueError("one string per row of the set is needed")
+            return (C.c_char_p * max(len(values), 1))(*values)
+        self._methodcall(lib.smgpu_sigwriter_add, sketchset._get_objptr(), strings(names), strings(filenames))
+
+    def close(self):
+        if not self._closed:
+            self._closed = True
+            self._methodcall(lib.smgpu_sigwriter_close)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        return False
 
 
 def select_signature(ss, *, ksize=None, moltype=None, scaled=0, num=0, containment=False, abund=None, picklist=None):

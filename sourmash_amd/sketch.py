@@ -421,6 +421,43 @@ def sketch_file(path, param_str=DEFAULTS["dna"], *, name=None, check_sequence=Fa
                           singleton=singleton, moltype=moltype, input_is_protein=input_is_protein)
 
 
+def sketch_file_to(path, out, param_str=DEFAULTS["dna"], *, singleton=True, compression=1):
+    """`sourmash sketch dna --singleton -p <param_str> <path> -o <out>`: the records' sketches written to `out` (.zip, .sig.gz,
+    .sig) without a SourmashSignature object per record.  Where sketch_file(singleton=True) takes the one-pass per-record
+    path (scaled DNA sketches, k <= 88, a file within its size limit), every ksize becomes a SketchSet on the device and goes
+    straight into a SketchSetWriter (one set after the other: all records of the first ksize, then the next); every other
+    case is sketch_file followed by save_signatures_to_json (.sig, .sig.gz) or the same writer, a member per sketch (.zip).
+    -> number of sketches written."""
+    import os
+    from .index import SketchSet, SketchSetWriter
+    from .signature import save_signatures_to_json
+    path, out = os.fspath(path), os.fspath(out)
+    params = ComputeParameters.from_param_str(param_str)
+    if (singleton and params.dna and params.num_hashes == 0 and params.scaled and not params.track_abundance
+            and _records_path_takes(path, params.ksizes)):
+        n = 0
+        with SketchSetWriter(out, compression=compression) as w:
+            for k in params.ksizes:
+                sset = SketchSet.sketch_file(path, ksize=k, scaled=params.scaled, seed=params.seed)
+                w.add(sset)
+                n += len(sset)
+        return n
+    sigs = sketch_file(path, param_str, singleton=singleton)
+    n = sum(len(sig.minhashes()) for sig in sigs)                    # a signature holds a sketch per ksize (and molecule)
+    if out.endswith(".zip"):
+        # a member per sketch, as the reference's zip writer flattens a signature (save_load.py:527)
+        sketches = [(sig, mh) for sig in sigs for mh in sig.minhashes()]
+        if any(mh.track_abundance for _, mh in sketches):
+            raise NotImplementedError("a SketchSet is flat: abundance sketches cannot be written to a zip by this writer")
+        with SketchSetWriter(out, compression=compression) as w:
+            for sig, mh in sketches:
+                w.add(SketchSet([mh]), names=[sig.name], filenames=[sig.filename])
+    else:
+        with open(out, "wb") as fp:
+            save_signatures_to_json(sigs, fp, compression=compression if out.endswith(".gz") else 0)
+    return n
+
+
 def sketch_files(paths, param_str=DEFAULTS["dna"], *, threads=0):
     """`sourmash sketch dna -p <param_str> f1 f2 ...` -> one SourmashSignature per file, in order.
 
