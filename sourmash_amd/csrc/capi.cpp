@@ -4,9 +4,8 @@
 // (src/core/src/ffi/{utils,mod,minhash,signature,cmd/compute}.rs) on top of the
 // host containers (minhash_host.hpp, signature_host.hpp) and the HIP kernels
 // (DeviceCtx / device_api.hpp).  Part 2 are the smgpu_* batch extensions.
-#if defined(__SSE2__)
-#include <emmintrin.h>
-#endif
+// The HyperLogLog and Nodegraph families are units of their own (capi_hll.cpp, capi_nodegraph.cpp); capi_common.hpp is
+// what the units share, record_queue.hpp the deferred-record queue of all three add_sequence families.
 #include <hip/hip_runtime_api.h>
 #include <stdio.h>
 #include <string.h>
@@ -18,14 +17,11 @@
 #include <memory>
 #include <sstream>
 #include <thread>
-#include "../../include/sourmash_amd.h"
-#include "collection.hpp"
+#include "capi_common.hpp"
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
-#include "device_ctx.hpp"
-#include "hostxfer.hpp"
 #include "pargz.hpp"
 #include "ingest.hpp"
 #include "sigload.hpp"
@@ -33,100 +29,12 @@
 #include "murmur3.hpp"
 #include "uniform_sort_core.hpp"
 #include "residues.hpp"
-#include "signature_host.hpp"
-#include "hll_host.hpp"
-#include "nodegraph_host.hpp"
 
 using namespace smg;
 
-// ---------------------------------------------------------------------------------------------
-// thread-local last error + landing pad (ffi/utils.rs:17-19,58-83,195-207)
-// ---------------------------------------------------------------------------------------------
 namespace {
 
-thread_local uint32_t g_err_code = 0;
-thread_local std::string g_err_msg;
-
-void set_error(uint32_t code, const std::string& msg) { g_err_code = code; g_err_msg = msg; }
-
-template <class R, class F>
-R landing(F&& f) {
-    try {
-        return f();
-    } catch (const Error& e) {
-        set_error(e.code, e.what());
-    } catch (const std::bad_alloc&) {
-        set_error(E_PANIC, "sourmash panicked: out of memory");
-    } catch (const std::exception& e) {
-        set_error(E_PANIC, std::string("sourmash panicked: ") + e.what());
-    } catch (...) {
-        set_error(E_PANIC, "sourmash panicked: unknown exception");
-    }
-    return R{};
-}
-template <class F>
-void landing_void(F&& f) {
-    landing<int>([&]() { f(); return 0; });
-}
-
-SourmashStr make_str(const std::string& s) {
-    SourmashStr out;
-    out.data = (char*)malloc(s.size() + 1);
-    memcpy(out.data, s.data(), s.size());
-    out.data[s.size()] = 0;
-    out.len = s.size();
-    out.owned = true;
-    return out;
-}
-
-// ---- deferred sketching behind the per-record API -------------------------------------------------------------
-// The reference's loop is one add_sequence per record (src/sourmash/command_sketch.py:746-768, signature.rs:38-58).
-// A kernel launch per 150-base read would cost ~40 us of copy + launch + synchronise each, so add_sequence only
-// validates and appends the record to the sketch's `pending` buffer; the buffer goes through the sketch kernel in one
-// launch when it is large enough or when anything looks at the sketch (every accessor below goes through MH / SIG,
-// which settle first).  Results are those of immediate hashing: adding hashes to a sketch commutes (set union, counts
-// add, bottom-k keeps the smallest), and everything that does not commute with it settles first.
-constexpr size_t PENDING_FLUSH_BYTES = (size_t)32 << 20;
-void settle(KmerMinHash& mh, bool streaming = false);
-
-inline KmerMinHash* RAW(SourmashKmerMinHash* p) { return reinterpret_cast<KmerMinHash*>(p); }
-inline const KmerMinHash* RAW(const SourmashKmerMinHash* p) { return reinterpret_cast<const KmerMinHash*>(p); }
-inline KmerMinHash* settled(KmerMinHash* m) {
-    if (m && !m->pending.empty()) {
-        // accessors without a landing pad cannot throw across the C boundary: the failure is left in the thread's error slot
-        try { settle(*m); }
-        catch (const Error& e) { set_error(e.code, e.what()); }
-        catch (const std::exception& e) { set_error(E_PANIC, std::string("sourmash panicked: ") + e.what()); }
-    }
-    return m;
-}
-inline KmerMinHash* MH(SourmashKmerMinHash* p) { return settled(reinterpret_cast<KmerMinHash*>(p)); }
-inline const KmerMinHash* MH(const SourmashKmerMinHash* p) { return settled(const_cast<KmerMinHash*>(reinterpret_cast<const KmerMinHash*>(p))); }
-inline Signature* SIGRAW(SourmashSignature* p) { return reinterpret_cast<Signature*>(p); }
-inline Signature* SIG(SourmashSignature* p) {
-    Signature* s = reinterpret_cast<Signature*>(p);
-    if (s) for (auto& mh : s->sketches) settled(&mh);
-    return s;
-}
-inline const Signature* SIG(const SourmashSignature* p) { return SIG(const_cast<SourmashSignature*>(p)); }
-inline ComputeParameters* CP(SourmashComputeParameters* p) { return reinterpret_cast<ComputeParameters*>(p); }
-inline const ComputeParameters* CP(const SourmashComputeParameters* p) { return reinterpret_cast<const ComputeParameters*>(p); }
-
-uint64_t* slice_out(const std::vector<uint64_t>& v, uintptr_t* size) {
-    *size = v.size();
-    uint64_t* p = (uint64_t*)malloc((v.size() ? v.size() : 1) * sizeof(uint64_t));
-    if (v.size()) memcpy(p, v.data(), v.size() * sizeof(uint64_t));
-    return p;
-}
-
-std::string upper_ascii(const uint8_t* p, size_t n) {
-    std::string s((const char*)p, n);
-    for (auto& c : s) if (c >= 'a' && c <= 'z') c = (char)(c - 32);
-    return s;
-}
-
-inline uint64_t keep_threshold(const KmerMinHash& mh) { return mh.max_hash ? mh.max_hash : ~0ull; }
-
+// ---- deferred sketching behind the per-record API (record_queue.hpp) ---------------------------------------------
 // The DNA add_sequence path (signature.rs:38-58 + :246-306) on the GPU.
 // force == false: the walk is streaming in the reference, so the hashes of every
 // k-mer before the first offending one are added before InvalidDNA is raised.
@@ -145,50 +53,20 @@ void add_residue_kmers(KmerMinHash& mh, const uint8_t* seq, size_t len, bool is_
     mh.add_sorted_batch(hs.data(), mh.track_abundance ? cs.data() : nullptr, hs.size());
 }
 
-// first byte outside ACGTacgt (what kills a k-mer, encodings.rs:370-377 after signature.rs:214's upper-casing), or SIZE_MAX.
-// Only decides whether add_sequence(force = false) must raise and where the valid prefix ends; the k-mers themselves
-// are validated again, hashed and filtered by the kernel.
-size_t first_invalid_byte(const uint8_t* seq, size_t len) {
-    static const struct Table {
-        uint8_t bad[256];
-        Table() { memset(bad, 1, sizeof(bad)); for (const char* c = "ACGTacgt"; *c; ++c) bad[(uint8_t)*c] = 0; }
-    } t;
-    size_t i = 0;
-#if defined(__SSE2__)
-    // sixteen bytes at a time (SSE2, part of every x86-64): fold the case bit away, then a byte is fine iff it equals one
-    // of A C G T (a byte >= 0x80 keeps its top bit and equals none of them)
-    const __m128i fold = _mm_set1_epi8((char)0xdf), cA = _mm_set1_epi8('A'), cC = _mm_set1_epi8('C'), cG = _mm_set1_epi8('G'),
-                  cT = _mm_set1_epi8('T');
-    for (; i + 16 <= len; i += 16) {
-        const __m128i x = _mm_and_si128(_mm_loadu_si128(reinterpret_cast<const __m128i*>(seq + i)), fold);
-        const __m128i ok = _mm_or_si128(_mm_or_si128(_mm_cmpeq_epi8(x, cA), _mm_cmpeq_epi8(x, cC)),
-                                        _mm_or_si128(_mm_cmpeq_epi8(x, cG), _mm_cmpeq_epi8(x, cT)));
-        const unsigned m = (unsigned)_mm_movemask_epi8(ok);
-        if (m != 0xffffu) return i + (size_t)__builtin_ctz(~m & 0xffffu);
-    }
-#endif
-    for (; i < len; ++i)
-        if (t.bad[seq[i]]) return i;
-    return SIZE_MAX;
-}
+}  // namespace
 
-void settle(KmerMinHash& mh, bool streaming) {
+// MinHash's rule: ONE process-wide lock for settling, none for appending, and the queue is consumed whatever the device work does.
+void smg::settle(KmerMinHash& mh, bool streaming) {
     // Accessors that only read (get_mins, md5sum, similarity ...) come through here too, possibly from two threads on
     // the same sketch (ctypes releases the GIL): one of them hashes the queue, the other finds it empty afterwards.
     static std::recursive_mutex settle_mu;
     std::lock_guard<std::recursive_mutex> sg(settle_mu);
     if (mh.pending.empty()) return;
-    // whatever happens below, the records are consumed once.  A flush from inside the add_sequence loop (`streaming`)
-    // keeps the queue's storage (a fresh 32 MiB string per flush costs 8,192 page faults, which was a fifth of the
-    // per-record time of a loop over 150-bp reads); a flush because somebody looks at the sketch gives storage beyond
-    // 1 MiB back, or every sketch of a many-ksize signature would hold a copy of its longest record for life.
+    // whatever happens below, the records are consumed once: adding their hashes a second time would count them twice
     struct Consume {
         std::string& q;
         bool keep;
-        ~Consume() {
-            if (keep || q.capacity() <= ((size_t)1 << 20)) q.clear();
-            else std::string().swap(q);
-        }
+        ~Consume() { release_queue(q, keep); }
     } consume{mh.pending, streaming};
     DeviceCtx& ctx = DeviceCtx::get();
     std::lock_guard<std::recursive_mutex> g(ctx.mutex());
@@ -197,6 +75,8 @@ void settle(KmerMinHash& mh, bool streaming) {
                     mh.num, hs, cs);
     mh.add_sorted_batch(hs.data(), mh.track_abundance ? cs.data() : nullptr, hs.size());
 }
+
+namespace {
 
 // The DNA add_sequence path (signature.rs:38-58 + :246-306).
 // force == false: the walk is streaming in the reference, so the hashes of every k-mer before the first offending
@@ -209,25 +89,9 @@ void add_sequence_dna(KmerMinHash& mh, const uint8_t* seq, size_t len, bool forc
     if (mh.num == 0 && mh.max_hash == 0) return;                    // sketch that can never hold anything
     (void)DeviceCtx::get();                                         // no device: fail now, not at the first accessor
     check_dna_ksize(k);
-    size_t use_len = len;
-    bool raise = false;
-    size_t bad_kmer = 0;
-    if (!force) {
-        const size_t p = scanned ? first_bad : first_invalid_byte(seq, len);
-        if (p != SIZE_MAX) {
-            bad_kmer = p + 1 >= k ? p + 1 - k : 0;                  // first k-mer whose window covers byte p
-            if (bad_kmer < len - k + 1) {
-                raise = true;
-                use_len = bad_kmer + k - 1;                         // k-mers 0 .. bad_kmer-1 only
-            }
-        }
-    }
-    if (use_len >= k) {
-        mh.pending.append((const char*)seq, use_len);
-        mh.pending.push_back('\n');                                 // records never share a k-mer
-        if (mh.pending.size() >= PENDING_FLUSH_BYTES) settle(mh, true);
-    }
-    if (raise) throw err_invalid_dna(upper_ascii(seq + bad_kmer, k));   // errors.rs:49-50
+    const ValidPrefix v = valid_prefix(seq, len, k, force, scanned, first_bad);
+    if (queue_record(mh.pending, seq, v.use_len, k)) settle(mh, true);
+    if (v.raise) throw err_invalid_dna(upper_ascii(seq + v.bad_kmer, k));   // errors.rs:49-50
 }
 
 struct Downsampled {
@@ -1564,16 +1428,6 @@ void smgpu_compare_abund_raw_n(const uint64_t* d_hashes, const uint64_t* d_abund
 }
 
 // ---- device-resident sketch collections and gather counters ------------------------------------
-struct SketchSet {
-    DevBuf hashes, offsets;
-    uint64_t n = 0, total = 0;
-    // filled by smgpu_sketchset_load (empty for sets built from sketch handles)
-    std::vector<uint64_t> host_offsets;
-    std::vector<ManifestRow> rows;
-    uint32_t ksize = 0, hash_function = HF_DNA;
-    uint64_t seed = 42, max_hash = 0, num = 0, skipped = 0;
-    // (the device blocks are arena blocks and go back to the arena with the DevBufs: no hipFree, which would synchronise the device)
-};
 struct GatherCounter {
     const SketchSet* set = nullptr;
     DevBuf q, list, scal;
@@ -1935,6 +1789,7 @@ void smgpu_sketchset_compare(const SmgpuSketchSet* p, uint32_t* common_out, doub
 // ---- one sketch per record of a device buffer / of a file (sketch_records.hip) ----------------------------------------------
 // The reference's singleton loop (src/sourmash/command_sketch.py:712-739) makes a signature object, an add_sequence call and a
 // sorted insert per record; here the records of a buffer become the rows of one CSR in a single pass over the buffer.
+}  // extern "C"
 namespace {
 
 constexpr uint64_t RECORDS_MAX_FILE = (uint64_t)2 << 30;            // a file is resident as a whole (ingest.hpp: MAX_FILE)
@@ -2129,6 +1984,7 @@ void parse_records_file(const std::string& path, ParsedRecords& out, hipStream_t
 }
 
 }  // namespace
+extern "C" {
 
 uint64_t smgpu_sketch_records_workspace_bytes(uint64_t pair_capacity, uint64_t n_records) {
     (void)n_records;                                                // (the offsets are the caller's; the scratch depends on the pairs alone)
@@ -2235,6 +2091,7 @@ SmgpuSketchSet* smgpu_sketchset_sketch_file(const char* path, uint32_t ksize, ui
 }
 
 // ---- signature writer (sigwrite.hpp): a set's rows as .sig / .sig.gz / .zip, written from the device ---------------------------
+}  // extern "C"
 namespace {
 
 // a set as the writer's source; `off`: room for the offsets of a set that keeps none on the host
@@ -2272,6 +2129,7 @@ struct SigWriterHandle {
 };
 
 }  // namespace
+extern "C" {
 
 // A set from a CSR the caller holds in HBM (torch tensors): n flat sketches of shared parameters, row r = d_hashes[d_offsets[r] ..
 // d_offsets[r + 1]) ascending.  The rows are copied (device to device) on the library's stream; names / filenames: NULL or one C
@@ -2619,6 +2477,7 @@ SourmashSignature** smgpu_sketch_file_singleton(const char* path, const Sourmash
 }
 
 // ---- a sketch's k-mers in sequences (sketch_find.hip; `sourmash sig kmers`, src/sourmash/sig/__main__.py:1087-1310) ----------
+}  // extern "C"
 namespace {
 
 // The query: the merged sketch on the host; its hashes and their bucket directory (find_core.hpp) go to the device when a find
@@ -2705,6 +2564,7 @@ struct KmerMatches {
 };
 
 }  // namespace
+extern "C" {
 
 SmgpuKmerQuery* smgpu_kmerquery_new(const SourmashKmerMinHash* const* mhs, uintptr_t n) {
     return landing<SmgpuKmerQuery*>([&]() -> SmgpuKmerQuery* {
@@ -3260,719 +3120,6 @@ void smgpu_intersect_raw(const uint64_t* d_a, uint64_t na, const uint64_t* d_b, 
 void smgpu_subtract_raw(const uint64_t* d_a, uint64_t na, const uint64_t* d_b, uint64_t nb, uint64_t* d_out, uint64_t* d_n,
                         void* d_ws, uint64_t ws_bytes, void* stream) {
     select_pair(d_a, na, d_b, nb, d_out, d_n, d_ws, ws_bytes, 1, stream);
-}
-
-// =============================================================================================
-// HyperLogLog (ffi/hyperloglog.rs over sketch/hyperloglog/mod.rs): the host container is hll_host.hpp; k-mers reach the
-// registers through hll.hip.  add_sequence queues records like the MinHash path above (no launch per record: the reference's
-// tests make 1.5 million add calls of 21 bases); every reader of the registers settles the queue first.  Creating, add_hash,
-// merge, the estimators and load / save never touch the device.
-// =============================================================================================
-}  // extern "C"
-namespace {
-
-inline HyperLogLog* HLLRAW(SourmashHyperLogLog* p) { return reinterpret_cast<HyperLogLog*>(p); }
-inline HyperLogLog* HLLRAW(const SourmashHyperLogLog* p) { return reinterpret_cast<HyperLogLog*>(const_cast<SourmashHyperLogLog*>(p)); }
-
-// Run device work on the handle's registers: upload them as u32, `work(d_regs, stream)`, pack to u8 on the device, read back.
-template <class F>
-void hll_on_device(HyperLogLog& h, F&& work) {
-    if (h.registers.empty()) throw err_internal("HyperLogLog without registers (made by hll_new)");
-    DeviceCtx& ctx = DeviceCtx::get();
-    std::lock_guard<std::recursive_mutex> g(ctx.mutex());
-    hipStream_t st = ctx.stream();
-    const uint32_t n = (uint32_t)h.registers.size();
-    std::vector<uint32_t> wide(h.registers.begin(), h.registers.end());
-    AsyncBuf d_regs((size_t)n * 4, st), d_packed(n, st);
-    hip_check(hipMemcpyAsync(d_regs.p, wide.data(), (size_t)n * 4, hipMemcpyHostToDevice, st), "H2D");
-    work(d_regs.as<uint32_t>(), st);
-    hip_check(hll_pack_launch(d_regs.as<uint32_t>(), n, d_packed.as<uint8_t>(), st), "hll_pack");
-    hip_check(hipMemcpyAsync(h.registers.data(), d_packed.p, n, hipMemcpyDeviceToHost, st), "D2H");
-    hip_check(hipStreamSynchronize(st), "sync");
-}
-
-void hll_settle(HyperLogLog& h, bool streaming = false) {
-    std::lock_guard<std::recursive_mutex> sg(h.settle_mu);
-    if (h.pending.empty()) return;
-    std::string& q = h.pending;
-    hll_on_device(h, [&](uint32_t* d_regs, hipStream_t st) {
-        AsyncBuf d_seq(q.size() + 64, st);
-        hip_check(hipMemcpyAsync(d_seq.p, q.data(), q.size(), hipMemcpyHostToDevice, st), "H2D");
-        hip_check(hll_dna_launch(d_seq.as<uint8_t>(), q.size(), (uint32_t)h.ksize, (uint32_t)h.p, d_regs, st), "hll_dna");
-        hip_check(hipStreamSynchronize(st), "sync");    // d_seq is released at the end of this scope
-    });
-    // Consumed only once the registers hold the records: if the device work throws, the queue stays and the error reaches
-    // the caller; hashing it again later is harmless (register updates are max operations, so repeating one changes nothing).
-    // A flush from inside the add_sequence loop (`streaming`) keeps the queue's storage; a flush because somebody reads the
-    // registers gives storage beyond 1 MiB back.
-    if (streaming || q.capacity() <= ((size_t)1 << 20)) q.clear();
-    else std::string().swap(q);
-}
-
-// Every reader settles the queue first; the emptiness test is made under the handle's lock (hll_settle), as the appends are.
-inline HyperLogLog* HLL(SourmashHyperLogLog* p) {
-    HyperLogLog* h = HLLRAW(p);
-    if (h) hll_settle(*h);
-    return h;
-}
-inline const HyperLogLog* HLL(const SourmashHyperLogLog* p) { return HLL(const_cast<SourmashHyperLogLog*>(p)); }
-
-// SigsTrait::add_sequence (signature.rs:38-58) into an HLL: seed 42, hash 0 skipped; force == false raises InvalidDNA naming
-// the first bad k-mer after the k-mers before it have been queued (the MinHash path's add_sequence_dna)
-void hll_add_sequence_impl(HyperLogLog& h, const uint8_t* seq, size_t len, bool force) {
-    const size_t k = h.ksize;
-    if (h.registers.empty()) throw err_internal("HyperLogLog without registers (made by hll_new)");
-    if (k == 0 || len < k) return;
-    (void)DeviceCtx::get();
-    check_dna_ksize((uint32_t)std::min<size_t>(k, UINT32_MAX));
-    size_t use_len = len;
-    bool raise = false;
-    size_t bad_kmer = 0;
-    if (!force) {
-        const size_t p = first_invalid_byte(seq, len);
-        if (p != SIZE_MAX) {
-            bad_kmer = p + 1 >= k ? p + 1 - k : 0;
-            if (bad_kmer < len - k + 1) {
-                raise = true;
-                use_len = bad_kmer + k - 1;
-            }
-        }
-    }
-    if (use_len >= k) {
-        std::lock_guard<std::recursive_mutex> sg(h.settle_mu);
-        h.pending.append((const char*)seq, use_len);
-        h.pending.push_back('\n');
-        if (h.pending.size() >= PENDING_FLUSH_BYTES) hll_settle(h, true);
-    }
-    if (raise) throw err_invalid_dna(upper_ascii(seq + bad_kmer, k));
-}
-
-// hashes of a sketch into h: small sketches on the host, large ones through hll_hashes_kernel
-void hll_add_hashes(HyperLogLog& h, const std::vector<uint64_t>& hs) {
-    constexpr size_t DEVICE_FROM = (size_t)1 << 16;
-    if (hs.size() < DEVICE_FROM) {
-        for (uint64_t x : hs) h.add_hash(x);
-        return;
-    }
-    hll_on_device(h, [&](uint32_t* d_regs, hipStream_t st) {
-        AsyncBuf d_h(hs.size() * 8, st);
-        hip_check(hipMemcpyAsync(d_h.p, hs.data(), hs.size() * 8, hipMemcpyHostToDevice, st), "H2D");
-        hip_check(hll_hashes_launch(d_h.as<uint64_t>(), hs.size(), (uint32_t)h.p, d_regs, false, st), "hll_hashes");
-        hip_check(hipStreamSynchronize(st), "sync");
-    });
-}
-
-HyperLogLog hll_read_plain(const std::string& raw) {
-    const std::string text = maybe_gunzip(raw.data(), raw.size());
-    return HyperLogLog::parse((const uint8_t*)text.data(), text.size());
-}
-
-}  // namespace
-extern "C" {
-
-SourmashHyperLogLog* hll_new(void) { return reinterpret_cast<SourmashHyperLogLog*>(new HyperLogLog()); }
-void hll_free(SourmashHyperLogLog* ptr) { delete HLLRAW(ptr); }
-
-SourmashHyperLogLog* hll_with_error_rate(double error_rate, uintptr_t ksize) {
-    return landing<SourmashHyperLogLog*>([&] {
-        return reinterpret_cast<SourmashHyperLogLog*>(new HyperLogLog(HyperLogLog::make(HyperLogLog::precision_for(error_rate), ksize)));
-    });
-}
-
-uintptr_t hll_ksize(const SourmashHyperLogLog* ptr) { return HLLRAW(ptr)->ksize; }
-
-uintptr_t hll_cardinality(const SourmashHyperLogLog* ptr) {
-    return landing<uintptr_t>([&] { return (uintptr_t)HLL(ptr)->cardinality(); });
-}
-double hll_similarity(const SourmashHyperLogLog* ptr, const SourmashHyperLogLog* optr) {
-    return landing<double>([&] { return HLL(ptr)->similarity(*HLL(optr)); });
-}
-double hll_containment(const SourmashHyperLogLog* ptr, const SourmashHyperLogLog* optr) {
-    return landing<double>([&] { return HLL(ptr)->containment(*HLL(optr)); });
-}
-uintptr_t hll_intersection_size(const SourmashHyperLogLog* ptr, const SourmashHyperLogLog* optr) {
-    return landing<uintptr_t>([&] { return (uintptr_t)HLL(ptr)->intersection(*HLL(optr)); });
-}
-
-void hll_add_sequence(SourmashHyperLogLog* ptr, const char* sequence, uintptr_t insize, bool force) {
-    landing_void([&] {
-        if (!sequence && insize) throw err_internal("null sequence");
-        hll_add_sequence_impl(*HLLRAW(ptr), (const uint8_t*)sequence, insize, force);
-    });
-}
-void hll_add_hash(SourmashHyperLogLog* ptr, uint64_t hash) {
-    landing_void([&] { HLLRAW(ptr)->add_hash(hash); });
-}
-
-void hll_merge(SourmashHyperLogLog* ptr, const SourmashHyperLogLog* optr) {
-    landing_void([&] {
-        HyperLogLog* a = HLL(ptr);
-        const HyperLogLog* b = HLL(optr);
-        if (a == b) return;
-        std::lock_guard<std::recursive_mutex> sg(a->settle_mu);
-        a->merge(*b);
-    });
-}
-
-void hll_update_mh(SourmashHyperLogLog* ptr, const SourmashKmerMinHash* optr) {
-    landing_void([&] {
-        HyperLogLog* h = HLL(ptr);
-        const KmerMinHash* mh = MH(optr);
-        if (h->registers.empty()) throw err_internal("HyperLogLog without registers (made by hll_new)");
-        std::lock_guard<std::recursive_mutex> sg(h->settle_mu);
-        hll_add_hashes(*h, mh->mins);
-    });
-}
-
-// KmerMinHash::as_hll (minhash.rs:759-767): the sketch's hashes in a fresh HLL at error rate 0.01, then `intersection`
-uintptr_t hll_matches(const SourmashHyperLogLog* ptr, const SourmashKmerMinHash* mh_ptr) {
-    return landing<uintptr_t>([&] {
-        const HyperLogLog* h = HLL(ptr);
-        const KmerMinHash* mh = MH(mh_ptr);
-        HyperLogLog other = HyperLogLog::make(HyperLogLog::precision_for(0.01), mh->ksize);
-        hll_add_hashes(other, mh->mins);
-        return (uintptr_t)h->intersection(other);
-    });
-}
-
-SourmashHyperLogLog* hll_from_path(const char* filename) {
-    return landing<SourmashHyperLogLog*>([&]() -> SourmashHyperLogLog* {
-        if (!filename) throw err_internal("null filename");
-        std::ifstream f(filename, std::ios::binary);
-        if (!f) throw Error(E_IO, std::string("No such file or directory: ") + filename);
-        std::stringstream ss;
-        ss << f.rdbuf();
-        return reinterpret_cast<SourmashHyperLogLog*>(new HyperLogLog(hll_read_plain(ss.str())));
-    });
-}
-
-SourmashHyperLogLog* hll_from_buffer(const char* ptr, uintptr_t insize) {
-    return landing<SourmashHyperLogLog*>([&]() -> SourmashHyperLogLog* {
-        if (!ptr && insize) throw err_internal("null buffer");
-        return reinterpret_cast<SourmashHyperLogLog*>(new HyperLogLog(hll_read_plain(std::string(ptr ? ptr : "", insize))));
-    });
-}
-
-void hll_save(const SourmashHyperLogLog* ptr, const char* filename) {
-    landing_void([&] {
-        if (!filename) throw err_internal("null filename");
-        const std::string s = HLL(ptr)->serialize();
-        std::ofstream f(filename, std::ios::binary | std::ios::trunc);
-        if (!f) throw Error(E_IO, std::string("cannot create ") + filename);
-        f.write(s.data(), (std::streamsize)s.size());
-        if (!f) throw Error(E_IO, std::string("cannot write ") + filename);
-    });
-}
-
-// gzip (level 1) of the file layout, as ffi/hyperloglog.rs writes it; freed with nodegraph_buffer_free
-const uint8_t* hll_to_buffer(const SourmashHyperLogLog* ptr, uintptr_t* size) {
-    return landing<const uint8_t*>([&]() -> const uint8_t* {
-        const std::string s = gzip_bytes(HLL(ptr)->serialize(), 1);
-        uint8_t* out = (uint8_t*)malloc(s.size() ? s.size() : 1);
-        memcpy(out, s.data(), s.size());
-        *size = s.size();
-        return out;
-    });
-}
-
-// ---- HyperLogLog extensions ----
-void smgpu_hll_flush(SourmashHyperLogLog* ptr) {
-    landing_void([&] { HLL(ptr); });
-}
-
-const uint8_t* smgpu_hll_registers(const SourmashHyperLogLog* ptr, uintptr_t* size) {
-    return landing<const uint8_t*>([&]() -> const uint8_t* {
-        const HyperLogLog* h = HLL(ptr);
-        *size = h->registers.size();
-        return h->registers.data();
-    });
-}
-
-uint64_t smgpu_hll_add_file(SourmashHyperLogLog* ptr, const char* path, uint64_t* n_records) {
-    uint64_t bases = 0;
-    landing_void([&] {
-        if (!path) throw err_internal("null path");
-        HyperLogLog* h = HLL(ptr);
-        std::lock_guard<std::recursive_mutex> sg(h->settle_mu);
-        if (h->ksize == 0) return;
-        check_dna_ksize((uint32_t)std::min<size_t>(h->ksize, UINT32_MAX));
-        uint64_t recs = 0;
-        hll_on_device(*h, [&](uint32_t* d_regs, hipStream_t) {
-            std::vector<KmerMinHash*> none;
-            const std::vector<HllSink> sinks{HllSink{(uint32_t)h->ksize, (uint32_t)h->p, d_regs}};
-            sketch_file_into(none, path, &recs, &bases, &sinks);
-        });
-        if (n_records) *n_records = recs;
-    });
-    return bases;
-}
-
-void smgpu_hll_add_device(SourmashHyperLogLog* ptr, const uint8_t* d_seq, uint64_t len, void* stream) {
-    landing_void([&] {
-        HyperLogLog* h = HLL(ptr);
-        std::lock_guard<std::recursive_mutex> sg(h->settle_mu);
-        if (h->ksize == 0 || len < h->ksize) return;
-        check_dna_ksize((uint32_t)std::min<size_t>(h->ksize, UINT32_MAX));
-        hll_on_device(*h, [&](uint32_t* d_regs, hipStream_t st) {
-            hipStream_t src = (hipStream_t)stream;
-            if (src != st) hip_check(hipStreamSynchronize(src), "sync");   // the caller's writes of d_seq are complete
-            hip_check(hll_dna_launch(d_seq, len, (uint32_t)h->ksize, (uint32_t)h->p, d_regs, st), "hll_dna");
-        });
-    });
-}
-
-void smgpu_hll_dna_raw(const uint8_t* d_seq, uint64_t len, uint32_t ksize, uint32_t p, uint32_t* d_regs, void* stream) {
-    landing_void([&] {
-        if (p < 4 || p > 18) throw Error(E_HLL_PRECISION_BOUNDS, "HLL precision must be between 4 and 18");
-        check_dna_ksize(ksize);
-        hip_check(hll_dna_launch(d_seq, len, ksize, p, d_regs, (hipStream_t)stream), "hll_dna");
-    });
-}
-
-uint32_t smgpu_hll_precision(const SourmashHyperLogLog* ptr) { return (uint32_t)HLLRAW(ptr)->p; }
-
-// =============================================================================================
-// Nodegraph (ffi/nodegraph.rs over sketch/nodegraph.rs): the host container is nodegraph_host.hpp; k-mers and large hash lists
-// reach the tables through nodegraph.hip.  The handle keeps a device mirror of the tables tagged with the host copy's content
-// generation: a bulk call uploads the tables only when the host copy changed since the last upload, runs its kernel and leaves
-// the result on the device; the first host read after that downloads the tables and adds the device's count of table-0 bits
-// turned on to `occupied`.  A run of bulk calls therefore costs one upload and one download.  add_sequence queues records as
-// the HLL path does.  Creating, count / get of single hashes, update, load / save never touch the device on their own.
-// =============================================================================================
-}  // extern "C"
-namespace {
-
-struct NgHandle {
-    Nodegraph g;
-    DevBuf d_words, d_tabs, d_occ;      // the device mirror (arena blocks)
-    std::vector<NgTable> tabs;          // its table descriptors, as uploaded
-    uint64_t dev_gen = ~0ull;           // the host generation the mirror holds (~0: none)
-    bool host_stale = false;            // the mirror holds bits (and an occupied delta) the host copy does not
-};
-
-inline NgHandle* NGRAW(SourmashNodegraph* p) { return reinterpret_cast<NgHandle*>(p); }
-inline NgHandle* NGRAW(const SourmashNodegraph* p) { return reinterpret_cast<NgHandle*>(const_cast<SourmashNodegraph*>(p)); }
-
-// the mirror, current: uploads the tables when the host copy changed since the last upload.  Context lock held by the caller.
-NgDev ng_mirror(NgHandle& h, hipStream_t st) {
-    Nodegraph& g = h.g;
-    if (h.dev_gen != g.gen) {
-        if (h.host_stale) throw err_internal("nodegraph mirror out of step");
-        h.tabs.clear();
-        for (size_t t = 0; t < g.n_tables(); ++t) {
-            g.check_size(t);
-            if (g.sizes[t] >> 63) throw Error(E_MSG, "Nodegraph tables of 2^63 bits and more are not supported on the GPU");
-            h.tabs.push_back(NgTable{g.sizes[t], ng_magic(g.sizes[t]), g.offs[t]});
-        }
-        const size_t nw = g.words.size();
-        h.d_words.reserve(std::max<size_t>(nw, 1) * 4, st);
-        h.d_tabs.reserve(std::max<size_t>(h.tabs.size(), 1) * sizeof(NgTable), st);
-        h.d_occ.reserve(8, st);
-        if (nw) hip_check(hipMemcpyAsync(h.d_words.p, g.words.data(), nw * 4, hipMemcpyHostToDevice, st), "H2D");
-        if (!h.tabs.empty())
-            hip_check(hipMemcpyAsync(h.d_tabs.p, h.tabs.data(), h.tabs.size() * sizeof(NgTable), hipMemcpyHostToDevice, st), "H2D");
-        hip_check(hipMemsetAsync(h.d_occ.p, 0, 8, st), "memset");
-        hip_check(hipStreamSynchronize(st), "sync");
-        h.dev_gen = g.gen;
-    }
-    NgDev d;
-    d.tabs = h.d_tabs.as<NgTable>();
-    d.n_tables = (uint32_t)g.n_tables();
-    d.words = h.d_words.as<uint32_t>();
-    d.n_words = g.words.size();
-    d.t0_words = g.n_tables() ? Nodegraph::n_words(g.sizes[0]) : 0;
-    d.occ = h.d_occ.as<unsigned long long>();
-    return d;
-}
-
-// Device work on the mirror, `work(dev, stream)`, then a synchronisation.  writes: the work sets bits (the host copy is stale
-// from here on); otherwise it only reads them.
-template <class F>
-void ng_on_device(NgHandle& h, bool writes, F&& work) {
-    if (h.g.n_tables() > UINT32_MAX) throw err_internal("too many Nodegraph tables");
-    DeviceCtx& ctx = DeviceCtx::get();
-    std::lock_guard<std::recursive_mutex> g(ctx.mutex());
-    hipStream_t st = ctx.stream();
-    const NgDev d = ng_mirror(h, st);
-    if (writes) h.host_stale = true;    // (a failed launch may have set some bits: they and their count are read back alike)
-    work(d, st);
-    hip_check(hipStreamSynchronize(st), "sync");
-}
-
-// Hash the queued records into the mirror.  Consumed only once the tables hold them: if the device work throws, the queue
-// stays and the error reaches the caller; counting it again later is harmless (bits only turn on, and a bit already on is not
-// counted again).
-void ng_settle(NgHandle& h, bool streaming = false) {
-    Nodegraph& g = h.g;
-    std::lock_guard<std::recursive_mutex> sg(g.settle_mu);
-    if (g.pending.empty()) return;
-    std::string& q = g.pending;
-    ng_on_device(h, true, [&](const NgDev& d, hipStream_t st) {
-        AsyncBuf d_seq(q.size() + 64, st);
-        hip_check(hipMemcpyAsync(d_seq.p, q.data(), q.size(), hipMemcpyHostToDevice, st), "H2D");
-        hip_check(nodegraph_dna_launch(d_seq.as<uint8_t>(), q.size(), (uint32_t)g.ksize, d, st), "nodegraph_dna");
-        hip_check(hipStreamSynchronize(st), "sync");    // d_seq is released at the end of this scope
-    });
-    if (streaming || q.capacity() <= ((size_t)1 << 20)) q.clear();
-    else std::string().swap(q);
-}
-
-// The host copy, current: queued records counted, device bits and the occupied delta read back.  Every host read and every
-// host change goes through here first (under the handle's lock).
-Nodegraph& ng_host(NgHandle& h) {
-    ng_settle(h);
-    if (!h.host_stale) return h.g;
-    Nodegraph& g = h.g;
-    DeviceCtx& ctx = DeviceCtx::get();
-    std::lock_guard<std::recursive_mutex> lk(ctx.mutex());
-    hipStream_t st = ctx.stream();
-    unsigned long long delta = 0;
-    if (!g.words.empty())
-        hip_check(hipMemcpyAsync(g.words.data(), h.d_words.p, g.words.size() * 4, hipMemcpyDeviceToHost, st), "D2H");
-    hip_check(hipMemcpyAsync(&delta, h.d_occ.p, 8, hipMemcpyDeviceToHost, st), "D2H");
-    hip_check(hipMemsetAsync(h.d_occ.p, 0, 8, st), "memset");
-    hip_check(hipStreamSynchronize(st), "sync");
-    g.occupied += delta;
-    h.host_stale = false;               // the mirror equals the host copy again (same generation)
-    return g;
-}
-
-// k-mers reach the tables only through the kernel: k = 1 .. 32
-void ng_check_bulk_k(const Nodegraph& g) {
-    if (g.ksize == 0 || g.ksize > NG_MAX_K)
-        throw Error(E_MISMATCH_KSIZES, "Nodegraph k-mer input takes ksize 1 .. 32 (khmer's limit); this graph has ksize " +
-                                           std::to_string(g.ksize));
-}
-
-// add_sequence into the queue: force == false raises InvalidDNA naming the first bad k-mer after the k-mers before it were
-// queued (hll_add_sequence_impl's rule); force == true leaves bad k-mers to the kernel, which skips them
-void ng_add_sequence_impl(NgHandle& h, const uint8_t* seq, size_t len, bool force) {
-    Nodegraph& g = h.g;
-    ng_check_bulk_k(g);
-    const size_t k = g.ksize;
-    if (len < k) return;
-    (void)DeviceCtx::get();
-    size_t use_len = len;
-    bool raise = false;
-    size_t bad_kmer = 0;
-    if (!force) {
-        const size_t p = first_invalid_byte(seq, len);
-        if (p != SIZE_MAX) {
-            bad_kmer = p + 1 >= k ? p + 1 - k : 0;
-            if (bad_kmer < len - k + 1) {
-                raise = true;
-                use_len = bad_kmer + k - 1;
-            }
-        }
-    }
-    if (use_len >= k) {
-        std::lock_guard<std::recursive_mutex> sg(g.settle_mu);
-        g.pending.append((const char*)seq, use_len);
-        g.pending.push_back('\n');
-        if (g.pending.size() >= PENDING_FLUSH_BYTES) ng_settle(h, true);
-    }
-    if (raise) throw err_invalid_dna(upper_ascii(seq + bad_kmer, k));
-}
-
-constexpr size_t NG_DEVICE_FROM = (size_t)1 << 16;   // sketches of this many hashes and more go through the hash kernels
-
-// Update<Nodegraph> for KmerMinHash: count every hash (small sketches on the host, large ones through the hash kernel)
-void ng_add_hashes(NgHandle& h, const std::vector<uint64_t>& hs) {
-    if (hs.size() < NG_DEVICE_FROM) {
-        Nodegraph& g = ng_host(h);
-        for (uint64_t x : hs) g.count(x);
-        return;
-    }
-    ng_settle(h);
-    ng_on_device(h, true, [&](const NgDev& d, hipStream_t st) {
-        AsyncBuf d_h(hs.size() * 8, st);
-        hip_check(hipMemcpyAsync(d_h.p, hs.data(), hs.size() * 8, hipMemcpyHostToDevice, st), "H2D");
-        hip_check(nodegraph_hashes_launch(d_h.as<uint64_t>(), hs.size(), d, st), "nodegraph_hashes");
-        hip_check(hipStreamSynchronize(st), "sync");
-    });
-}
-
-uint64_t ng_matches_hashes(NgHandle& h, const std::vector<uint64_t>& hs) {
-    if (hs.size() < NG_DEVICE_FROM) {
-        const Nodegraph& g = ng_host(h);
-        uint64_t n = 0;
-        for (uint64_t x : hs) n += g.get(x);
-        return n;
-    }
-    ng_settle(h);
-    uint64_t n = 0;
-    ng_on_device(h, false, [&](const NgDev& d, hipStream_t st) {
-        const uint64_t off[2] = {0, (uint64_t)hs.size()};
-        AsyncBuf d_h(hs.size() * 8 + 16, st), d_out(8, st);
-        uint64_t* d_off = d_h.as<uint64_t>() + hs.size();
-        hip_check(hipMemcpyAsync(d_h.p, hs.data(), hs.size() * 8, hipMemcpyHostToDevice, st), "H2D");
-        hip_check(hipMemcpyAsync(d_off, off, 16, hipMemcpyHostToDevice, st), "H2D");
-        hip_check(nodegraph_matches_launch(d_h.as<uint64_t>(), d_off, 1, d, d_out.as<uint64_t>(), st), "nodegraph_matches");
-        hip_check(hipMemcpyAsync(&n, d_out.p, 8, hipMemcpyDeviceToHost, st), "D2H");
-        hip_check(hipStreamSynchronize(st), "sync");
-    });
-    return n;
-}
-
-NgHandle* ng_read_plain(const std::string& raw) {
-    const std::string text = maybe_gunzip(raw.data(), raw.size());
-    std::unique_ptr<NgHandle> h(new NgHandle());
-    h->g.parse((const uint8_t*)text.data(), text.size());
-    return h.release();
-}
-
-}  // namespace
-extern "C" {
-
-SourmashNodegraph* nodegraph_new(void) { return reinterpret_cast<SourmashNodegraph*>(new NgHandle()); }
-void nodegraph_free(SourmashNodegraph* ptr) { delete NGRAW(ptr); }
-
-SourmashNodegraph* nodegraph_with_tables(uintptr_t ksize, uintptr_t starting_size, uintptr_t n_tables) {
-    return landing<SourmashNodegraph*>([&]() -> SourmashNodegraph* {
-        std::unique_ptr<NgHandle> h(new NgHandle());
-        h->g.with_tables(ksize, starting_size, n_tables);
-        return reinterpret_cast<SourmashNodegraph*>(h.release());
-    });
-}
-
-bool nodegraph_count(SourmashNodegraph* ptr, uint64_t h) {
-    return landing<bool>([&] {
-        NgHandle* n = NGRAW(ptr);
-        std::lock_guard<std::recursive_mutex> sg(n->g.settle_mu);
-        return ng_host(*n).count(h);
-    });
-}
-bool nodegraph_count_kmer(SourmashNodegraph* ptr, const char* kmer) {
-    return landing<bool>([&] {
-        if (!kmer) throw err_internal("null k-mer");
-        const uint64_t hv = ng_twobit_hash((const uint8_t*)kmer, strlen(kmer));
-        NgHandle* n = NGRAW(ptr);
-        std::lock_guard<std::recursive_mutex> sg(n->g.settle_mu);
-        return ng_host(*n).count(hv);
-    });
-}
-uintptr_t nodegraph_get(const SourmashNodegraph* ptr, uint64_t h) {
-    return landing<uintptr_t>([&] {
-        NgHandle* n = NGRAW(ptr);
-        std::lock_guard<std::recursive_mutex> sg(n->g.settle_mu);
-        return (uintptr_t)ng_host(*n).get(h);
-    });
-}
-uintptr_t nodegraph_get_kmer(const SourmashNodegraph* ptr, const char* kmer) {
-    return landing<uintptr_t>([&] {
-        if (!kmer) throw err_internal("null k-mer");
-        const uint64_t hv = ng_twobit_hash((const uint8_t*)kmer, strlen(kmer));
-        NgHandle* n = NGRAW(ptr);
-        std::lock_guard<std::recursive_mutex> sg(n->g.settle_mu);
-        return (uintptr_t)ng_host(*n).get(hv);
-    });
-}
-
-double nodegraph_expected_collisions(const SourmashNodegraph* ptr) {
-    return landing<double>([&] {
-        NgHandle* n = NGRAW(ptr);
-        std::lock_guard<std::recursive_mutex> sg(n->g.settle_mu);
-        return ng_host(*n).expected_collisions();
-    });
-}
-uintptr_t nodegraph_ksize(const SourmashNodegraph* ptr) { return NGRAW(ptr)->g.ksize; }
-uintptr_t nodegraph_ntables(const SourmashNodegraph* ptr) { return NGRAW(ptr)->g.n_tables(); }
-uintptr_t nodegraph_noccupied(const SourmashNodegraph* ptr) {
-    return landing<uintptr_t>([&] {
-        NgHandle* n = NGRAW(ptr);
-        std::lock_guard<std::recursive_mutex> sg(n->g.settle_mu);
-        return (uintptr_t)ng_host(*n).occupied;
-    });
-}
-// freed with kmerminhash_slice_free (the reference's Python does so)
-const uint64_t* nodegraph_hashsizes(const SourmashNodegraph* ptr, uintptr_t* size) {
-    const std::vector<uint64_t>& s = NGRAW(ptr)->g.sizes;
-    uint64_t* out = (uint64_t*)malloc(s.empty() ? 8 : s.size() * 8);
-    if (!s.empty()) memcpy(out, s.data(), s.size() * 8);
-    *size = s.size();
-    return out;
-}
-
-uintptr_t nodegraph_matches(const SourmashNodegraph* ptr, const SourmashKmerMinHash* mh_ptr) {
-    return landing<uintptr_t>([&] {
-        NgHandle* n = NGRAW(ptr);
-        const KmerMinHash* mh = MH(mh_ptr);
-        std::lock_guard<std::recursive_mutex> sg(n->g.settle_mu);
-        return (uintptr_t)ng_matches_hashes(*n, mh->mins);
-    });
-}
-
-void nodegraph_update(SourmashNodegraph* ptr, const SourmashNodegraph* optr) {
-    landing_void([&] {
-        NgHandle* a = NGRAW(ptr);
-        NgHandle* b = NGRAW(optr);
-        std::lock_guard<std::recursive_mutex> sa(a->g.settle_mu);
-        std::lock_guard<std::recursive_mutex> sb(b->g.settle_mu);
-        const Nodegraph& other = ng_host(*b);
-        ng_host(*a).update(other);
-    });
-}
-void nodegraph_update_mh(SourmashNodegraph* ptr, const SourmashKmerMinHash* optr) {
-    landing_void([&] {
-        NgHandle* n = NGRAW(ptr);
-        const KmerMinHash* mh = MH(optr);
-        std::lock_guard<std::recursive_mutex> sg(n->g.settle_mu);
-        ng_add_hashes(*n, mh->mins);
-    });
-}
-
-SourmashNodegraph* nodegraph_from_path(const char* filename) {
-    return landing<SourmashNodegraph*>([&]() -> SourmashNodegraph* {
-        if (!filename) throw err_internal("null filename");
-        std::ifstream f(filename, std::ios::binary);
-        if (!f) throw Error(E_IO, std::string("No such file or directory: ") + filename);
-        std::stringstream ss;
-        ss << f.rdbuf();
-        return reinterpret_cast<SourmashNodegraph*>(ng_read_plain(ss.str()));
-    });
-}
-SourmashNodegraph* nodegraph_from_buffer(const char* ptr, uintptr_t insize) {
-    return landing<SourmashNodegraph*>([&]() -> SourmashNodegraph* {
-        if (!ptr && insize) throw err_internal("null buffer");
-        return reinterpret_cast<SourmashNodegraph*>(ng_read_plain(std::string(ptr ? ptr : "", insize)));
-    });
-}
-
-// always the plain layout (nodegraph.rs `save`)
-void nodegraph_save(const SourmashNodegraph* ptr, const char* filename) {
-    landing_void([&] {
-        if (!filename) throw err_internal("null filename");
-        NgHandle* n = NGRAW(ptr);
-        std::lock_guard<std::recursive_mutex> sg(n->g.settle_mu);
-        const std::string s = ng_host(*n).serialize();
-        std::ofstream f(filename, std::ios::binary | std::ios::trunc);
-        if (!f) throw Error(E_IO, std::string("cannot create ") + filename);
-        f.write(s.data(), (std::streamsize)s.size());
-        if (!f) throw Error(E_IO, std::string("cannot write ") + filename);
-    });
-}
-
-// compression 0: the plain layout; 1 .. 9: gzip at that level (above 9: 9).  Freed with nodegraph_buffer_free.
-const uint8_t* nodegraph_to_buffer(const SourmashNodegraph* ptr, uint8_t compression, uintptr_t* size) {
-    return landing<const uint8_t*>([&]() -> const uint8_t* {
-        NgHandle* n = NGRAW(ptr);
-        std::lock_guard<std::recursive_mutex> sg(n->g.settle_mu);
-        std::string s = ng_host(*n).serialize();
-        if (compression > 0) s = gzip_bytes(s, compression > 9 ? 9 : compression);
-        uint8_t* out = (uint8_t*)malloc(s.size() ? s.size() : 1);
-        if (!out) throw std::bad_alloc();
-        memcpy(out, s.data(), s.size());
-        *size = s.size();
-        return out;
-    });
-}
-
-// ---- Nodegraph extensions ----
-void smgpu_nodegraph_add_sequence(SourmashNodegraph* ptr, const char* sequence, uintptr_t insize, bool force) {
-    landing_void([&] {
-        if (!sequence && insize) throw err_internal("null sequence");
-        ng_add_sequence_impl(*NGRAW(ptr), (const uint8_t*)sequence, insize, force);
-    });
-}
-
-void smgpu_nodegraph_flush(SourmashNodegraph* ptr) {
-    landing_void([&] { ng_settle(*NGRAW(ptr)); });
-}
-
-uint64_t smgpu_nodegraph_add_file(SourmashNodegraph* ptr, const char* path, uint64_t* n_records) {
-    uint64_t bases = 0;
-    landing_void([&] {
-        if (!path) throw err_internal("null path");
-        NgHandle* n = NGRAW(ptr);
-        std::lock_guard<std::recursive_mutex> sg(n->g.settle_mu);
-        ng_check_bulk_k(n->g);
-        ng_settle(*n);
-        uint64_t recs = 0;
-        ng_on_device(*n, true, [&](const NgDev& d, hipStream_t) {
-            std::vector<KmerMinHash*> none;
-            const std::vector<NgSink> sinks{NgSink{(uint32_t)n->g.ksize, d}};
-            sketch_file_into(none, path, &recs, &bases, nullptr, &sinks);
-        });
-        if (n_records) *n_records = recs;
-    });
-    return bases;
-}
-
-void smgpu_nodegraph_add_device(SourmashNodegraph* ptr, const uint8_t* d_seq, uint64_t len, void* stream) {
-    landing_void([&] {
-        NgHandle* n = NGRAW(ptr);
-        std::lock_guard<std::recursive_mutex> sg(n->g.settle_mu);
-        ng_check_bulk_k(n->g);
-        if (len < n->g.ksize) return;
-        ng_settle(*n);
-        ng_on_device(*n, true, [&](const NgDev& d, hipStream_t st) {
-            hipStream_t src = (hipStream_t)stream;
-            if (src != st) hip_check(hipStreamSynchronize(src), "sync");   // the caller's writes of d_seq are complete
-            hip_check(nodegraph_dna_launch(d_seq, len, (uint32_t)n->g.ksize, d, st), "nodegraph_dna");
-        });
-    });
-}
-
-// every hash of every row of a SketchSet, in one launch over the resident CSR
-void smgpu_nodegraph_update_sketchset(SourmashNodegraph* ptr, const SmgpuSketchSet* set) {
-    landing_void([&] {
-        NgHandle* n = NGRAW(ptr);
-        const SketchSet* s = reinterpret_cast<const SketchSet*>(set);
-        std::lock_guard<std::recursive_mutex> sg(n->g.settle_mu);
-        if (s->total == 0) return;
-        ng_settle(*n);
-        ng_on_device(*n, true, [&](const NgDev& d, hipStream_t st) {
-            hip_check(nodegraph_hashes_launch(s->hashes.as<uint64_t>(), s->total, d, st), "nodegraph_hashes");
-        });
-    });
-}
-
-// out[r] = nodegraph_matches of row r, for every row of a SketchSet (one read-only launch)
-void smgpu_nodegraph_matches_sketchset(const SourmashNodegraph* ptr, const SmgpuSketchSet* set, uint64_t* out) {
-    landing_void([&] {
-        NgHandle* n = NGRAW(ptr);
-        const SketchSet* s = reinterpret_cast<const SketchSet*>(set);
-        std::lock_guard<std::recursive_mutex> sg(n->g.settle_mu);
-        if (s->n == 0) return;
-        if (!out) throw err_internal("null output");
-        ng_settle(*n);
-        ng_on_device(*n, false, [&](const NgDev& d, hipStream_t st) {
-            AsyncBuf d_out(s->n * 8, st);
-            hip_check(nodegraph_matches_launch(s->hashes.as<uint64_t>(), s->offsets.as<uint64_t>(), s->n, d, d_out.as<uint64_t>(), st),
-                      "nodegraph_matches");
-            hip_check(hipMemcpyAsync(out, d_out.p, s->n * 8, hipMemcpyDeviceToHost, st), "D2H");
-            hip_check(hipStreamSynchronize(st), "sync");
-        });
-    });
-}
-
-double smgpu_nodegraph_similarity(const SourmashNodegraph* ptr, const SourmashNodegraph* optr) {
-    return landing<double>([&] {
-        NgHandle* a = NGRAW(ptr);
-        NgHandle* b = NGRAW(optr);
-        std::lock_guard<std::recursive_mutex> sa(a->g.settle_mu);
-        std::lock_guard<std::recursive_mutex> sb(b->g.settle_mu);
-        const Nodegraph& other = ng_host(*b);
-        return ng_host(*a).similarity(other);
-    });
-}
-double smgpu_nodegraph_containment(const SourmashNodegraph* ptr, const SourmashNodegraph* optr) {
-    return landing<double>([&] {
-        NgHandle* a = NGRAW(ptr);
-        NgHandle* b = NGRAW(optr);
-        std::lock_guard<std::recursive_mutex> sa(a->g.settle_mu);
-        std::lock_guard<std::recursive_mutex> sb(b->g.settle_mu);
-        const Nodegraph& other = ng_host(*b);
-        return ng_host(*a).containment(other);
-    });
-}
-
-uintptr_t smgpu_nodegraph_table_sizes(uintptr_t starting_size, uintptr_t n_tables, uint64_t* out, uintptr_t cap) {
-    return landing<uintptr_t>([&] {
-        const std::vector<uint64_t> s = ng_table_sizes(starting_size, n_tables);
-        for (size_t i = 0; i < s.size() && i < cap; ++i) out[i] = s[i];
-        return (uintptr_t)s.size();
-    });
 }
 
 }  // extern "C"

@@ -1,0 +1,116 @@
+// capi_common.hpp -- what the units of the extern "C" surface (capi.cpp, capi_hll.cpp, capi_nodegraph.cpp; include/sourmash_amd.h)
+// share: the thread's error slot and the landing pad, the handle casts, small output helpers and the device-resident sketch collection.  Internal to the
+// library: everything here is hidden, and state lives in inline variables / inline functions so that the library has ONE of each.
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <stdlib.h>
+#include <string.h>
+#include <mutex>
+#include <string>
+#include <vector>
+#include "../../include/sourmash_amd.h"
+#include "collection.hpp"
+#include "device_ctx.hpp"
+#include "hostxfer.hpp"
+#include "record_queue.hpp"
+#include "signature_host.hpp"
+
+#pragma GCC visibility push(hidden)
+namespace smg {
+
+// ---------------------------------------------------------------------------------------------
+// thread-local last error + landing pad (ffi/utils.rs:17-19,58-83,195-207)
+// ---------------------------------------------------------------------------------------------
+inline thread_local uint32_t g_err_code = 0;
+inline thread_local std::string g_err_msg;
+
+inline void set_error(uint32_t code, const std::string& msg) { g_err_code = code; g_err_msg = msg; }
+
+template <class R, class F>
+R landing(F&& f) {
+    try {
+        return f();
+    } catch (const Error& e) {
+        set_error(e.code, e.what());
+    } catch (const std::bad_alloc&) {
+        set_error(E_PANIC, "sourmash panicked: out of memory");
+    } catch (const std::exception& e) {
+        set_error(E_PANIC, std::string("sourmash panicked: ") + e.what());
+    } catch (...) {
+        set_error(E_PANIC, "sourmash panicked: unknown exception");
+    }
+    return R{};
+}
+template <class F>
+void landing_void(F&& f) {
+    landing<int>([&]() { f(); return 0; });
+}
+
+inline SourmashStr make_str(const std::string& s) {
+    SourmashStr out;
+    out.data = (char*)malloc(s.size() + 1);
+    memcpy(out.data, s.data(), s.size());
+    out.data[s.size()] = 0;
+    out.len = s.size();
+    out.owned = true;
+    return out;
+}
+
+// ---- handles ---------------------------------------------------------------------------------------------------
+// hash the records add_sequence queued on the sketch (capi.cpp; record_queue.hpp).  Every accessor goes through MH / SIG,
+// which settle first: results are those of immediate hashing, since adding hashes to a sketch commutes (set union, counts add,
+// bottom-k keeps the smallest) and everything that does not commute with it settles first.
+void settle(KmerMinHash& mh, bool streaming = false);
+
+inline KmerMinHash* RAW(SourmashKmerMinHash* p) { return reinterpret_cast<KmerMinHash*>(p); }
+inline const KmerMinHash* RAW(const SourmashKmerMinHash* p) { return reinterpret_cast<const KmerMinHash*>(p); }
+inline KmerMinHash* settled(KmerMinHash* m) {
+    if (m && !m->pending.empty()) {
+        // accessors without a landing pad cannot throw across the C boundary: the failure is left in the thread's error slot
+        try { settle(*m); }
+        catch (const Error& e) { set_error(e.code, e.what()); }
+        catch (const std::exception& e) { set_error(E_PANIC, std::string("sourmash panicked: ") + e.what()); }
+    }
+    return m;
+}
+inline KmerMinHash* MH(SourmashKmerMinHash* p) { return settled(reinterpret_cast<KmerMinHash*>(p)); }
+inline const KmerMinHash* MH(const SourmashKmerMinHash* p) { return settled(const_cast<KmerMinHash*>(reinterpret_cast<const KmerMinHash*>(p))); }
+inline Signature* SIGRAW(SourmashSignature* p) { return reinterpret_cast<Signature*>(p); }
+inline Signature* SIG(SourmashSignature* p) {
+    Signature* s = reinterpret_cast<Signature*>(p);
+    if (s) for (auto& mh : s->sketches) settled(&mh);
+    return s;
+}
+inline const Signature* SIG(const SourmashSignature* p) { return SIG(const_cast<SourmashSignature*>(p)); }
+inline ComputeParameters* CP(SourmashComputeParameters* p) { return reinterpret_cast<ComputeParameters*>(p); }
+inline const ComputeParameters* CP(const SourmashComputeParameters* p) { return reinterpret_cast<const ComputeParameters*>(p); }
+
+inline uint64_t* slice_out(const std::vector<uint64_t>& v, uintptr_t* size) {
+    *size = v.size();
+    uint64_t* p = (uint64_t*)malloc((v.size() ? v.size() : 1) * sizeof(uint64_t));
+    if (v.size()) memcpy(p, v.data(), v.size() * sizeof(uint64_t));
+    return p;
+}
+
+inline std::string upper_ascii(const uint8_t* p, size_t n) {
+    std::string s((const char*)p, n);
+    for (auto& c : s) if (c >= 'a' && c <= 'z') c = (char)(c - 32);
+    return s;
+}
+
+inline uint64_t keep_threshold(const KmerMinHash& mh) { return mh.max_hash ? mh.max_hash : ~0ull; }
+
+// ---- device-resident sketch collections (capi.cpp makes them; the Nodegraph unit reads them)
+struct SketchSet {
+    DevBuf hashes, offsets;
+    uint64_t n = 0, total = 0;
+    // filled by smgpu_sketchset_load (empty for sets built from sketch handles)
+    std::vector<uint64_t> host_offsets;
+    std::vector<ManifestRow> rows;
+    uint32_t ksize = 0, hash_function = HF_DNA;
+    uint64_t seed = 42, max_hash = 0, num = 0, skipped = 0;
+    // (the device blocks are arena blocks and go back to the arena with the DevBufs: no hipFree, which would synchronise the device)
+};
+
+}  // namespace smg
+#pragma GCC visibility pop

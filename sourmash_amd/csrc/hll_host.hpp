@@ -8,7 +8,7 @@
 // reference, with the same libm calls, so they return the same f64 bits; every f64 -> size_t conversion saturates (negative
 // or NaN -> 0, too large -> SIZE_MAX), which is what Rust's `as usize` does and what a plain C++ cast leaves undefined.
 //
-// Nothing here touches the device: k-mers are hashed into the registers by hll.hip (capi.cpp queues the records first).
+// Nothing here touches the device: k-mers are hashed into the registers by hll.hip (capi_hll.cpp queues the records first).
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -127,7 +127,7 @@ inline JointMle hll_joint_mle(const uint8_t* k1, size_t n1, const uint8_t* k2, s
 struct HyperLogLog {
     std::vector<uint8_t> registers;
     size_t p = 0, q = 0, ksize = 0;
-    // DNA records handed to add_sequence and not hashed yet, each followed by a '\n' (no k-mer spans it): capi.cpp runs them
+    // DNA records handed to add_sequence and not hashed yet, each followed by a '\n' (no k-mer spans it): capi_hll.cpp runs them
     // through the HLL kernel in one launch when the queue is large or when anything reads the registers
     std::string pending;
     std::recursive_mutex settle_mu;     // settling a handle's queue is serialised (two readers on two threads)

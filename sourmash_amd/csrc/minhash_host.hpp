@@ -44,7 +44,7 @@ struct KmerMinHash {
     std::vector<uint64_t> mins;
     std::vector<uint64_t> abunds;   // parallel to mins iff track_abundance
     // DNA records handed to add_sequence and not hashed yet (each followed by a '\n', which no k-mer may span): the C-ABI
-    // layer runs them through the sketch kernel in one launch when the state is next looked at (capi.cpp: settle)
+    // layer runs them through the sketch kernel in one launch when the state is next looked at (capi.cpp: settle; record_queue.hpp)
     mutable std::string pending;
     // Content generation: a process-wide unique number taken at construction and again by every mutator.  Two objects with
     // the same generation hold the same hashes (a copy keeps it until either side changes), which is what lets the device

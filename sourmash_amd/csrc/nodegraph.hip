@@ -3,7 +3,7 @@
 // A graph is n tables of prime sizes; a hash h sets bit h mod size_t of every table t.  k-mers are hashed with khmer's two-bit
 // code (A 0, T 1, C 2, G 3): h = min(forward word, reverse-complement word), k <= 32.  The device mirror of a graph is one
 // u32 word array (all tables, fixedbitset layout: bit b = bit b & 31 of word b >> 5) plus a table of {size, reciprocal,
-// first word} (NgTable) and a u64 counter of table-0 bits turned on (capi.cpp keeps it resident and adds the counter to the
+// first word} (NgTable) and a u64 counter of table-0 bits turned on (capi_nodegraph.cpp keeps it resident and adds the counter to the
 // host's `occupied` when it reads the tables back).
 //
 //   h mod size: ng_mod (nodegraph_core.hpp), a mulhi quotient estimate by the precomputed floor((2^64 - 1) / size) and at

@@ -9,7 +9,7 @@
 // the file stores size / 8 + 1 bytes of each table, and this is the number of words those bytes need (never fewer than
 // ceil(size / 32)).
 //
-// Nothing here touches the device: capi.cpp keeps the device mirror and runs the kernels of nodegraph.hip.
+// Nothing here touches the device: capi_nodegraph.cpp keeps the device mirror and runs the kernels of nodegraph.hip.
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -93,10 +93,10 @@ struct Nodegraph {
     std::vector<uint32_t> words;
     size_t ksize = 0;
     uint64_t occupied = 0;
-    // content generation: bumped by every host change of the tables or `occupied` (capi.cpp uploads the device mirror only
+    // content generation: bumped by every host change of the tables or `occupied` (capi_nodegraph.cpp uploads the device mirror only
     // when it holds an older generation)
     uint64_t gen = 0;
-    // DNA records handed to add_sequence and not counted yet, each followed by a '\n' (no k-mer spans it): capi.cpp runs them
+    // DNA records handed to add_sequence and not counted yet, each followed by a '\n' (no k-mer spans it): capi_nodegraph.cpp runs them
     // through the k-mer kernel in one launch when the queue is large or when anything reads the tables
     std::string pending;
     std::recursive_mutex settle_mu;

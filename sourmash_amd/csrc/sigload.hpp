@@ -14,6 +14,7 @@
 #pragma once
 #include "collection.hpp"
 #include "gunzip.hpp"
+#include "ingest.hpp"   // PinnedBuf
 #include "sigjson_api.hpp"
 
 namespace smg {

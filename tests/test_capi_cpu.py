@@ -34,6 +34,22 @@ def test_every_declared_symbol_is_exported(sm):
         assert name in funcs
 
 
+def test_every_exported_c_symbol_is_declared(sm):
+    """The reverse: the strong, unmangled functions in the library's dynamic table are the header's and nothing else (a helper of
+    the C-ABI units with external linkage would show up here under a name as plain as read_whole_file)."""
+    import shutil
+    import subprocess
+    from sourmash_amd._lowlevel import LIBPATH, parse_header
+    if shutil.which("nm") is None:
+        pytest.skip("nm is not on the path")
+    funcs, _ = parse_header()
+    out = subprocess.check_output(["nm", "-D", "--defined-only", LIBPATH], text=True)
+    exported = [f[2] for f in (line.split() for line in out.splitlines()) if len(f) == 3 and f[1] == "T"]
+    assert len(exported) > 100
+    extra = sorted(n for n in exported if not n.startswith(("_Z", "__hip_", "_init", "_fini")) and n not in funcs)
+    assert not extra, extra
+
+
 def test_error_codes_match_reference_header(sm):
     # include/sourmash.h:19-53 values are ABI; exceptions map like src/sourmash/exceptions.py:136-153
     from sourmash_amd.exceptions import exceptions_by_code

@@ -1,7 +1,7 @@
 """Host pieces of the per-record path that need no GPU: the C method behind MinHash.add_sequence (csrc/fastcall.c) --
 that it is built, bound to the loaded library, parses arguments like the Python signature it replaces and routes the
 library's error through the usual exception classes -- and the vectorised validity scan that decides where
-add_sequence(force=False) must raise (capi.cpp: first_invalid_byte; encodings.rs:370-377 of the reference)."""
+add_sequence(force=False) must raise (csrc/record_queue.hpp: first_invalid_byte; encodings.rs:370-377 of the reference)."""
 import ctypes as C
 import random
 

@@ -1,4 +1,5 @@
-"""The per-record API with deferred hashing (capi.cpp: add_sequence queues, accessors settle): the observable behaviour
+"""The per-record API with deferred hashing (csrc/capi.cpp: add_sequence queues, accessors settle; the queue's rule shared
+with HyperLogLog and Nodegraph: csrc/record_queue.hpp): the observable behaviour
 must stay that of the reference's streaming add_sequence (src/core/src/signature.rs:38-58) -- same sketch whatever
 the interleaving with other calls, InvalidDNA raised by the offending call after the k-mers in front of the bad one were
 added (tests/test_minhash.py:711-719,2594-2602 of the reference).  Run with -m gpu."""
@@ -239,3 +240,94 @@ def test_pending_sketches_straight_into_sketchset_and_counter(sm):
     t.join(120)
     assert not t.is_alive(), "deadlock: SketchSet / counter construction from a sketch with queued records"
     assert result["got"] == result["want"] and max(result["want"]) > 0
+
+
+# ---- the rule the three families share (csrc/record_queue.hpp) -------------------------------------------------------------------
+def _edge_records(k):
+    "-> [(label, record)]: mixed-case records at the edges of the valid-prefix rule for ksize k"
+    rng = np.random.default_rng(k)
+    def dna(n):
+        return bytes(rng.choice(np.frombuffer(b"ACGTacgt", dtype=np.uint8), n)).decode()
+    length = 3 * k + 5
+    cases = [("len == k", dna(k)), ("len == k - 1", dna(k - 2) + "N")]
+    for label, p in (("0", 0), ("k - 1", k - 1), ("k", k), ("len - k", length - k), ("len - 1", length - 1)):
+        r = dna(length)
+        cases.append(("bad byte at " + label, r[:p] + "n" + r[p + 1:]))
+    assert len({r for _, r in cases}) == 7 and all(len(r) <= 200 for _, r in cases)
+    return cases
+
+
+def _edge_expectation(rec, k):
+    "-> (k-mer the error names or None, the prefix whose k-mers are added) by the reference's streaming walk"
+    for i in range(len(rec) - k + 1):
+        if set(rec[i:i + k].upper()) - set("ACGT"):
+            return rec[i:i + k].upper(), rec[:i + k - 1] if i else ""
+    return None, rec
+
+
+@pytest.mark.parametrize("k", [21, 31, 32])
+def test_three_families_share_the_edge_rule(sm, k):
+    """MinHash, HyperLogLog and Nodegraph fed the same edge records behind a good record (so that the queue's separator is
+    exercised): the same exception naming the same k-mer, the state of the valid prefix by each family's oracle, and nothing
+    more settled by a second read.  k = 32 is Nodegraph's upper end; the other two run at 21 and 31."""
+    import test_gpu_hll as th
+    import test_gpu_nodegraph as tn
+    lead = _records(1, 2 * k, seed=k)[0]
+    p = 10
+
+    class MinHashCase:
+        def __init__(self):
+            # with abundances: a record hashed twice (MinHash's queue is consumed whatever happens, record_queue.hpp) would show
+            self.obj = sm.MinHash(0, k, scaled=1, track_abundance=True)
+            self.want = oracle.OracleMinHash(0, k, scaled=1, track_abundance=True)
+        def expect(self, rec):
+            self.want.add_sequence(rec.encode(), force=True)
+        def read(self):
+            got = dict(self.obj.hashes)
+            assert _pending(self.obj) == 0
+            return got
+        def check(self):
+            first = self.read()
+            assert first == dict(zip(self.want.mins.tolist(), self.want.abunds.tolist()))
+            assert self.read() == first
+
+    class HllCase:
+        def __init__(self):
+            self.obj = th._hll(sm, k, p)
+            self.recs = []
+        def expect(self, rec):
+            self.recs.append(rec.encode())
+        def check(self):
+            first = th._regs(self.obj).copy()
+            assert np.array_equal(first, th._want(self.recs, k, p))
+            assert np.array_equal(th._regs(self.obj), first)
+
+    class NodegraphCase:
+        def __init__(self):
+            self.obj = sm.Nodegraph(k, 1000, 3)
+            self.recs = []
+        def expect(self, rec):
+            self.recs.append(rec.encode())
+        def check(self):
+            tn.assert_model(self.obj, tn.all_hashes(self.recs, k))
+            first = (tn.graph_tables(self.obj), self.obj.n_occupied())
+            assert (tn.graph_tables(self.obj), self.obj.n_occupied()) == first
+
+    families = [NodegraphCase] if k == 32 else [MinHashCase, HllCase, NodegraphCase]
+    for label, rec in _edge_records(k):
+        named, prefix = _edge_expectation(rec, k)
+        assert (named is None) == (label.startswith("len ==")), label
+        for force in (False, True):
+            for family in families:
+                case = family()
+                case.obj.add_sequence(lead)
+                case.expect(lead)
+                if named is None or force:
+                    case.obj.add_sequence(rec, force=force)          # nothing to raise
+                    case.expect(rec)                                  # (the oracles skip the k-mers over a bad byte)
+                else:
+                    with pytest.raises(ValueError) as err:
+                        case.obj.add_sequence(rec, force=False)
+                    assert str(err.value) == "invalid DNA character in input k-mer: " + named, (family.__name__, label)
+                    case.expect(prefix)
+                case.check()
