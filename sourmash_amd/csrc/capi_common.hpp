@@ -1,5 +1,6 @@
-// capi_common.hpp -- what the units of the extern "C" surface (capi.cpp, capi_hll.cpp, capi_nodegraph.cpp; include/sourmash_amd.h)
-// share: the thread's error slot and the landing pad, the handle casts, small output helpers and the device-resident sketch collection.  Internal to the
+// capi_common.hpp -- what the units of the extern "C" surface (capi.cpp and the capi_*.cpp families; include/sourmash_amd.h)
+// share: the thread's error slot and the landing pad, the handle casts, small output helpers, the three helpers that cross
+// units (sigs_out, upload_rows, compare_device_csr) and the device-resident sketch collection.  Internal to the
 // library: everything here is hidden, and state lives in inline variables / inline functions so that the library has ONE of each.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -92,6 +93,16 @@ inline uint64_t* slice_out(const std::vector<uint64_t>& v, uintptr_t* size) {
     return p;
 }
 
+inline SourmashSignature** sigs_out(std::vector<Signature>&& sigs, uintptr_t* size) {
+    *size = sigs.size();
+    SourmashSignature** out = (SourmashSignature**)malloc((sigs.size() ? sigs.size() : 1) * sizeof(void*));
+    for (size_t i = 0; i < sigs.size(); ++i) out[i] = reinterpret_cast<SourmashSignature*>(new Signature(std::move(sigs[i])));
+    return out;
+}
+
+// x rounded up to the 256-byte granule the workspaces are carved in
+inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
+
 inline std::string upper_ascii(const uint8_t* p, size_t n) {
     std::string s((const char*)p, n);
     for (auto& c : s) if (c >= 'a' && c <= 'z') c = (char)(c - 32);
@@ -100,7 +111,15 @@ inline std::string upper_ascii(const uint8_t* p, size_t n) {
 
 inline uint64_t keep_threshold(const KmerMinHash& mh) { return mh.max_hash ? mh.max_hash : ~0ull; }
 
-// ---- device-resident sketch collections (capi.cpp makes them; the Nodegraph unit reads them)
+// ---- helpers of the compare unit (capi_compare.cpp) that the sketch-set unit uses too
+// n x n common counts (+ Jaccard) of a device-resident CSR into host matrices
+void compare_device_csr(const uint64_t* d_hashes, const uint64_t* d_offsets, uint64_t n, uint64_t total,
+                        uint32_t* common_out, double* jaccard_out, hipStream_t st);
+// the hash vectors (or abundance vectors) of n sketches back to back into d_dst
+void upload_rows(const SourmashKmerMinHash* const* mhs, uintptr_t n, const std::vector<uint64_t>& offsets, bool abunds,
+                 void* d_dst, hipStream_t st);
+
+// ---- device-resident sketch collections (capi_sketchset.cpp and capi_records.cpp make them; the gather and Nodegraph units read them)
 struct SketchSet {
     DevBuf hashes, offsets;
     uint64_t n = 0, total = 0;

@@ -554,7 +554,7 @@ __global__ __launch_bounds__(PL_THREADS) void gather_loop_kernel(LoopArgs a) {
     // decides for the whole grid: it counts arrivals and reaches n_wg, or a workgroup that waited gate_ticks sets bit 63 by
     // compare-and-swap while the count is still short (no CAS can succeed once everybody is there).  Given up: every
     // workgroup -- those that start later included -- leaves at once with counters, uncovered set and results untouched, and
-    // the host runs the two-kernel rounds on the same state (GS_ERR = 10; capi.cpp: gather_drain).
+    // the host runs the two-kernel rounds on the same state (GS_ERR = 10; capi_gather.cpp: gather_drain).
     {
         constexpr unsigned long long GAVE_UP = 1ull << 63;
         if (tid == 0) {

@@ -372,7 +372,7 @@ def _add_buffer_to_signature(sig, buf):
             rustcall(lib.signature_push_mh, sig._get_objptr(), mh._get_objptr())
 
 
-RECORDS_MAX_FILE = 2 << 30           # text bytes the per-record path keeps resident (csrc/capi.cpp: RECORDS_MAX_FILE)
+RECORDS_MAX_FILE = 2 << 30           # text bytes the per-record path keeps resident (csrc/capi_records.cpp: RECORDS_MAX_FILE)
 RECORDS_MAX_KSIZE = 88               # the longest k-mer of its kernel (csrc/sketch_kernel.hpp: SK_FAST_MAX_K)
 
 

@@ -286,6 +286,34 @@ def test_bad_starts_raise_and_launch_nothing(sm):
     assert m.offsets[1] == m.offsets[2] and m.offsets[3] == len(m) > 0
 
 
+ERROR_CODE_INTERNAL = 2                                   # SOURMASH_ERROR_CODE_INTERNAL (include/sourmash_amd.h)
+
+
+def raw_find_bad_starts(sm, bad):
+    """smgpu_find_kmers_raw over 200 bases, k = 21, three records whose starts are `bad` -> (returned, code, message).  Only the
+    checking kernel reads the starts (d_starts[0 .. 3], nothing they point at); the error is raised on the host from its flag."""
+    import torch
+    assert len(bad) == 4
+    buf = oracle.synth_dna(0, 200, seed=5)
+    dense = dense_hashes(buf, 21)
+    query = make_query(sm, dense[dense > 0][:50], 21, 1)
+    got, code, msg, result, positions = raw_find(sm, query, to_dev(torch, buf), to_dev(torch, np.array(bad, dtype=np.int64)), 256)
+    assert result[0] == 0 and (positions == -7).all()                          # raised in front of the pairs kernel
+    return got, code, msg
+
+
+def test_raw_starts_not_ascending_message(sm):
+    got, code, msg = raw_find_bad_starts(sm, [0, 120, 60, 200])
+    assert got == 2**64 - 1 and code == ERROR_CODE_INTERNAL
+    assert msg == 'internal error: "record starts: the offsets are not ascending"'
+
+
+def test_raw_last_offset_beyond_len_message(sm):
+    got, code, msg = raw_find_bad_starts(sm, [0, 60, 120, 201])
+    assert got == 2**64 - 1 and code == ERROR_CODE_INTERNAL
+    assert msg == 'internal error: "record starts: the last offset lies behind the end of the buffer (200 bytes)"'
+
+
 def test_raw_capacity_error_names_the_count(sm):
     import torch
     k, scaled = 31, 10

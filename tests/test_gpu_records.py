@@ -348,6 +348,46 @@ def test_bad_starts_raise_value_error(sm):
     assert o[1] == o[2] and o[3] == len(h)
 
 
+def raw_bad_starts(bad):
+    """smgpu_sketch_records_raw over 200 bases, k = 21, three records whose starts are `bad` -> (returned, code, message).  Only the
+    checking kernel reads the starts (d_starts[0 .. 3], nothing they point at); the error is raised on the host from its flag."""
+    import torch
+    from sourmash_amd._lowlevel import lib
+    from sourmash_amd.utils import decode_str
+    assert len(bad) == 4
+    seq = to_dev(torch, oracle.synth_dna(0, 200, seed=5))
+    starts = to_dev(torch, np.array(bad, dtype=np.int64))
+    cap = 256
+    hashes = torch.zeros(cap, dtype=torch.int64, device="cuda")
+    offsets = torch.zeros(4, dtype=torch.int64, device="cuda")
+    result = torch.zeros(4, dtype=torch.int64, device="cuda")
+    ws = torch.empty(int(lib.smgpu_sketch_records_workspace_bytes(cap, 3)), dtype=torch.uint8, device="cuda")
+    lib.sourmash_err_clear()
+    n = lib.smgpu_sketch_records_raw(C.c_void_p(seq.data_ptr()), 200, C.c_void_p(starts.data_ptr()), 3, 21, 42, 0,
+                                     C.c_void_p(hashes.data_ptr()), None, cap, C.c_void_p(offsets.data_ptr()),
+                                     C.c_void_p(result.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                     C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    code = lib.sourmash_err_get_last_code()
+    msg = decode_str(lib.sourmash_err_get_last_message()) if code else ""
+    lib.sourmash_err_clear()
+    return n, code, msg
+
+
+ERROR_CODE_INTERNAL = 2                                   # SOURMASH_ERROR_CODE_INTERNAL (include/sourmash_amd.h)
+
+
+def test_raw_starts_not_ascending_message(sm):
+    n, code, msg = raw_bad_starts([0, 120, 60, 200])
+    assert n == 2**64 - 1 and code == ERROR_CODE_INTERNAL
+    assert msg == 'internal error: "record starts: the offsets are not ascending"'
+
+
+def test_raw_last_offset_beyond_len_message(sm):
+    n, code, msg = raw_bad_starts([0, 60, 120, 201])
+    assert n == 2**64 - 1 and code == ERROR_CODE_INTERNAL
+    assert msg == 'internal error: "record starts: the last offset lies behind the end of the buffer (200 bytes)"'
+
+
 def test_raw_capacity_error_names_the_count(sm):
     import torch
     from sourmash_amd._lowlevel import lib

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Where `auto` (the cost model of csrc/capi.cpp: bitindex_build) stops choosing the general all-pairs kernel
+"""Where `auto` (the cost model of csrc/capi_compare.cpp: bitindex_build) stops choosing the general all-pairs kernel
 (compare_hash_kernel): N = 16 ... 2,000 sketches of ~5,000 hashes, a collection with heavy sharing (pool 50,000) and one whose
 hashes are mostly private (pool 2e6: a hash sits in n / 400 sketches).  Per row: ms of the general kernel, of a forced index (build + matrices), of auto, and
 what auto took.  python tools/bench_compare_small.py -> JSON lines (GPU box)."""
