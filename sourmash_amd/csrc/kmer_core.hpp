@@ -102,6 +102,10 @@ struct LaneGeom {
     static constexpr int NWK = (K + 3) / 4;         // dwords of one k-mer
     static constexpr int NCH = (K + 7) / 8;         // 8-byte chunks of one k-mer
     static constexpr uint32_t LAST_MASK = (K % 4) ? ((1u << (8 * (K % 4))) - 1u) : 0xffffffffu;
+    // The last key dword holds K % 4 bytes.  Where a caller asks for the late mask (PosOps<.., LATE>), both strands' last
+    // dwords are built whole and the chosen one is masked once, behind the strand select -- if there is a mask at all and the
+    // last dword is no part of the first-8-bytes compare.
+    static constexpr bool LATE_MASK_OK = (K % 4) != 0 && NWK > 2;
 };
 
 // selector for "4 bytes starting at byte a of {hi:lo}, reversed"
@@ -118,10 +122,12 @@ constexpr uint32_t rev_sel_partial(int a, int nb) {
     return s;
 }
 
-// One start position `O` (compile time) of the lane window.
-template <int K, int P, int O>
+// One start position `O` (compile time) of the lane window.  LATE: the last key dword is masked behind the strand select (below);
+// the same keys and hashes either way.  A kernel that would lose a wave per SIMD to it keeps the early mask, as with PLAIN.
+template <int K, int P, int O, bool LATE = false>
 struct PosOps {
     using G = LaneGeom<K, P>;
+    static constexpr bool LATE_MASK = LATE && G::LATE_MASK_OK;
 
     // forward k-mer dword d: bytes O+4d .. O+4d+3 of the window
     template <int D>
@@ -131,14 +137,19 @@ struct PosOps {
         if constexpr (a == 0) v = U[q];
         else if constexpr (q + 1 < G::NW) v = alignbyte_b32(U[q + 1], U[q], a);
         else v = U[q] >> (8 * a);
-        if constexpr (D == G::NWK - 1) v &= G::LAST_MASK;
+        if constexpr (D == G::NWK - 1 && !LATE_MASK) v &= G::LAST_MASK;
         return v;
     }
 
     // reverse-complement k-mer dword d: rc[j] = comp(win[O + K-1 - j]), j = 4d..4d+3
+    // The last dword of a K % 4 != 0 holds nb < 4 bytes.  Under LATE_MASK it is taken whole where its 4 bytes lie inside the
+    // window -- O + K - 4 D - 4 >= 0: the bytes in front of the k-mer fill its top, and that whole dword is one another position
+    // of the lane builds anyway -- and hash_open masks it behind the select; a position whose whole dword would start in front
+    // of the window keeps the zero-filling selector.
     template <int D>
     static SMG_HD uint32_t rev(const uint32_t* C) {
-        constexpr int nb = (K - 4 * D) >= 4 ? 4 : (K - 4 * D);  // valid bytes in this dword
+        constexpr int nbk = (K - 4 * D) >= 4 ? 4 : (K - 4 * D);  // valid bytes in this dword
+        constexpr int nb = (LATE_MASK && O + K - 4 * D - 4 >= 0) ? 4 : nbk;
         constexpr int s = O + K - 4 * D - nb;                    // first window byte of the group
         constexpr int q = s >> 2, a = s & 3;
         constexpr uint32_t sel = (nb == 4) ? rev_sel(a) : rev_sel_partial(a, nb);
@@ -153,10 +164,17 @@ struct PosOps {
         return v;
     }
 
+    // (under LATE_MASK the strands' last dwords are unmasked: this path compares whole keys and masks its own copies)
+    template <int D>
+    static SMG_HD uint32_t key_dword_opaque(const uint32_t* W) {
+        const uint32_t v = opaque(W[D]);
+        if constexpr (D == G::NWK - 1 && LATE_MASK) return v & G::LAST_MASK;
+        else return v;
+    }
     template <int CH>
     static SMG_HD uint64_t be_chunk_opaque(const uint32_t* W) {
-        uint64_t v = (uint64_t)bswap32(opaque(W[2 * CH])) << 32;
-        if constexpr (2 * CH + 1 < G::NWK) v |= bswap32(opaque(W[2 * CH + 1]));
+        uint64_t v = (uint64_t)bswap32(key_dword_opaque<2 * CH>(W)) << 32;
+        if constexpr (2 * CH + 1 < G::NWK) v |= bswap32(key_dword_opaque<2 * CH + 1>(W));
         return v;
     }
 
@@ -192,6 +210,7 @@ struct PosOps {
         const uint32_t m = gt ? 0xffffffffu : 0u;
 #pragma unroll
         for (int d = 0; d < G::NWK; ++d) W[d] = bitselect(m, R[d], F[d]);
+        if constexpr (LATE_MASK) W[G::NWK - 1] &= G::LAST_MASK;    // one mask for both strands
         return mmh3_open_words<K, PLAIN>(W, seed);
     }
 };
@@ -226,7 +245,7 @@ SMG_HD bool early_may_keep(Mmh3Open open, uint32_t lim) { return (uint32_t)(mmh3
 // The two prologues and the positions sit in ONE function on purpose: with the prologue in one function and the positions in
 // another the compiler pairs the window's LDS reads differently, and sketch_dna_kernel<18, 16, false> (96 -> 98 VGPRs) and
 // hll_dna_kernel<19, 16, true> (80 -> 82) each lose a wave per SIMD.
-template <int K, int P, bool EARLY, bool PLAIN, bool STAGED, class Emit, int... O>
+template <int K, int P, bool EARLY, bool PLAIN, bool STAGED, bool LATE, class Emit, int... O>
 SMG_HD void process_window(const uint32_t* raw, const uint32_t* comp, bool dirty, uint64_t seed, uint64_t thr, Emit&& emit,
                            std::integer_sequence<int, O...>) {
     using G = LaneGeom<K, P>;
@@ -278,7 +297,7 @@ SMG_HD void process_window(const uint32_t* raw, const uint32_t* comp, bool dirty
     static_assert(G::NBYTES <= 192 && K <= 128 && P <= 64, "window too long for the 192-bit validity mask");
     (
         [&] {
-            const Mmh3Open open = PosOps<K, P, O>::template hash_open<PLAIN>(U, C, seed);
+            const Mmh3Open open = PosOps<K, P, O, LATE>::template hash_open<PLAIN>(U, C, seed);
             if constexpr (EARLY) {
                 if (!any_lane(early_may_keep(open, lim))) return;
             }
@@ -303,13 +322,14 @@ SMG_HD void process_window(const uint32_t* raw, const uint32_t* comp, bool dirty
 // PLAIN: the 64-bit constant multiplies of the hash as plain products (murmur3.hpp, mul_c64); the same values.
 template <int K, int P, bool EARLY = true, bool PLAIN = false, class Emit>
 SMG_HD void process_lane(const uint32_t* raw, uint64_t seed, uint64_t thr, Emit&& emit) {
-    process_window<K, P, EARLY, PLAIN, false>(raw, nullptr, false, seed, thr, static_cast<Emit&&>(emit),
+    process_window<K, P, EARLY, PLAIN, false, false>(raw, nullptr, false, seed, thr, static_cast<Emit&&>(emit),
                                               std::make_integer_sequence<int, P>{});
 }
 // A staged window: U upper-cased, C its complement.  `dirty` (the tile's flag) MUST be wave-uniform on the device.
-template <int K, int P, bool EARLY = true, bool PLAIN = false, class Emit>
+// LATE: the last key dword masked once, behind the strand select (PosOps); the same hashes.
+template <int K, int P, bool EARLY = true, bool PLAIN = false, bool LATE = false, class Emit>
 SMG_HD void process_lane_staged(const uint32_t* U, const uint32_t* C, bool dirty, uint64_t seed, uint64_t thr, Emit&& emit) {
-    process_window<K, P, EARLY, PLAIN, true>(U, C, dirty, seed, thr, static_cast<Emit&&>(emit), std::make_integer_sequence<int, P>{});
+    process_window<K, P, EARLY, PLAIN, true, LATE>(U, C, dirty, seed, thr, static_cast<Emit&&>(emit), std::make_integer_sequence<int, P>{});
 }
 
 // ---- the tile walk: what every DNA k-mer kernel does around its per-position code ---------------------------------------------

@@ -11,10 +11,12 @@
 // smg::process_lane (kmer_core.hpp).  The appending form does the per-byte work
 // (upper-casing, complement, validity) where the tile is staged: the tile goes
 // to LDS twice, upper-cased and complemented, with one dirty flag per tile, and
-// the lanes read both (process_lane_staged); from k = 19 on it stages three such
-// windows as one tile and takes the lanes through them in a rolled loop, so that
-// the tile's barriers and the wait for its global loads come once per 12,288
-// positions (sketch_kernel.hpp, SK_R_MAX).  A launch with more tiles than workgroups
+// the lanes read both (process_lane_staged); from k = 19 on a lane takes 32
+// positions, not P, and two such windows of 8,192 positions are staged as one
+// tile (three of 4,096 where a k stays at 16 positions) and the lanes go through
+// them in a rolled loop, so that the tile's barriers and the wait for its global
+// loads come once per 16,384 positions (sketch_kernel.hpp, sk_lane_positions,
+// sk_rounds_max).  A launch with more tiles than workgroups
 // starts as many workgroups as are resident at once and hands every tile behind a
 // workgroup's first out by a ticket from a counter of its own (sk_handout), so that
 // no workgroup's share is fixed at launch.  Kept hashes (about 1 in `scaled`) are

@@ -30,7 +30,8 @@ constexpr bool sk_plain_mul(int k, bool dense) {
 // second copy's 4 KiB of LDS take the seventh workgroup of a CU, and k = 18, 20 and 30, which need a few registers more and
 // cross a step of the register file (profiles/strand_lds_kernel_resources.txt).
 constexpr bool sk_staged(int k) { return k > 11 && k != 18 && k != 20 && k != 30; }
-// The staged appending form walks tiles of several window rounds: R_MAX consecutive windows of SK_BLOCK x 16 positions are
+// The staged appending form walks tiles of several window rounds: R_MAX consecutive windows of SK_BLOCK x 16 positions (x 32
+// where sk_lane_positions says so, below, with rounds and sink of its own) are
 // staged together, behind one pair of barriers, one wait for the global loads and one halo, and a rolled loop takes the lanes
 // through them (`rounds`, a launch argument: 1 where the sink could overfill between two flush checks, kmer_core.hpp
 // sk_tile_rounds).  SK_R_MAX sizes the LDS copies: 2 with the 2,048-entry sink and 3 with a 1,024-entry one are about 33 KB at
@@ -42,9 +43,43 @@ constexpr bool sk_staged(int k) { return k > 11 && k != 18 && k != 20 && k != 30
 #endif
 constexpr int SK_R_MAX = SMG_SK_R_MAX;
 static_assert(SK_R_MAX >= 1 && SK_R_MAX <= 3, "four rounds do not fit four workgroups per CU");
+// The last key dword of a K % 4 != 0 masked once behind the strand select instead of once per strand (kmer_core.hpp, PosOps):
+// the staged appending form, but for k = 13, which would run five workgroups per CU instead of six with it (80 -> 82 registers).
+constexpr bool sk_late_mask(int k) { return sk_staged(k) && k != 13; }
 constexpr bool sk_one_round(int k) { return k <= 17; }      // k = 12, 13: six workgroups per CU, 14 .. 17: five
-constexpr int sk_rounds_max(int k, bool dense) { return !dense && sk_staged(k) && !sk_one_round(k) ? SK_R_MAX : 1; }
-constexpr int sk_out_cap(int r_max) { return r_max >= 3 ? SK_OUT_CAP / 2 : SK_OUT_CAP; }
+// Start positions a lane takes per round.  The kernel's template argument P stays 16 -- it is the kernel's name, which the
+// benchmark, the counter summaries and tools/valu_mix.py look it up by -- and the kernel derives its lane geometry from this rule.
+// 32 in the staged appending form of several rounds (k >= 19): a lane's window is P + K - 1 bytes, and the unaligned forward
+// dwords (P + 28 offsets at k = 31), the reverse dwords (P + 24) and the compare words are shared between the positions of a
+// lane, so the halo's share of the byte plumbing halves when P doubles, and a lane reads 8 x 16 bytes of LDS per 32 positions
+// where two rounds of 16 read 12.  An instantiation that would run fewer waves per SIMD, gain scratch or spill with the longer
+// window's registers stays at 16 (sk_lane16_only; profiles/lane32_kernel_resources.txt), as do the per-position form, the
+// unstaged k and k <= 17.  SMG_SK_LANE_POSITIONS: a variant build with one value for every k of the rule, for A/B runs.
+constexpr bool sk_lane16_only(int k) { return (k >= 35 && k <= 40) || (k >= 53 && k <= 56); }   // past 128 / 168 registers at 32
+#ifndef SMG_SK_LANE_POSITIONS
+#define SMG_SK_LANE_POSITIONS 32
+#endif
+constexpr int sk_lane_positions(int k, bool dense) {
+    return !dense && sk_staged(k) && !sk_one_round(k) && !sk_lane16_only(k) ? SMG_SK_LANE_POSITIONS : 16;
+}
+// Rounds and sink by the window: with 32 positions per lane a window is 8,192 positions, and two rounds (2 x 16.4 KB of copies at
+// k = 31) with a 512-entry sink are 36.9 KB, one round with the 2,048-entry sink 32.8 KB: four workgroups per CU fit either way,
+// three rounds do not.  SMG_SK_LANE32_R_MAX: the other of the two, for A/B runs (profiles/lane32_bench.txt).
+#ifndef SMG_SK_LANE32_R_MAX
+#define SMG_SK_LANE32_R_MAX 2
+#endif
+static_assert(SMG_SK_LANE32_R_MAX >= 1 && SMG_SK_LANE32_R_MAX <= 2, "three rounds of 8,192 positions do not fit four workgroups per CU");
+constexpr int sk_rounds_max(int k, bool dense) {
+    if (dense || !sk_staged(k) || sk_one_round(k)) return 1;
+    return sk_lane_positions(k, dense) == 32 ? SMG_SK_LANE32_R_MAX : SK_R_MAX;
+}
+// Sink entries by the tile's length in positions (r_max rounds of SK_BLOCK x lane_positions): the longer the tile's copies, the
+// smaller the sink beside them.  A tile of 16,384 positions is expected to keep about 16 hashes at scaled = 1,000, well under
+// the quarter of 512 entries that sk_tile_rounds asks for and the half at which the sink is flushed.
+constexpr int sk_out_cap(int r_max, int lane_positions = 16) {
+    const int tile = r_max * SK_BLOCK * lane_positions;
+    return tile >= 16384 ? SK_OUT_CAP / 4 : tile >= 12288 ? SK_OUT_CAP / 2 : SK_OUT_CAP;
+}
 // The appending form hands its tiles out by tickets where a launch has more tiles than workgroups (tile_counter below): a
 // workgroup's share is then what it gets through, not a fixed 1 / grid of the tiles, and the launch ends within one tile's time
 // of its last workgroup, whatever the grid.  An instantiation that would run fewer waves per SIMD with the ticket's LDS word
@@ -78,11 +113,13 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
     uint64_t n_tiles, uint32_t skip, uint32_t rounds, unsigned long long* __restrict__ tile_counter) {
     // seq is 16-byte aligned; its first `skip` (< 16) bytes precede the caller's buffer and are
     // treated as invalid.  len includes them.  DENSE positions are reported relative to seq + skip.
-    // A tile is `rounds` (1 .. R_MAX) windows of SK_BLOCK x P positions; n_tiles counts tiles of that length.
+    // A tile is `rounds` (1 .. R_MAX) windows of SK_BLOCK x LP positions (LP = sk_lane_positions(K, DENSE), not P); n_tiles counts tiles of that length.
     // tile_counter (appending form only): null, and the workgroups walk the tiles by stride; or a zeroed counter of this launch
     // alone, and every tile behind a workgroup's first is handed out by a ticket from it (kmer_core.hpp, tile_first).
-    constexpr int R_MAX = sk_rounds_max(K, DENSE), OUT_CAP = sk_out_cap(R_MAX);
-    using T = TileGeom<K, P, SK_BLOCK, R_MAX>;
+    static_assert(P == 16, "the kernel's name; the lane's positions are LP");
+    constexpr int LP = sk_lane_positions(K, DENSE);          // start positions per lane and round
+    constexpr int R_MAX = sk_rounds_max(K, DENSE), OUT_CAP = sk_out_cap(R_MAX, LP);
+    using T = TileGeom<K, LP, SK_BLOCK, R_MAX>;
     constexpr int WINDOW = T::WINDOW, LANE_RD = T::LANE_RD, IN_CHUNKS = T::IN_CHUNKS;
     constexpr bool STAGED = !DENSE && sk_staged(K);          // per-byte work at staging, U and C from LDS
     static_assert(R_MAX == 1 || STAGED, "only the staged form walks several rounds");
@@ -140,34 +177,34 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
             if (handout && tid == 0) s_next = tile_from_ticket(gridDim.x, atomicAdd(tile_counter, 1ull));
         }
         uint32_t raw[LANE_RD];
-        if constexpr (R_MAX == 1) read_window<LANE_RD, P>(s_in, tid, raw);
+        if constexpr (R_MAX == 1) read_window<LANE_RD, LP>(s_in, tid, raw);
         auto emit = [&](int o, uint64_t h) {
             if constexpr (DENSE) {
-                const uint64_t pos = base + (uint64_t)tid * P + (uint64_t)o - skip;   // valid k-mers never start in the prefix
+                const uint64_t pos = base + (uint64_t)tid * LP + (uint64_t)o - skip;   // valid k-mers never start in the prefix
                 if (pos < out_cap) out[pos] = h;
             } else {
                 sink.append(h);
             }
         };
         if constexpr (STAGED) {
-            static_assert(!STAGED || P == 16, "the staged form reads whole 16-byte groups");
+            static_assert(!STAGED || LP == 16 || LP == 32, "the staged form reads whole 16-byte groups");
             uint32_t comp[LANE_RD];
             if constexpr (R_MAX == 1) {
-                read_window<LANE_RD, P>(s_comp, tid, comp);
+                read_window<LANE_RD, LP>(s_comp, tid, comp);
                 const bool dirty = __builtin_amdgcn_readfirstlane(s_dirty) != 0;
-                process_lane_staged<K, P, true, sk_plain_mul(K, false)>(raw, comp, dirty, seed, thr, emit);
+                process_lane_staged<K, LP, true, sk_plain_mul(K, false), sk_late_mask(K)>(raw, comp, dirty, seed, thr, emit);
             } else {
                 // the rounds of the tile, rolled: the position code stays one copy, its registers and its size what they were
                 const bool dirty = __builtin_amdgcn_readfirstlane(s_dirty) != 0;   // one flag for the whole tile
 #pragma unroll 1
                 for (uint32_t r = 0; r < n_rounds; ++r) {
-                    read_window<LANE_RD, P>(s_in, tid + (int)r * SK_BLOCK, raw);
-                    read_window<LANE_RD, P>(s_comp, tid + (int)r * SK_BLOCK, comp);
-                    process_lane_staged<K, P, true, sk_plain_mul(K, false)>(raw, comp, dirty, seed, thr, emit);
+                    read_window<LANE_RD, LP>(s_in, tid + (int)r * SK_BLOCK, raw);
+                    read_window<LANE_RD, LP>(s_comp, tid + (int)r * SK_BLOCK, comp);
+                    process_lane_staged<K, LP, true, sk_plain_mul(K, false), sk_late_mask(K)>(raw, comp, dirty, seed, thr, emit);
                 }
             }
         } else {
-            process_lane<K, P, !DENSE, sk_plain_mul(K, DENSE)>(raw, seed, thr, emit);
+            process_lane<K, LP, !DENSE, sk_plain_mul(K, DENSE)>(raw, seed, thr, emit);
         }
         if constexpr (DENSE) { tile += gridDim.x; continue; }
         __syncthreads();
@@ -214,8 +251,9 @@ struct SketchLaunch {
     static hipError_t launch(const uint8_t* d_seq, uint64_t len, uint64_t seed, uint64_t thr, uint64_t* d_out,
                              unsigned long long* d_count, uint64_t cap, uint32_t grid, hipStream_t stream) {
         // the rounds first: the tile count and the grid are those of the tile length this launch walks
-        constexpr uint32_t WINDOW = (uint32_t)SK_BLOCK * 16, R_MAX = (uint32_t)sk_rounds_max(K, DENSE);
-        const uint32_t rounds = sk_tile_rounds(thr, R_MAX, WINDOW, (uint32_t)sk_out_cap((int)R_MAX));
+        constexpr uint32_t LP = (uint32_t)sk_lane_positions(K, DENSE), WINDOW = (uint32_t)SK_BLOCK * LP;
+        constexpr uint32_t R_MAX = (uint32_t)sk_rounds_max(K, DENSE);
+        const uint32_t rounds = sk_tile_rounds(thr, R_MAX, WINDOW, (uint32_t)sk_out_cap((int)R_MAX, (int)LP));
         const TileSpan t = align_to_tiles(d_seq, len, (uint64_t)rounds * WINDOW);
         if (t.n_tiles == 0) return hipSuccess;
         constexpr unsigned per_cu = sk_grid_per_cu((int)R_MAX, !DENSE && sk_handout(K));

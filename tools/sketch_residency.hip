@@ -13,7 +13,7 @@ static int report(bool last) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, f, smg::SK_BLOCK, 0) != hipSuccess) return 1;
     if (hipFuncGetAttributes(&a, f) != hipSuccess) return 1;
     printf("  \"k%d\": {\"rounds_max\": %d, \"sink_entries\": %d, \"workgroups_per_cu\": %d, \"waves_per_simd\": %d, \"lds_bytes\": %zu, \"registers\": %d}%s\n",
-           K, smg::sk_rounds_max(K, false), smg::sk_out_cap(smg::sk_rounds_max(K, false)), blocks, blocks * smg::SK_BLOCK / 64 / 4,
+           K, smg::sk_rounds_max(K, false), smg::sk_out_cap(smg::sk_rounds_max(K, false), smg::sk_lane_positions(K, false)), blocks, blocks * smg::SK_BLOCK / 64 / 4,
            a.sharedSizeBytes, a.numRegs, last ? "" : ",");
     return 0;
 }

@@ -5,7 +5,8 @@ bench.py turns the counter SQ_INSTS_VALU into "fraction of the SIMDs' issue cycl
 instruction MIX.  Round 1-3 carried that average as a constant (3.76) from a one-off count.  This tool derives it from the code:
 
   1. compiles csrc/sketch.hip for gfx950 to assembly (hipcc --cuda-device-only -S; no GPU needed),
-  2. takes the kernel's main loop (one window of 256 lanes x 16 positions per trip: the rolled loop over a tile's window rounds,
+  2. takes the kernel's main loop (one window of 256 lanes x P positions per trip, P = sk_lane_positions(31, false) read from
+     sketch_kernel.hpp through a constexpr probe compiled for the host: the rolled loop over a tile's window rounds,
      nested in the tile loop; what a tile does once -- staging, the flush check -- is outside it) and splits it into the HOT path and the
      blocks that a wave-level branch (s_cbranch_vccz / vccnz / scc0 / scc1 over a forward region: "some lane of the wave has a
      bad byte / a tie / a hash that can still pass") skips -- bad bytes and canonical ties do not occur on random DNA, the hash is
@@ -63,6 +64,17 @@ def ubench_costs():
     return costs
 
 
+def trip_positions(hipcc, csrc, td):
+    "start positions per lane and trip of the kernel: sketch_kernel.hpp's own constexpr rule, printed by a host program"
+    if "sk_lane_positions" not in open(os.path.join(csrc, "sketch_kernel.hpp")).read():
+        return 16                                # a tree from before the rule: the template argument was the trip
+    src, exe = os.path.join(td, "trip.hip"), os.path.join(td, "trip")
+    with open(src, "w") as f:
+        f.write('#include <stdio.h>\n#include "sketch_kernel.hpp"\nint main() { printf("%d\\n", smg::sk_lane_positions(31, false)); return 0; }\n')
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-std=c++17", "-I", csrc, src, "-o", exe], stderr=subprocess.DEVNULL)
+    return int(subprocess.check_output([exe]).split()[0])
+
+
 def opcode_cost(op, costs):
     base = re.sub(r"_(e32|e64|sdwa|dpp)$", "", op)
     if base.startswith("v_cmp") or base.startswith("v_cmpx"):
@@ -85,6 +97,7 @@ def main():
         subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-S",
                                os.path.join(csrc, "sketch.hip"), "-o", asm], stderr=subprocess.DEVNULL)
         lines = open(asm).read().splitlines()
+        positions = trip_positions(hipcc, csrc, td)
     start = next(i for i, ln in enumerate(lines) if ln.startswith("_ZN3smg") and KERNEL in ln and ln.rstrip().endswith(tuple(": ;")) or (KERNEL in ln and re.match(r"^_ZN3smg\S+:", ln)))
     body = []
     for ln in lines[start + 1:]:
@@ -103,7 +116,7 @@ def main():
             items.append(("inst", t))
     label_at = {t: i for i, (k, t) in enumerate(items) if k == "label"}
     # the main loop: the backward branch that spans the most instructions -- the tile loop -- and from there inwards while a loop
-    # nested in it holds more than half of it: the rolled loop over a tile's window rounds is the trip of 16 positions per lane
+    # nested in it holds more than half of it: the rolled loop over a tile's window rounds is the trip of P positions per lane
     loops = []
     for i, (k, t) in enumerate(items):
         m = re.match(r"s_cbranch_\w+\s+(\.LBB\d+_\d+)", t) if k == "inst" else None
@@ -147,9 +160,9 @@ def main():
             continue
         d = parts[("hot", "wave_conditional", "lane_conditional")[cold[i]]]
         d[op] = d.get(op, 0) + 1
-    positions = 16
     out = {"kernel": "sketch_dna_kernel<31, 16, false>", "sources": {f: source_hashes()[f] for f in SOURCES},
-           "method": "static opcode histogram of the main loop (one trip = 16 positions per lane), hot path and wave-conditional blocks "
+           "positions_per_trip": positions,
+           "method": f"static opcode histogram of the main loop (one trip = {positions} positions per lane), hot path and wave-conditional blocks "
                      "apart; costs per opcode class from profiles/r01_ubench_valu.txt (waves/SIMD = 4)",
            "finish_probability": FINISH_PROB, "keep_probability": round(KEEP_PROB, 4), "unmeasured_opcodes": []}
     tot_n = tot_c = 0.0
