@@ -673,6 +673,54 @@ void smgpu_sketchset_device_csr(const SmgpuSketchSet *ptr, const uint64_t **d_ha
 void smgpu_sketchset_overlaps(const SmgpuSketchSet *ptr, const SourmashKmerMinHash *query, uint64_t *counts_out);
 /* n x n matrices of a loaded set on the host (either may be NULL); same kernels as smgpu_compare_all_pairs. */
 void smgpu_sketchset_compare(const SmgpuSketchSet *ptr, uint32_t *common_out, double *jaccard_out);
+/* ---- many queries against a collection in one pass over it (csrc/overlap_many.hip, csrc/many_core.hpp) ----
+ * The reference searches many against many with a loop of Index.search / Index.prefetch around the collection
+ * (src/sourmash/index/__init__.py:115-170, 202-256).  Here the queries' hashes are merged into one index on the device and the
+ * collection is read once: the hits -- the (query, row) pairs whose common count reaches the query's `need` -- leave as triples
+ * ordered by (query, row).  When the two sets differ in scaled every pair is taken at the coarser one (minhash.rs:539-548).
+ * geometry: lanes of a workgroup, the default queries per pass, and the most a caller may ask for.
+ * need: the integer filter of a search at `threshold` for queries of the given sizes (mode 0 Jaccard, 1 containment, 2 max
+ * containment): never above the smallest count that passes the float test, never 0.  Host only. */
+typedef struct SmgpuManyHits SmgpuManyHits;
+void smgpu_many_geometry(uint32_t *workgroup, uint32_t *q_block, uint32_t *q_block_max);
+void smgpu_many_need(uint32_t mode, double threshold, const uint64_t *sizes, uint64_t m, uint32_t *need_out);
+uint64_t smgpu_many_overlap_workspace_bytes(uint64_t m, uint64_t q_total, uint64_t capacity);
+/* Both CSRs in device memory: the queries (m rows, d_qoffsets m + 1 entries, q_total hashes in all) and the collection (n_rows
+ * rows); rows ascending.  d_need: one u32 >= 1 per query; cutoff: only hashes <= cutoff count (the smaller max_hash of the two
+ * sets; UINT64_MAX: all).  q_block: queries counted per pass over the collection (0: the default); grid: workgroups of a pass (0:
+ * the library's number).  The hits go to d_queries / d_rows / d_common (capacity entries each), ordered by (query, row).  d_result
+ * (device, 4 x u64): [0] the true number of hits, [1] distinct query hashes <= cutoff, [2] passes.  Returns the number of hits;
+ * when it exceeds the capacity the arrays hold the first `capacity` hits found, unordered, nothing is written behind them, and the
+ * caller runs again with room.  Synchronises the stream.  UINT64_MAX with an error set: a refused argument, or no device. */
+uint64_t smgpu_many_overlap_raw(const uint64_t *d_qhashes, const uint64_t *d_qoffsets, uint64_t m, uint64_t q_total,
+                                const uint64_t *d_hashes, const uint64_t *d_offsets, uint64_t n_rows, const uint32_t *d_need,
+                                uint64_t cutoff, uint32_t q_block, uint32_t grid, uint32_t *d_queries, uint32_t *d_rows,
+                                uint32_t *d_common, uint64_t capacity, uint64_t *d_result, void *d_workspace,
+                                uint64_t workspace_bytes, void *stream);
+/* d_sizes[r] = hashes of row r that are <= cutoff: a set's sizes at the common scaled.  Asynchronous on `stream`. */
+void smgpu_many_sizes_raw(const uint64_t *d_hashes, const uint64_t *d_offsets, uint64_t n, uint64_t cutoff, uint64_t *d_sizes,
+                          void *stream);
+/* The same for a resident set, into a host array (max_hash 0: the full sizes). */
+void smgpu_sketchset_sizes_at(const SmgpuSketchSet *set, uint64_t max_hash, uint64_t *sizes_out);
+/* Every row of `queries` against every row of `db`.  need: one count per query (NULL: need_all for each); never 0.  The sets must
+ * be compatible in the reference's order (check_compatible, minhash.rs:886-912: ksize, hash function, seed) and scaled; num sets
+ * are refused.  The capacity is the library's choice; a result that does not fit is computed once more with room.  The getters
+ * borrow from the handle: len hits (queries, rows, common), the sizes of every query and every row at the common scaled, that
+ * scaled; stats: out[0 .. 3) ms of the index build, the passes and the final sort (device), [3] ms of the whole call (host), [4]
+ * reruns, [5] passes over the collection. */
+SmgpuManyHits *smgpu_sketchset_overlaps_many(const SmgpuSketchSet *db, const SmgpuSketchSet *queries, const uint32_t *need,
+                                             uint32_t need_all);
+void smgpu_manyhits_free(SmgpuManyHits *ptr);
+uint64_t smgpu_manyhits_len(const SmgpuManyHits *ptr);
+const uint32_t *smgpu_manyhits_queries(const SmgpuManyHits *ptr);
+const uint32_t *smgpu_manyhits_rows(const SmgpuManyHits *ptr);
+const uint32_t *smgpu_manyhits_common(const SmgpuManyHits *ptr);
+const uint64_t *smgpu_manyhits_query_sizes(const SmgpuManyHits *ptr);
+const uint64_t *smgpu_manyhits_row_sizes(const SmgpuManyHits *ptr);
+uint64_t smgpu_manyhits_scaled(const SmgpuManyHits *ptr);
+void smgpu_manyhits_stats(const SmgpuManyHits *ptr, double *out6);
+/* Test support: the capacity smgpu_sketchset_overlaps_many first tries (0: its own choice), to see the second run. */
+void smgpu_many_set_first_capacity(uint64_t capacity);
 SmgpuCounter *smgpu_counter_new(const SmgpuSketchSet *set, const SourmashKmerMinHash *query);
 void smgpu_counter_free(SmgpuCounter *ptr);
 void smgpu_counter_get(const SmgpuCounter *ptr, uint64_t *counts_out);

@@ -145,6 +145,35 @@ hipError_t find_rows_launch(const uint8_t* d_seq, uint64_t len, uint64_t* d_pair
                             const uint64_t* d_starts, uint64_t n_records, uint32_t k, uint64_t* d_positions, uint64_t* d_hashes,
                             uint8_t* d_kmers, uint64_t* d_offsets, uint64_t* d_n_out, void* d_temp, size_t temp_bytes, hipStream_t stream);
 
+// ---- overlap_many.hip (m queries against every row of a CSR collection in one pass; many_core.hpp holds its rules) -------------
+// Both CSRs on the device: the queries (m rows, q_total hashes in all) and the collection (n_rows rows).  d_need[q] >= 1: the count
+// a pair of query q must reach to be reported; cutoff: only hashes <= cutoff count (rows are ascending and end there).  q_block:
+// queries counted per pass over the collection (0: MANY_Q_BLOCK); grid: workgroups of the pass (0: the launcher's own number).
+// The hits (query, row, count) leave in d_queries / d_rows / d_common, at most `capacity` of them, ordered by (query, row);
+// d_result (4 x u64): [0] the true number of hits, [1] distinct query hashes <= cutoff, [2] passes over the collection.
+struct ManyArgs {
+    const uint64_t *d_qhashes, *d_qoffsets;
+    uint64_t m, q_total;
+    const uint64_t *d_hashes, *d_offsets;
+    uint64_t n_rows;
+    const uint32_t* d_need;
+    uint64_t cutoff;
+    uint32_t q_block, grid;
+    uint32_t *d_queries, *d_rows, *d_common;
+    uint64_t capacity;
+    uint64_t* d_result;
+    void* d_workspace;
+    uint64_t workspace_bytes;
+};
+size_t many_overlap_workspace_bytes(uint64_t m, uint64_t q_total, uint64_t capacity);
+uint32_t many_overlap_passes(uint64_t m, uint32_t q_block);
+// Synchronises the stream (the index geometry and the hit count are read back).  *hits = d_result[0]; when it exceeds the capacity
+// the first `capacity` hits found stand unordered in the arrays and nothing lies behind them.  ms3 (may be null): milliseconds of
+// the index build, the passes, and the final sort.
+hipError_t many_overlap_run(const ManyArgs& args, uint64_t* hits, float* ms3, hipStream_t stream);
+// d_sizes[r] = hashes of row r that are <= cutoff (a set's sizes at the common scaled)
+hipError_t many_sizes_launch(const uint64_t* d_hashes, const uint64_t* d_offsets, uint64_t n, uint64_t cutoff, uint64_t* d_sizes, hipStream_t stream);
+
 // ---- synth.hip --------------------------------------------------------------------
 hipError_t synth_dna_launch(uint8_t* d_out, uint64_t start, uint64_t n, uint64_t seed, uint64_t record_len,
                             hipStream_t stream);

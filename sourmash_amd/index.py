@@ -26,7 +26,7 @@ from .search import calc_threshold_from_bp, make_containment_query, make_jaccard
 from .signature import SourmashSignature, load_signatures_from_json, save_signatures_to_json
 from .utils import RustObject, decode_str, objptr_array, rustcall
 
-__all__ = ["IndexSearchResult", "Collection", "SketchSet", "SketchSetWriter", "select_signature", "Index", "LinearIndex", "CounterGather"]
+__all__ = ["IndexSearchResult", "Collection", "SketchSet", "many_need", "score_hits", "rank_scored", "SketchSetWriter", "select_signature", "Index", "LinearIndex", "CounterGather"]
 
 IndexSearchResult = namedtuple("Result", "score, signature, location")
 
@@ -95,25 +95,45 @@ class Collection(RustObject):
         return SketchSet._from_objptr(self._methodcall(lib.smgpu_sketchset_from_collection))
 
 
-def rank_search_hits(shared, sizes, n_query, *, threshold=0.0, do_containment=False, do_max_containment=False, best_only=False):
-    """[(score, row)] best first from one overlap pass: shared[r] = |query ∩ row r|, sizes[r] = |row r|.  Jaccard by default,
-    query containment or max containment on request -- the scores of JaccardSearch (search.py:88-160); rows scoring below
-    the threshold or sharing nothing are dropped (index/__init__.py:115-170).  Shared by SketchSet.search (one GPU) and
-    parallel.search_distributed (database sharded over the ranks)."""
+def score_hits(shared, sizes, n_query, *, do_containment=False, do_max_containment=False):
+    """score[i] of a query of n_query hashes against a row of sizes[i] hashes sharing shared[i] with it: Jaccard by default, query
+    containment or max containment on request -- the scores of JaccardSearch (search.py:88-160), 0 where the denominator is."""
     shared = np.asarray(shared).astype(np.float64)
     sizes = np.asarray(sizes).astype(np.float64)
     nq = float(n_query)
     if do_containment:
-        score = shared / nq if nq else np.zeros_like(shared)
-    elif do_max_containment:
-        score = np.divide(shared, np.minimum(sizes, nq), out=np.zeros_like(shared), where=np.minimum(sizes, nq) > 0)
-    else:
-        union = sizes + nq - shared
-        score = np.divide(shared, union, out=np.zeros_like(shared), where=union > 0)
+        return shared / nq if nq else np.zeros_like(shared)
+    if do_max_containment:
+        return np.divide(shared, np.minimum(sizes, nq), out=np.zeros_like(shared), where=np.minimum(sizes, nq) > 0)
+    union = sizes + nq - shared
+    return np.divide(shared, union, out=np.zeros_like(shared), where=union > 0)
+
+
+def rank_scored(score, rows, *, threshold=0.0, best_only=False):
+    "[(score, row)] best first, ties in the order given: the entries scoring >= threshold and above 0 (index/__init__.py:115-170)"
     keep = np.flatnonzero((score >= threshold) & (score > 0))
     order = keep[np.argsort(-score[keep], kind="stable")]
-    hits = [(float(score[r]), int(r)) for r in order]
+    hits = [(float(score[i]), int(rows[i])) for i in order]
     return hits[:1] if best_only else hits
+
+
+def rank_search_hits(shared, sizes, n_query, *, threshold=0.0, do_containment=False, do_max_containment=False, best_only=False):
+    """[(score, row)] best first from one overlap pass: shared[r] = |query ∩ row r|, sizes[r] = |row r|.  Jaccard by default,
+    query containment or max containment on request -- the scores of JaccardSearch (search.py:88-160); rows scoring below
+    the threshold or sharing nothing are dropped (index/__init__.py:115-170).  Shared by SketchSet.search (one GPU),
+    SketchSet.search_many (the hits of one pass for many queries) and parallel.search_distributed (database sharded over the ranks)."""
+    score = score_hits(shared, sizes, n_query, do_containment=do_containment, do_max_containment=do_max_containment)
+    return rank_scored(score, np.arange(len(score)), threshold=threshold, best_only=best_only)
+
+
+def many_need(sizes, threshold, *, do_containment=False, do_max_containment=False):
+    """The integer filter the device applies for a search at `threshold`: need[q] for a query of sizes[q] hashes, never above the
+    smallest common count that passes the float test of score_hits, never 0 (csrc/many_core.hpp: many_need)."""
+    sizes = np.ascontiguousarray(sizes, dtype=np.uint64)
+    out = np.ones(max(len(sizes), 1), dtype=np.uint32)
+    mode = 1 if do_containment else 2 if do_max_containment else 0
+    rustcall(lib.smgpu_many_need, mode, float(threshold), sizes.ctypes.data_as(C.c_void_p), len(sizes), out.ctypes.data_as(C.c_void_p))
+    return out[:len(sizes)]
 
 
 def prefetch_rows(shared, threshold_bp, scaled):
@@ -345,6 +365,119 @@ class SketchSet(RustObject):
         return [(int(i), int(c)) for i, c in zip(idx, isect)]
 
 
+    # ---- many queries in one pass over the set (csrc/overlap_many.hip) --------------------------------------------------------
+    def _many_hits(self, queries, need):
+        "the hits of `queries` (a SketchSet) against this set whose common count reaches need (an int, or one per query)"
+        if not isinstance(queries, SketchSet):
+            raise TypeError("the queries of a many-query search are a SketchSet")
+        if np.ndim(need) == 0:
+            need_arr, need_all = None, int(need)
+            low = need_all < 1
+        else:
+            need_arr = np.ascontiguousarray(need, dtype=np.int64)
+            if need_arr.shape != (len(queries),):
+                raise ValueError("one count per query is needed")
+            low = bool((need_arr < 1).any())
+            need_arr, need_all = np.minimum(need_arr, 0xffffffff).astype(np.uint32), 1
+        if low or need_all > 0xffffffff:
+            raise ValueError("the common count a hit needs is at least 1")
+        hits = _ManyHits._from_objptr(rustcall(lib.smgpu_sketchset_overlaps_many, self._get_objptr(), queries._get_objptr(),
+                                               need_arr.ctypes.data_as(C.c_void_p) if need_arr is not None else None, need_all))
+        hits._n_queries, hits._n_rows = len(queries), len(self)
+        return hits
+
+    def _sizes_at(self, scaled):
+        "the rows' sizes once downsampled to `scaled`"
+        from .minhash import _get_max_hash_for_scaled
+        out = np.zeros(max(len(self), 1), dtype=np.uint64)
+        self._methodcall(lib.smgpu_sketchset_sizes_at, _get_max_hash_for_scaled(int(scaled)), out.ctypes.data_as(C.c_void_p))
+        return out[:len(self)]
+
+    def overlaps_many(self, queries, min_common=1):
+        """Every row of `queries` (a SketchSet) against every row of this set in one pass over it -> (query, row, common) arrays of
+        the pairs sharing at least min_common hashes (an int, or one value per query; at least 1), ordered by (query, row).  Sets
+        of different scaled meet at the coarser one."""
+        hits = self._many_hits(queries, min_common)
+        return hits.queries, hits.rows, hits.common
+
+    def prefetch_many(self, queries, threshold_bp=0):
+        "[self.prefetch(q, threshold_bp) for q in queries] from one pass over the set: per query [(row, |intersect|)] in row order"
+        if not isinstance(queries, SketchSet):
+            raise TypeError("the queries of a many-query search are a SketchSet")
+        scaled = queries.params[3]
+        if not scaled or not self.params[3]:
+            raise ValueError("prefetch requires scaled signatures")
+        need = float(threshold_bp) / scaled if threshold_bp else 0.0
+        hits = self._many_hits(queries, max(1, int(math.ceil(need))))
+        out = []
+        for rows, common in hits.per_query(len(queries)):
+            keep = (common >= need) & (common > 0)
+            out.append([(int(r), int(c)) for r, c in zip(rows[keep], common[keep])])
+        return out
+
+    def search_many(self, queries, *, threshold=0.0, do_containment=False, do_max_containment=False, best_only=False):
+        """[self.search(q, ...) for q in queries] from one pass over the set: per query [(score, row)] best first.  The device drops
+        the pairs whose common count cannot reach the threshold (many_need); the float test and the ranking are the host's, by the
+        code rank_search_hits uses.  Sets of different scaled are scored at the coarser one (both sizes downsampled)."""
+        if do_containment and do_max_containment:
+            raise TypeError("'do_containment' and 'do_max_containment' cannot both be True")
+        if not isinstance(queries, SketchSet):
+            raise TypeError("the queries of a many-query search are a SketchSet")
+        q_scaled, scaled = queries.params[3], self.params[3]
+        if (do_containment or do_max_containment) and not q_scaled:
+            raise TypeError("this search requires a scaled signature")
+        q_sizes = queries.sizes if q_scaled == scaled else queries._sizes_at(max(q_scaled, scaled))
+        need = many_need(q_sizes, threshold, do_containment=do_containment, do_max_containment=do_max_containment)
+        hits = self._many_hits(queries, need)
+        q_sizes, row_sizes = hits.query_sizes, hits.row_sizes
+        out = []
+        for q, (rows, common) in enumerate(hits.per_query(len(queries))):
+            score = score_hits(common, row_sizes[rows], int(q_sizes[q]), do_containment=do_containment, do_max_containment=do_max_containment)
+            out.append(rank_scored(score, rows, threshold=threshold, best_only=best_only))
+        return out
+
+class _ManyHits(RustObject):
+    "the hits of a many-query pass on the host (smgpu_manyhits_*): arrays ordered by (query, row), sizes at the common scaled"
+    __dealloc_func__ = lib.smgpu_manyhits_free
+
+    def _array(self, func, n, dtype):
+        if not n:
+            return np.zeros(0, dtype=dtype)
+        return np.ctypeslib.as_array(C.cast(func(self._get_objptr()), C.POINTER(C.c_uint32 if dtype == np.uint32 else C.c_uint64)), shape=(n,)).copy()
+
+    def __len__(self):
+        return lib.smgpu_manyhits_len(self._get_objptr())
+
+    queries = property(lambda self: self._array(lib.smgpu_manyhits_queries, len(self), np.uint32))
+    rows = property(lambda self: self._array(lib.smgpu_manyhits_rows, len(self), np.uint32))
+    common = property(lambda self: self._array(lib.smgpu_manyhits_common, len(self), np.uint32))
+    scaled = property(lambda self: lib.smgpu_manyhits_scaled(self._get_objptr()))
+
+    def _sizes(self, func, n):
+        return self._array(func, n, np.uint64)
+
+    @property
+    def query_sizes(self):
+        return self._sizes(lib.smgpu_manyhits_query_sizes, self._n_queries)
+
+    @property
+    def row_sizes(self):
+        return self._sizes(lib.smgpu_manyhits_row_sizes, self._n_rows)
+
+    @property
+    def stats(self):
+        "ms of the index build, the passes, the final sort (device) and the whole call (host); reruns; passes over the collection"
+        out = (C.c_double * 6)()
+        lib.smgpu_manyhits_stats(self._get_objptr(), out)
+        return dict(zip(("build_ms", "kernel_ms", "sort_ms", "call_ms", "reruns", "passes"), out))
+
+    def per_query(self, m):
+        "(rows, common) of query 0, 1, .. m - 1"
+        queries, rows, common = self.queries, self.rows, self.common
+        cut = np.searchsorted(queries, np.arange(m + 1))
+        return [(rows[cut[q]:cut[q + 1]], common[cut[q]:cut[q + 1]]) for q in range(m)]
+
+
 class _DeviceCounter(RustObject):
     "c[d] = |query ∩ D_d| on the GPU (smgpu_counter_*)."
     __dealloc_func__ = lib.smgpu_counter_free
@@ -530,6 +663,74 @@ class Index:
         subj = [flatten_and_downsample_scaled(mh, query_scaled) for _, _, mh in items]
         return (SketchSet(subj) if subj else None), subj
 
+    def _score_shared(self, search_fn, query_mh, items, subj, shared):
+        "the results of find for scaled sketches, from shared[i] = |query ∩ subject i|"
+        skip_zero = _zero_overlap_never_matches(search_fn, len(query_mh))
+        for i, ((ss, loc, _), subj_mh) in enumerate(zip(items, subj)):
+            if skip_zero and not shared[i]:
+                continue
+            # the query is downsampled to the subject's scaled when the subject is coarser (:129-131)
+            q_mh = query_mh if subj_mh.scaled <= query_mh.scaled else flatten_and_downsample_scaled(query_mh, subj_mh.scaled)
+            q_size, s_size = len(q_mh), len(subj_mh)
+            # plain |Q ∩ D| is unchanged by downsampling either side to the coarser scaled
+            n_shared = int(shared[i])
+            total = q_size + s_size - n_shared
+            score = search_fn.score_fn(q_size, n_shared, s_size, total)
+            if search_fn.passes(score) and search_fn.collect(score, ss):
+                yield IndexSearchResult(score, ss, loc)
+
+    def _find_many(self, search_fns, queries):
+        """[list(self.find(search_fns[i], queries[i]))] for scaled queries of one scaled, from ONE pass over the subjects' device CSR
+        (SketchSet.overlaps_many) in place of one pass per query."""
+        queries = list(queries)
+        mhs = []
+        for search_fn, query in zip(search_fns, queries):
+            search_fn.check_is_compatible(query)
+            assert not query.minhash.track_abundance
+            mhs.append(query.minhash)
+        if not queries:
+            return []
+        scaled = mhs[0].scaled
+        if not scaled or any(mh.scaled != scaled for mh in mhs):
+            raise ValueError("a search of many queries takes scaled queries of one scaled")
+        items, pending = self._walk()
+        if not all(mh.scaled for _, _, mh in items):
+            raise ValueError("a search of many queries takes scaled signatures")
+        sset, subj = self._subject_set(scaled, items)
+        out = []
+        if sset is not None:
+            hits = sset._many_hits(SketchSet([mh.flatten() for mh in mhs]), 1)
+            per_query = hits.per_query(len(mhs))
+        for i, (search_fn, mh) in enumerate(zip(search_fns, mhs)):
+            shared = np.zeros(len(items), dtype=np.uint64)
+            if sset is not None:
+                rows, common = per_query[i]
+                shared[rows] = common
+            out.append(list(self._score_shared(search_fn, mh, items, subj, shared)))
+        if pending is not None:
+            raise pending
+        return out
+
+    def search_many(self, queries, *, threshold=None, do_containment=False, do_max_containment=False, best_only=False):
+        "[self.search(q, ...) for q in queries]: the same result objects in the same order, from one pass over the collection"
+        if threshold is None:
+            raise TypeError("'search' requires 'threshold'")
+        queries = list(queries)
+        fns = [make_jaccard_search_query(do_containment=do_containment, do_max_containment=do_max_containment, best_only=best_only,
+                                         threshold=float(threshold)) for _ in queries]
+        out = self._find_many(fns, queries)
+        for matches in out:
+            matches.sort(key=lambda x: -x.score)
+        return out
+
+    def prefetch_many(self, queries, threshold_bp, **kwargs):
+        "[list(self.prefetch(q, threshold_bp)) for q in queries], from one pass over the collection"
+        if not self:
+            raise ValueError("no signatures to search")
+        queries = list(queries)
+        fns = [make_containment_query(q.minhash, threshold_bp, best_only=kwargs.get("best_only", False)) for q in queries]
+        return self._find_many(fns, queries)
+
     def find(self, search_fn, query, **kwargs):
         search_fn.check_is_compatible(query)
         query_mh = query.minhash
@@ -538,19 +739,7 @@ class Index:
         if query_mh.scaled and all(mh.scaled for _, _, mh in items):
             sset, subj = self._subject_set(query_mh.scaled, items)
             shared = sset.overlaps(query_mh) if sset is not None else []
-            skip_zero = _zero_overlap_never_matches(search_fn, len(query_mh))
-            for i, ((ss, loc, _), subj_mh) in enumerate(zip(items, subj)):
-                if skip_zero and not shared[i]:
-                    continue
-                # the query is downsampled to the subject's scaled when the subject is coarser (:129-131)
-                q_mh = query_mh if subj_mh.scaled <= query_mh.scaled else flatten_and_downsample_scaled(query_mh, subj_mh.scaled)
-                q_size, s_size = len(q_mh), len(subj_mh)
-                # plain |Q ∩ D| is unchanged by downsampling either side to the coarser scaled
-                n_shared = int(shared[i])
-                total = q_size + s_size - n_shared
-                score = search_fn.score_fn(q_size, n_shared, s_size, total)
-                if search_fn.passes(score) and search_fn.collect(score, ss):
-                    yield IndexSearchResult(score, ss, loc)
+            yield from self._score_shared(search_fn, query_mh, items, subj, shared)
         else:
             # num sketches (or mixed): per-pair GPU intersections, like the reference loop
             for ss, loc, mh in items:
