@@ -721,6 +721,50 @@ uint64_t smgpu_manyhits_scaled(const SmgpuManyHits *ptr);
 void smgpu_manyhits_stats(const SmgpuManyHits *ptr, double *out6);
 /* Test support: the capacity smgpu_sketchset_overlaps_many first tries (0: its own choice), to see the second run. */
 void smgpu_many_set_first_capacity(uint64_t capacity);
+
+/* ---- gather of many queries against a collection in one call (csrc/gather_many.hip, csrc/gather_many_core.hpp) ----
+ * The reference decomposes many queries against one collection with a loop of GatherDatabases (src/sourmash/search.py:877-949
+ * over CounterGather, src/sourmash/index/__init__.py:735-909).  Here the many-queries pass above finds every query's candidates
+ * (the rows sharing at least max(1, threshold) hashes with it) and one kernel then runs the min-set-cover loops side by side: a
+ * workgroup a query, the counters of its candidates and its uncovered hashes in LDS.  Per query: the largest counter wins a
+ * round (ties: the lowest row), the loop ends at a best counter of 0 or below threshold_hashes, the round's intersect is what
+ * the winner holds of the still-uncovered hashes, and every counter drops by what it shares with that.  Sets of different
+ * scaled meet at the coarser one.
+ * geometry: lanes of a workgroup, and the default caps: the most hashes (<= cutoff) and the most candidates a query may have to
+ * run in that kernel.  workspace_bytes: for m queries with n_hits hits whose common counts sum to total_common. */
+void smgpu_gather_many_geometry(uint32_t *workgroup, uint32_t *max_query_hashes, uint32_t *max_candidates);
+uint64_t smgpu_gather_many_workspace_bytes(uint64_t m, uint64_t n_hits, uint64_t total_common);
+/* Both CSRs in device memory as for smgpu_many_overlap_raw, and the hits that call produced for them, ordered by (query, row);
+ * d_hit_common must be the true common counts at `cutoff` (checked: a row that shares another number of hashes with its query
+ * is an error).  The picks of query q go to [first hit of q, + d_out_rounds[q]) of d_out_rows / d_out_isect, in rank order;
+ * the slots behind them are left untouched.  A query with more than max_query_hashes hashes <= cutoff or more than
+ * max_candidates hits is not run: d_status[q] = 1 and nothing else is written for it (d_status[q] = 0 for the others).  Caps of
+ * 0 mean the defaults; grid: workgroups of the launches (0: the library's numbers).  Returns the total number of rounds.
+ * Synchronises the stream.  UINT64_MAX with an error set: a refused argument (caps beyond what LDS holds, grid above 1048576, a
+ * null pointer, a workspace smaller than smgpu_gather_many_workspace_bytes says, 2^32 rows or hits), or no device. */
+uint64_t smgpu_gather_many_raw(const uint64_t *d_qhashes, const uint64_t *d_qoffsets, uint64_t m,
+                               const uint64_t *d_hashes, const uint64_t *d_offsets, uint64_t n_rows,
+                               const uint32_t *d_hit_queries, const uint32_t *d_hit_rows, const uint32_t *d_hit_common,
+                               uint64_t n_hits, uint64_t cutoff, uint64_t threshold_hashes,
+                               uint32_t max_query_hashes, uint32_t max_candidates, uint32_t grid,
+                               uint32_t *d_out_rows, uint32_t *d_out_isect, uint32_t *d_out_rounds, uint32_t *d_status,
+                               void *d_workspace, uint64_t workspace_bytes, void *stream);
+/* [gather(query q of `queries`) against `db` for every q]: compatibility as for smgpu_sketchset_overlaps_many.  Queries are run
+ * in contiguous batches whose forward lists stay under a budget; a query beyond a cap runs through the one-query path
+ * (smgpu_counter_new / smgpu_counter_gather on the resident buffers), so the answer is always complete.  The getters borrow from
+ * the handle: offsets (m + 1 entries) into rows / isect, the picks of a query in rank order, and the common scaled; stats:
+ * out[0 .. 4) ms of the candidate pass, the fill, the sort and the rounds kernel (device), [4] ms of the one-query way out and
+ * [5] of the whole call (host), [6] queries that took the way out, [7] batches. */
+typedef struct SmgpuManyGather SmgpuManyGather;
+SmgpuManyGather *smgpu_sketchset_gather_many(const SmgpuSketchSet *db, const SmgpuSketchSet *queries, uint64_t threshold_hashes);
+void            smgpu_manygather_free(SmgpuManyGather *ptr);
+const uint64_t *smgpu_manygather_offsets(const SmgpuManyGather *ptr);   /* m + 1 */
+const uint32_t *smgpu_manygather_rows(const SmgpuManyGather *ptr);
+const uint32_t *smgpu_manygather_isect(const SmgpuManyGather *ptr);
+uint64_t        smgpu_manygather_scaled(const SmgpuManyGather *ptr);
+void            smgpu_manygather_stats(const SmgpuManyGather *ptr, double *out8);
+/* Test support: the caps and the batch budget smgpu_sketchset_gather_many works with (0: the default of each). */
+void smgpu_gather_many_set_limits(uint32_t max_query_hashes, uint32_t max_candidates, uint64_t batch_common);
 SmgpuCounter *smgpu_counter_new(const SmgpuSketchSet *set, const SourmashKmerMinHash *query);
 void smgpu_counter_free(SmgpuCounter *ptr);
 void smgpu_counter_get(const SmgpuCounter *ptr, uint64_t *counts_out);

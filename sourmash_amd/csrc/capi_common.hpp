@@ -131,5 +131,22 @@ struct SketchSet {
     // (the device blocks are arena blocks and go back to the arena with the DevBufs: no hipFree, which would synchronise the device)
 };
 
+// ---- helpers of the many-queries unit (capi_many.cpp) and the gather unit (capi_gather.cpp) that the gather-many unit uses too
+// throws the reference's mismatch error for two sets that cannot meet (many_core.hpp: many_compat_code)
+void check_sets_compatible(const SketchSet& db, const SketchSet& q);
+// the hits of the many-queries pass left on the device, ordered by (query, row); ms3: index build, passes, final sort
+struct ManyDeviceHits {
+    AsyncBuf queries, rows, common;
+    uint64_t hits = 0, reruns = 0;
+    float ms3[3] = {0.f, 0.f, 0.f};
+};
+// every row of qs against every row of db at `cutoff`, d_need[q] the count a hit of query q needs; runs again once when the hits
+// did not fit the first capacity
+void many_hits_on_device(const SketchSet& db, const SketchSet& qs, const uint32_t* d_need, uint64_t cutoff, ManyDeviceHits& out, hipStream_t st);
+// One query that is resident on the device (d_query[0, nq), ascending) against a resident set by the one-query path: index build,
+// arm, rounds to exhaustion.  -> rounds; idx / isect: the winners' rows and |intersect| in rank order.
+uint64_t gather_one_on_device(const uint64_t* d_query, uint64_t nq, const SketchSet& db, uint64_t threshold_hashes, std::vector<uint64_t>& idx,
+                              std::vector<uint64_t>& isect, hipStream_t st);
+
 }  // namespace smg
 #pragma GCC visibility pop

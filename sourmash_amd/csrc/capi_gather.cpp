@@ -177,6 +177,26 @@ static void select_pair(const uint64_t* d_a, uint64_t na, const uint64_t* d_b, u
 
 }  // namespace
 
+uint64_t smg::gather_one_on_device(const uint64_t* d_query, uint64_t nq, const SketchSet& db, uint64_t threshold_hashes, std::vector<uint64_t>& idx,
+                                   std::vector<uint64_t>& isect, hipStream_t st) {
+    GatherRaw r;
+    r.g.Q = d_query;
+    r.g.nq = nq;
+    r.g.hashes = db.hashes.as<uint64_t>();
+    r.g.offsets = db.offsets.as<uint64_t>();
+    r.g.ndb = db.n;
+    r.g.index_base = 0;
+    hip_check(gather_build(r.g, st), "gather index");
+    hip_check(gather_begin(r.g, threshold_hashes, db.n ? db.n : 1, st), "gather arm");
+    const uint64_t cap = db.n ? db.n : 1;
+    idx.assign(cap, 0);
+    isect.assign(cap, 0);
+    const uint64_t rounds = gather_drain(r.g, idx.data(), isect.data(), cap, st);
+    idx.resize((size_t)std::min(rounds, cap));
+    isect.resize(idx.size());
+    return rounds;
+}
+
 extern "C" {
 
 SmgpuCounter* smgpu_counter_new(const SmgpuSketchSet* set, const SourmashKmerMinHash* query) {

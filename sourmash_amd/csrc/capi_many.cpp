@@ -22,8 +22,14 @@ struct ManyHits {
 
 std::atomic<uint64_t> g_first_capacity{0};                    // test support: smgpu_many_set_first_capacity
 
+void check_raw(const void* p, const char* what) {
+    if (!p) throw err_internal(std::string("smgpu_many_overlap_raw: null pointer (") + what + ")");
+}
+
+}  // namespace
+
 // the reference's order (check_compatible, minhash.rs:886-912): ksize, hash function, max_hash only when a side is num, seed
-void check_sets_compatible(const SketchSet& db, const SketchSet& q) {
+void smg::check_sets_compatible(const SketchSet& db, const SketchSet& q) {
     if (db.ksize == 0 || q.ksize == 0) throw err_internal("the set's sketches do not share one set of parameters");
     // (a set keeps its ksize in residues; the reference compares the sketches' own, three times that for the amino acid alphabets)
     auto params = [](const SketchSet& s) { return ManyParams{s.ksize * (s.hash_function == HF_DNA ? 1u : 3u), s.hash_function, s.seed, s.max_hash, s.num}; };
@@ -37,11 +43,30 @@ void check_sets_compatible(const SketchSet& db, const SketchSet& q) {
     }
 }
 
-void check_raw(const void* p, const char* what) {
-    if (!p) throw err_internal(std::string("smgpu_many_overlap_raw: null pointer (") + what + ")");
+// Room for the hits: a few per query and row is what a thresholded search leaves; every pair at most.  A result that does not fit
+// reports its size, and the second run has exactly that room.
+void smg::many_hits_on_device(const SketchSet& db, const SketchSet& qs, const uint32_t* d_need, uint64_t cutoff, ManyDeviceHits& out, hipStream_t st) {
+    const uint64_t m = qs.n, n = db.n;
+    const uint64_t all_pairs = m * n;
+    uint64_t cap = g_first_capacity.load();
+    if (cap == 0) cap = std::max<uint64_t>(1u << 20, 8 * (m + n));
+    cap = std::min<uint64_t>(cap, all_pairs);
+    AsyncBuf d_result(64, st), ws;
+    for (int attempt = 0;; ++attempt) {
+        if (cap >= 0xffffffffull) throw err_internal("smgpu_sketchset_overlaps_many: 2^32 hits or more; raise the counts the hits need");
+        out.queries.reset(cap * 4 + 16, st); out.rows.reset(cap * 4 + 16, st); out.common.reset(cap * 4 + 16, st);
+        const uint64_t ws_bytes = many_overlap_workspace_bytes(m, qs.total, cap);
+        ws.reset((size_t)ws_bytes, st);
+        const ManyArgs a{qs.hashes.as<uint64_t>(), qs.offsets.as<uint64_t>(), m, qs.total, db.hashes.as<uint64_t>(), db.offsets.as<uint64_t>(), n,
+                         d_need, cutoff, 0, 0, out.queries.as<uint32_t>(), out.rows.as<uint32_t>(), out.common.as<uint32_t>(), cap,
+                         d_result.as<uint64_t>(), ws.p, ws_bytes};
+        hip_check(many_overlap_run(a, &out.hits, out.ms3, st), "many_overlap");
+        if (out.hits <= cap) break;
+        if (attempt) throw err_internal("smgpu_sketchset_overlaps_many: the second run found more hits than the first");
+        cap = out.hits;
+        out.reruns = 1;
+    }
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -134,7 +159,7 @@ SmgpuManyHits* smgpu_sketchset_overlaps_many(const SmgpuSketchSet* db_p, const S
         h->query_sizes.assign(m, 0);
         h->row_sizes.assign(n, 0);
         if (m == 0 || n == 0) return reinterpret_cast<SmgpuManyHits*>(h.release());
-        AsyncBuf d_qsizes(m * 8, st), d_rsizes(n * 8, st), d_need(m * 4, st), d_result(64, st);
+        AsyncBuf d_qsizes(m * 8, st), d_rsizes(n * 8, st), d_need(m * 4, st);
         hip_check(many_sizes_launch(qs->hashes.as<uint64_t>(), qs->offsets.as<uint64_t>(), m, h->max_hash, d_qsizes.as<uint64_t>(), st), "many_sizes");
         hip_check(many_sizes_launch(db->hashes.as<uint64_t>(), db->offsets.as<uint64_t>(), n, h->max_hash, d_rsizes.as<uint64_t>(), st), "many_sizes");
         hip_check(hipMemcpyAsync(h->query_sizes.data(), d_qsizes.p, m * 8, hipMemcpyDeviceToHost, st), "D2H");
@@ -142,30 +167,12 @@ SmgpuManyHits* smgpu_sketchset_overlaps_many(const SmgpuSketchSet* db_p, const S
         std::vector<uint32_t> need_v(need ? need : nullptr, need ? need + m : nullptr);
         if (!need) need_v.assign(m, need_all);
         hip_check(hipMemcpyAsync(d_need.p, need_v.data(), m * 4, hipMemcpyHostToDevice, st), "H2D");
-        // Room for the hits: a few per query and row is what a thresholded search leaves; every pair at most.  A result that does
-        // not fit reports its size, and the second run has exactly that room.
-        const uint64_t all_pairs = m * n;
-        uint64_t cap = g_first_capacity.load();
-        if (cap == 0) cap = std::max<uint64_t>(1u << 20, 8 * (m + n));
-        cap = std::min<uint64_t>(cap, all_pairs);
-        uint64_t hits = 0;
-        AsyncBuf d_q, d_r, d_c, ws;
-        for (int attempt = 0;; ++attempt) {
-            if (cap >= 0xffffffffull) throw err_internal("smgpu_sketchset_overlaps_many: 2^32 hits or more; raise the counts the hits need");
-            d_q.reset(cap * 4 + 16, st); d_r.reset(cap * 4 + 16, st); d_c.reset(cap * 4 + 16, st);
-            const uint64_t ws_bytes = many_overlap_workspace_bytes(m, qs->total, cap);
-            ws.reset((size_t)ws_bytes, st);
-            const ManyArgs a{qs->hashes.as<uint64_t>(), qs->offsets.as<uint64_t>(), m, qs->total, db->hashes.as<uint64_t>(), db->offsets.as<uint64_t>(), n,
-                             d_need.as<uint32_t>(), h->max_hash, 0, 0, d_q.as<uint32_t>(), d_r.as<uint32_t>(), d_c.as<uint32_t>(), cap,
-                             d_result.as<uint64_t>(), ws.p, ws_bytes};
-            float ms3[3];
-            hip_check(many_overlap_run(a, &hits, ms3, st), "many_overlap");
-            for (int i = 0; i < 3; ++i) h->ms[i] = ms3[i];
-            if (hits <= cap) break;
-            if (attempt) throw err_internal("smgpu_sketchset_overlaps_many: the second run found more hits than the first");
-            cap = hits;
-            h->reruns = 1;
-        }
+        ManyDeviceHits H;
+        many_hits_on_device(*db, *qs, d_need.as<uint32_t>(), h->max_hash, H, st);
+        for (int i = 0; i < 3; ++i) h->ms[i] = H.ms3[i];
+        h->reruns = H.reruns;
+        const uint64_t hits = H.hits;
+        AsyncBuf &d_q = H.queries, &d_r = H.rows, &d_c = H.common;
         h->passes = many_overlap_passes(m, 0);
         h->queries.resize(hits); h->rows.resize(hits); h->common.resize(hits);
         if (hits) {

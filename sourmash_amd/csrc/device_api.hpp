@@ -174,6 +174,40 @@ hipError_t many_overlap_run(const ManyArgs& args, uint64_t* hits, float* ms3, hi
 // d_sizes[r] = hashes of row r that are <= cutoff (a set's sizes at the common scaled)
 hipError_t many_sizes_launch(const uint64_t* d_hashes, const uint64_t* d_offsets, uint64_t n, uint64_t cutoff, uint64_t* d_sizes, hipStream_t stream);
 
+// ---- gather_many.hip (the min-set-cover loop for many small queries, one workgroup a query; gather_many_core.hpp holds its rules) ----
+// The queries [q_base, q_base + m) of a call: d_qoffsets points at THEIR m + 1 offsets (into d_qhashes), the hits are those of
+// many_overlap_run for them -- ordered by (query, row), query numbers starting at q_base -- and d_out_rounds / d_status have one
+// entry per query of the range.  The picks of a query go to the slots of its own hits in d_out_rows / d_out_isect, in rank order:
+// [its first hit, + d_out_rounds[q]).  d_status[q] = 1: the query is beyond a cap and nothing was written for it.  Caps of 0 mean
+// the defaults; grid: workgroups of the fill and the rounds (0: the launcher's own numbers).
+struct GatherManyArgs {
+    const uint64_t *d_qhashes, *d_qoffsets;
+    uint64_t m;
+    uint32_t q_base;
+    const uint64_t *d_hashes, *d_offsets;
+    uint64_t n_rows;
+    const uint32_t *d_hit_queries, *d_hit_rows, *d_hit_common;
+    uint64_t n_hits;
+    uint64_t cutoff, threshold_hashes;
+    uint32_t max_query_hashes, max_candidates, grid;
+    uint32_t *d_out_rows, *d_out_isect, *d_out_rounds, *d_status;
+    void* d_workspace;
+    uint64_t workspace_bytes;
+};
+// what a run can find wrong with its input beside a HIP error: the forward CSR did not come out as long as the hits' common counts
+// say (the hits are not those of these sets), 2^32 entries or more, or a workspace smaller than the entries need
+enum GatherManyTrouble : uint32_t { GM_OK = 0, GM_FILL_MISMATCH = 1, GM_TOO_MANY_ENTRIES = 2, GM_WORKSPACE_TOO_SMALL = 3 };
+// total_common: the sum of the hits' common counts over the queries within the caps (the entries of the forward CSR)
+size_t gather_many_workspace_bytes(uint64_t m, uint64_t n_hits, uint64_t total_common);
+// Synchronises the stream.  *total_rounds = picks of all queries that ran; ms3 (may be null): milliseconds of the fill (with the
+// scan in front of it), the sort, and the rounds.  hipErrorInvalidValue: an argument smgpu_gather_many_raw refuses.
+hipError_t gather_many_run(const GatherManyArgs& args, uint64_t* total_rounds, uint32_t* trouble, float* ms3, hipStream_t stream);
+// Per query of a whole call (q_base = 0): d_qlo[0 .. m] its first hit, d_qn its hashes <= cutoff, d_status as above, d_sums the sum
+// of common over its hits.  Asynchronous.
+hipError_t gather_many_plan(const uint64_t* d_qhashes, const uint64_t* d_qoffsets, uint64_t m, const uint32_t* d_hit_queries,
+                            const uint32_t* d_hit_common, uint64_t n_hits, uint64_t cutoff, uint32_t max_query_hashes, uint32_t max_candidates,
+                            uint32_t* d_qlo, uint32_t* d_qn, uint32_t* d_status, uint64_t* d_sums, hipStream_t stream);
+
 // ---- synth.hip --------------------------------------------------------------------
 hipError_t synth_dna_launch(uint8_t* d_out, uint64_t start, uint64_t n, uint64_t seed, uint64_t record_len,
                             hipStream_t stream);

@@ -436,6 +436,58 @@ class SketchSet(RustObject):
             out.append(rank_scored(score, rows, threshold=threshold, best_only=best_only))
         return out
 
+    # ---- gather of many queries in one call (csrc/gather_many.hip) -------------------------------------------------------------
+    def _many_gather(self, queries, threshold_bp):
+        if not isinstance(queries, SketchSet):
+            raise TypeError("the queries of a many-query search are a SketchSet")
+        # search.py:15-37: the loop stops below threshold_bp / scaled hashes, taken at the scaled the two sets meet at (a set that
+        # is not scaled is refused by the call itself, in the order overlaps_many checks two sets)
+        common_scaled = max(queries.params[3], self.params[3])
+        thr = math.ceil(float(threshold_bp) / common_scaled) if threshold_bp and common_scaled else 0
+        res = _ManyGather._from_objptr(rustcall(lib.smgpu_sketchset_gather_many, self._get_objptr(), queries._get_objptr(), int(thr)))
+        res._n_queries = len(queries)
+        return res
+
+    def gather_many(self, queries, threshold_bp=0):
+        """[self.gather(q, threshold_bp) for q in queries] from one call: per query [(row, |intersect|)] in rank order.  One pass over
+        the set finds every query's candidates, then the min-set-cover loops of all queries run side by side on the GPU, a
+        workgroup a query.  Sets of different scaled meet at the coarser one (both sides downsampled)."""
+        return self._many_gather(queries, threshold_bp).per_query()
+
+
+class _ManyGather(RustObject):
+    "the picks of a many-query gather on the host (smgpu_manygather_*): offsets per query into rows / isect, in rank order"
+    __dealloc_func__ = lib.smgpu_manygather_free
+    _n_queries = 0
+
+    def _array(self, func, n, ctype, dtype):
+        if not n:
+            return np.zeros(0, dtype=dtype)
+        return np.ctypeslib.as_array(C.cast(func(self._get_objptr()), C.POINTER(ctype)), shape=(n,)).copy()
+
+    @property
+    def offsets(self):
+        return self._array(lib.smgpu_manygather_offsets, self._n_queries + 1, C.c_uint64, np.uint64)
+
+    scaled = property(lambda self: lib.smgpu_manygather_scaled(self._get_objptr()))
+
+    @property
+    def stats(self):
+        """ms of the candidate pass, the fill, the sort and the rounds kernel (device), of the one-query way out and of the whole
+        call (host); queries that took the way out; batches"""
+        out = (C.c_double * 8)()
+        lib.smgpu_manygather_stats(self._get_objptr(), out)
+        return dict(zip(("candidates_ms", "fill_ms", "sort_ms", "rounds_ms", "way_out_ms", "call_ms", "way_out_queries", "batches"), out))
+
+    def per_query(self):
+        "[(row, |intersect|)] in rank order for query 0, 1, .."
+        off = self.offsets
+        total = int(off[-1]) if len(off) else 0
+        rows = self._array(lib.smgpu_manygather_rows, total, C.c_uint32, np.uint32).tolist()
+        isect = self._array(lib.smgpu_manygather_isect, total, C.c_uint32, np.uint32).tolist()
+        return [list(zip(rows[int(off[q]):int(off[q + 1])], isect[int(off[q]):int(off[q + 1])])) for q in range(self._n_queries)]
+
+
 class _ManyHits(RustObject):
     "the hits of a many-query pass on the host (smgpu_manyhits_*): arrays ordered by (query, row), sizes at the common scaled"
     __dealloc_func__ = lib.smgpu_manyhits_free
@@ -868,6 +920,50 @@ class LinearIndex(Index):
         if self._packed is None or self._packed[0] != key:
             self._packed = (key,) + Index._subject_set(self, query_scaled, items)
         return self._packed[1], self._packed[2]
+
+    def gather_many(self, queries, threshold_bp=0):
+        """[self.counter_gather(q, threshold_bp).gather_all(threshold_bp) for q in queries]: per query [(md5, |intersect|)] in rank
+        order.  One native call (SketchSet.gather_many over the subjects' device CSR) when the queries are flat, scaled and of one
+        scaled and every subject is at that scaled once flattened and downsampled; otherwise that loop itself.  What the loop
+        raises -- an empty index, an empty query, an unattainable threshold_bp -- is raised for the first offending query, before
+        any device work."""
+        queries = list(queries)
+
+        def loop():
+            return [self.counter_gather(q, threshold_bp).gather_all(threshold_bp) for q in queries]
+        mhs = [q.minhash for q in queries]
+        if not queries or not all(mh.scaled and not mh.track_abundance for mh in mhs) or any(mh.scaled != mhs[0].scaled for mh in mhs):
+            return loop()
+        scaled = mhs[0].scaled
+        items, pending = self._walk()
+
+        def meets(mh):
+            "the sketch can stand in one set with the first query: the same parameters, and not coarser"
+            return mh.scaled and mh.scaled <= scaled and (mh.ksize, mh.moltype, mh.seed) == (mhs[0].ksize, mhs[0].moltype, mhs[0].seed)
+        if not all(meets(mh) for mh in mhs) or not all(meets(mh) for _, _, mh in items):
+            return loop()                                           # (whatever a mismatch raises, the loop raises it)
+        for i, (query, mh) in enumerate(zip(queries, mhs)):
+            # what counter_gather checks on the host, in its order (the counter takes any scaled query): the index, then the
+            # prefetch's search object
+            if not self:
+                raise ValueError("no signatures to search")
+            make_containment_query(mh, threshold_bp, best_only=False).check_is_compatible(query)
+            if i == 0 and pending is not None:
+                raise pending                                       # (the walk of the first query's prefetch ends on it)
+        sset, _ = self._subject_set(scaled, items)
+        # The prefetch inside counter_gather keeps a subject by a float containment test, the device by the integer count
+        # ceil(threshold_bp / scaled).  Correctly rounded division by the same positive len(query) is monotone, so the two can only
+        # disagree on a subject whose count is below the integer threshold: never picked, and it changes no other counter.  Subjects
+        # with the same md5 are one entry of the counter; as rows the later one falls to 0 with the first and is never picked.
+        picks = sset.gather_many(SketchSet([mh.flatten() for mh in mhs]), threshold_bp)
+        md5 = {}
+        out = []
+        for rows in picks:
+            for row, _ in rows:
+                if row not in md5:
+                    md5[row] = items[row][0].md5sum()
+            out.append([(md5[row], n) for row, n in rows])
+        return out
 
 
 class CounterGather:
