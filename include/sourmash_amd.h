@@ -372,6 +372,38 @@ void smgpu_sigjson_parse_raw(const uint8_t *d_text, uint64_t text_len, const uin
  * start, one kernel pass per sketch covers all records.  Names are the header lines behind '>' / '@'.  *n = records.  Returns
  * an array of *n signature handles (ownership as for smgpu_sketch_files). */
 SourmashSignature **smgpu_sketch_file_singleton(const char *path, const SourmashComputeParameters *params, uintptr_t *n);
+/* The same for files sketched with protein / dayhoff / hp parameters (`sourmash sketch protein --singleton`, input_is_protein != 0:
+ * records are residues; `sourmash sketch translate --singleton`, input_is_protein == 0: records are DNA, translated in six frames):
+ * scaled, stored ksizes of 3 x (1 .. 79 residues).  A template that mixes molecule types runs one pass per sketch over the same
+ * parsed buffer; a DNA sketch in it (translated input only) takes the pass of smgpu_sketch_file_singleton. */
+SourmashSignature **smgpu_sketch_file_singleton_residues(const char *path, const SourmashComputeParameters *params,
+                                                         int32_t input_is_protein, uintptr_t *n);
+/* ---- one protein / dayhoff / hp sketch per record (csrc/protein_records.hip; src/core/src/signature.rs:257-261, 307-393) ----
+ * Records with explicit ends: record r is the bytes [d_starts[r], d_ends[r]) of d_seq with d_starts[r] <= d_ends[r] <=
+ * d_starts[r + 1]; d_ends NULL: d_ends[r] = d_starts[r + 1], records touch.  The bytes between d_ends[r] and d_starts[r + 1]
+ * -- the byte a file parser leaves between two records -- belong to no record.  translate == 0: the records are residues, a
+ * window of ksize residues counts for the record it lies in entirely.  translate != 0: the records are DNA, each translated in
+ * six frames by itself (frames 0..2 forward and on the record's reverse complement, a trailing partial codon dropped, no
+ * validity test; a record below 3 x ksize bases gives nothing).
+ * Scratch size of smgpu_sketch_residue_records_raw for a capacity of kept (hash, position) pairs and a buffer of len bytes. */
+uint64_t smgpu_sketch_residue_records_workspace_bytes(uint64_t pair_capacity, uint64_t n_records, uint64_t len, int32_t translate);
+/* The contract of smgpu_sketch_records_raw -- the same d_result words, the same errors for refused starts, the same capacity
+ * error -- for windows of ksize residues (1 .. 79) hashed as hash_function says (2 protein, 3 dayhoff, 4 hp).  One more error:
+ * a d_ends[r] outside [d_starts[r], d_starts[r + 1]] (d_result[3] & 4).  d_workspace must be 8-byte aligned.  Synchronises the
+ * stream three times (the records are checked before anything reads what they say). */
+uint64_t smgpu_sketch_residue_records_raw(const uint8_t *d_seq, uint64_t len, const uint64_t *d_starts, const uint64_t *d_ends,
+                                          uint64_t n_records, uint32_t ksize, uint32_t hash_function, int32_t translate,
+                                          uint64_t seed, uint64_t max_hash, uint64_t *d_hashes, uint64_t *d_abunds,
+                                          uint64_t capacity, uint64_t *d_offsets, uint64_t *d_result, void *d_workspace,
+                                          uint64_t workspace_bytes, void *stream);
+/* Only its window kernel, for measurements: d_aa[0,n) is a residue buffer (8-byte aligned, readable in whole 8-byte words), every
+ * kept hash of a window of ksize residues is appended unordered to d_hashes and the window's start to d_positions; the count is
+ * added to *d_count (device u64, caller zeroes).  d_n (device u64, NULL: n) is the buffer's size where only the device knows it;
+ * with it 0xFF bytes separate, as in the translated buffer.  d_positions NULL: the hash-only kernel of the record-by-record route
+ * (0xFF bytes separate) on the same buffer.  Fully asynchronous. */
+void smgpu_residue_records_kernel_raw(const uint8_t *d_aa, uint64_t n, const uint64_t *d_n, uint32_t ksize, uint64_t seed,
+                                      uint64_t max_hash, uint64_t *d_hashes, uint64_t *d_positions, uint64_t capacity,
+                                      uint64_t *d_count, void *stream);
 /* Only the k-mer kernel (no sort): appends kept hashes unordered to d_out, adds the
  * count to *d_count (device u64, caller zeroes).  Fully asynchronous. */
 void smgpu_sketch_dna_kernel_raw(const uint8_t *d_seq, uint64_t len, uint32_t ksize, uint64_t seed, uint64_t max_hash,
@@ -569,6 +601,14 @@ SmgpuSketchSet *smgpu_sketchset_sketch_records(const uint8_t *d_seq, uint64_t le
 /* The records of a FASTA / FASTQ file (plain or gzip, at most 2 GiB of text) as such a set; the manifest rows carry each
  * record's name and the file name. */
 SmgpuSketchSet *smgpu_sketchset_sketch_file(const char *path, uint32_t ksize, uint64_t seed, uint64_t scaled);
+/* The same for protein / dayhoff / hp sketches (smgpu_sketch_residue_records_raw describes records, ksize -- in residues, 1 .. 79
+ * -- hash_function and translate): the set carries hash_function, its manifest rows say protein / dayhoff / hp. */
+SmgpuSketchSet *smgpu_sketchset_sketch_residue_records(const uint8_t *d_seq, uint64_t len, const uint64_t *d_starts,
+                                                       const uint64_t *d_ends, uint64_t n_records, uint32_t ksize,
+                                                       uint32_t hash_function, int32_t translate, uint64_t seed, uint64_t scaled);
+/* The records of a FASTA / FASTQ file as such a set: a record ends in front of the next record's header line. */
+SmgpuSketchSet *smgpu_sketchset_sketch_residue_file(const char *path, uint32_t ksize, uint32_t hash_function, int32_t translate,
+                                                    uint64_t seed, uint64_t scaled);
 /* ---- a sketch's k-mers in sequences (csrc/sketch_find.hip; `sourmash sig kmers`, src/sourmash/sig/__main__.py:1087-1310) ----
  * The way back from a sketch to the sequences it came from: every position of a buffer or a file whose k-mer hashes into a
  * query, by record.  The query is the union of n compatible flat scaled DNA sketches, merged as the reference merges them

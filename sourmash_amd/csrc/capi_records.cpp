@@ -111,15 +111,33 @@ void sketch_records_csr(const uint8_t* d_seq, uint64_t len, const uint64_t* d_st
     }
 }
 
+// a set that takes over the blocks of a CSR; ksize in units of the molecule
+SketchSet* sketchset_of_csr(RecordsCsr& csr, uint64_t n_records, uint32_t ksize, uint32_t hf, uint64_t seed, uint64_t scaled, hipStream_t st);
+// sketch_records_csr for residue windows (below, with its pass)
+void residue_records_csr(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, const uint64_t* d_ends, uint64_t n_records, uint32_t ksize,
+                         uint32_t hf, bool translate, uint64_t seed, uint64_t max_hash, bool want_abunds, RecordsCsr& out, hipStream_t st);
+
 SketchSet* sketchset_from_records(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, uint64_t n_records, uint32_t ksize, uint64_t seed,
                                   uint64_t scaled, hipStream_t st) {
     if (scaled == 0) throw err_internal("per-record sketches are scaled sketches: scaled must not be 0");
-    std::unique_ptr<SketchSet> s(new SketchSet());
     RecordsCsr csr;
+    sketch_records_csr(d_seq, len, d_starts, n_records, ksize, seed, max_hash_for_scaled(scaled), false, csr, st);
+    return sketchset_of_csr(csr, n_records, ksize, HF_DNA, seed, scaled, st);
+}
+
+SketchSet* sketchset_from_residue_records(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, const uint64_t* d_ends, uint64_t n_records,
+                                          uint32_t ksize, uint32_t hf, bool translate, uint64_t seed, uint64_t scaled, hipStream_t st) {
+    if (scaled == 0) throw err_internal("per-record sketches are scaled sketches: scaled must not be 0");
+    RecordsCsr csr;
+    residue_records_csr(d_seq, len, d_starts, d_ends, n_records, ksize, hf, translate, seed, max_hash_for_scaled(scaled), false, csr, st);
+    return sketchset_of_csr(csr, n_records, ksize, hf, seed, scaled, st);
+}
+
+SketchSet* sketchset_of_csr(RecordsCsr& csr, uint64_t n_records, uint32_t ksize, uint32_t hf, uint64_t seed, uint64_t scaled, hipStream_t st) {
+    std::unique_ptr<SketchSet> s(new SketchSet());
     const uint64_t max_hash = max_hash_for_scaled(scaled);
-    sketch_records_csr(d_seq, len, d_starts, n_records, ksize, seed, max_hash, false, csr, st);
     s->n = n_records; s->total = csr.total;
-    s->ksize = ksize; s->hash_function = HF_DNA; s->seed = seed; s->max_hash = max_hash; s->num = 0;
+    s->ksize = ksize; s->hash_function = hf; s->seed = seed; s->max_hash = max_hash; s->num = 0;
     s->host_offsets.assign(n_records + 1, 0);
     hip_check(hipMemcpyAsync(s->host_offsets.data(), csr.offsets.p, (n_records + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
     hip_check(hipStreamSynchronize(st), "sync");
@@ -128,10 +146,92 @@ SketchSet* sketchset_from_records(const uint8_t* d_seq, uint64_t len, const uint
     s->rows.resize(n_records);
     for (uint64_t r = 0; r < n_records; ++r) {
         ManifestRow& m = s->rows[r];
-        m.ksize = ksize; m.moltype = "DNA"; m.scaled = scaled;
+        m.ksize = ksize; m.moltype = molecule_name(hf); m.scaled = scaled;
         m.n_hashes = s->host_offsets[r + 1] - s->host_offsets[r];
     }
     return s.release();
+}
+
+// ---- one protein / dayhoff / hp sketch per record (protein_records.hip) -------------------------------------------------------
+constexpr uint32_t RESIDUE_RECORDS_MAX_K = 79;                      // the register-window form (residue_core.hpp: RW_MAX_NB)
+
+// bytes of the residue buffer of a pass: protein input, the input's own; translated, the bound of the records' blocks
+uint64_t residue_buffer_bytes(uint64_t len, uint64_t n_records, bool translate) {
+    return al256((translate ? translated_records_bytes_bound(len, n_records) : len) + 64);
+}
+uint64_t residue_records_workspace(uint64_t cap, uint64_t n_records, uint64_t len, bool translate) {
+    return 2 * al256(cap * 8) + al256(records_csr_temp_bytes(cap)) + residue_buffer_bytes(len, n_records, translate) +
+           (translate ? al256((n_records + 2) * 8) + al256(translate_records_temp_bytes(n_records)) : 0) + 512;
+}
+
+// The pass of sketch_records_run for residue windows: d_result, the starts' errors, the capacity error and `exceeded` as there;
+// d_result[3] & 4: an end outside its record.  The workspace behind the pairs and the CSR scratch: [residue buffer][translated:
+// block starts, n_records + 1 u64][translated: the scan's scratch].
+uint64_t residue_records_run(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, const uint64_t* d_ends, uint64_t n_records, uint32_t ksize,
+                             uint32_t hf, bool translate, uint64_t seed, uint64_t max_hash, uint64_t* d_hashes, uint64_t* d_abunds, uint64_t cap,
+                             uint64_t* d_offsets, uint64_t* d_result, void* d_ws, uint64_t ws_bytes, hipStream_t st, uint64_t* exceeded) {
+    if (ksize < 1 || ksize > RESIDUE_RECORDS_MAX_K)
+        throw err_internal("per-record residue sketches take ksize 1 .. 79 residues, not " + std::to_string(ksize));
+    if (hf != HF_PROTEIN && hf != HF_DAYHOFF && hf != HF_HP) throw err_internal("per-record residue sketches are protein, dayhoff or hp sketches");
+    check_pass_arguments(d_starts, n_records, cap, ws_bytes, residue_records_workspace(cap, n_records, len, translate),
+                         "smgpu_sketch_residue_records_workspace_bytes");
+    if (reinterpret_cast<uintptr_t>(d_ws) % 8) throw err_internal("smgpu_sketch_residue_records_raw: the workspace must be 8-byte aligned");
+    const PairWorkspace ws(d_ws, ws_bytes, cap);
+    char* at = (char*)ws.d_tmp;
+    void* d_csr_tmp = at;
+    const size_t csr_bytes = al256(records_csr_temp_bytes(cap));
+    at += csr_bytes;
+    uint8_t* d_aa = (uint8_t*)at;
+    at += residue_buffer_bytes(len, n_records, translate);
+    uint64_t* d_blocks = (uint64_t*)at;
+    void* d_scan = at + al256((n_records + 2) * 8);
+    hip_check(hipMemsetAsync(d_result, 0, 32, st), "memset");
+    hip_check(records_check_starts_launch(d_starts, n_records, len, (unsigned long long*)d_result + 3, st), "record starts");
+    if (d_ends) hip_check(records_check_ends_launch(d_starts, d_ends, n_records, (unsigned long long*)d_result + 3, st), "record ends");
+    unsigned long long head[4] = {0, 0, 0, 0};
+    hip_check(hipMemcpyAsync(head, d_result, 32, hipMemcpyDeviceToHost, st), "D2H");
+    hip_check(hipStreamSynchronize(st), "sync");                    // the translation reads what the records say: checked first
+    raise_bad_starts(head, len);
+    if (head[3] & 4) throw err_internal("record ends: an end lies outside its record, [starts[r], starts[r + 1]]");
+    const uint64_t thr = max_hash ? max_hash : ~0ull;
+    if (translate) {
+        hip_check(translate_records_launch(d_seq, len, d_starts, d_ends, n_records, hf, d_blocks, d_aa, d_scan, al256(translate_records_temp_bytes(n_records)), st),
+                  "translate_records");
+        if (n_records)
+            hip_check(residue_pairs_launch(d_aa, translated_records_bytes_bound(len, n_records), d_blocks + n_records, ksize, seed, thr, ws.d_pair_hash,
+                                           ws.d_pair_pos, (unsigned long long*)d_result, cap, st), "residue_pairs");
+    } else {
+        hip_check(residues_launch(d_seq, len, hf, d_aa, st), "residues");
+        hip_check(residue_pairs_launch(d_aa, len, nullptr, ksize, seed, thr, ws.d_pair_hash, ws.d_pair_pos, (unsigned long long*)d_result, cap, st),
+                  "residue_pairs");
+    }
+    hip_check(hipMemcpyAsync(head, d_result, 8, hipMemcpyDeviceToHost, st), "D2H");
+    hip_check(hipStreamSynchronize(st), "sync");
+    if (!pairs_fit(head[0], cap, "kept", exceeded)) return ~0ull;
+    // translated: a window's record is the block of its start, and no window reaches out of a block (every block ends in 0xFF)
+    hip_check(records_csr_ends_launch(ws.d_pair_hash, ws.d_pair_pos, head[0], translate ? d_blocks : d_starts, translate ? nullptr : d_ends, n_records, ksize,
+                                      max_hash, d_hashes, d_abunds, d_offsets, d_result + 1, d_csr_tmp, csr_bytes, st), "records_csr");
+    return read_back_rows(d_result, st);
+}
+
+// windows a buffer is expected to keep: translated input has two residues per base
+void residue_records_csr(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, const uint64_t* d_ends, uint64_t n_records, uint32_t ksize,
+                         uint32_t hf, bool translate, uint64_t seed, uint64_t max_hash, bool want_abunds, RecordsCsr& out, hipStream_t st) {
+    out.offsets.reserve((n_records + 1) * 8 + 16, st);
+    AsyncBuf result(64, st);
+    uint64_t cap = records_pair_estimate(translate ? 2 * len : len, max_hash);
+    for (int attempt = 0;; ++attempt) {
+        out.hashes.reserve(cap * 8 + 16, st);
+        if (want_abunds) out.abunds.reserve(cap * 8 + 16, st);
+        const uint64_t ws_bytes = residue_records_workspace(cap, n_records, len, translate);
+        AsyncBuf ws((size_t)ws_bytes, st);
+        uint64_t exceeded = 0;
+        const uint64_t n = residue_records_run(d_seq, len, d_starts, d_ends, n_records, ksize, hf, translate, seed, max_hash, out.hashes.as<uint64_t>(),
+                                               want_abunds ? out.abunds.as<uint64_t>() : nullptr, cap, out.offsets.as<uint64_t>(),
+                                               result.as<uint64_t>(), ws.p, ws_bytes, st, attempt == 0 ? &exceeded : nullptr);
+        if (n != ~0ull) { out.total = n; return; }
+        cap = exceeded;                                              // repetitive input beat the estimate: once more with the count
+    }
 }
 
 // the whole file in host memory (gzip: through the host inflater); throws when it is larger than RECORDS_MAX_FILE
@@ -233,6 +333,15 @@ void parse_records_file(const std::string& path, ParsedRecords& out, hipStream_t
                            std::to_string(out.n_records) + "): " + path);
     out.len = kept;
 }
+
+// where the records of a parsed file end: in front of the header byte the parser keeps between two records
+void file_record_ends(const ParsedRecords& pr, AsyncBuf& ends, hipStream_t st) {
+    ends.reset((pr.n_records + 1) * 8, st);
+    hip_check(records_file_ends_launch(pr.starts.as<uint64_t>(), pr.n_records, ends.as<uint64_t>(), st), "record ends");
+}
+
+// every record of a file as a signature holding every sketch of `cp`: what smgpu_sketch_file_singleton and its residue sibling run
+SourmashSignature** file_singleton(const char* path, const ComputeParameters& cp, bool input_is_protein, uintptr_t* n);
 
 // ---- a sketch's k-mers in sequences (sketch_find.hip; `sourmash sig kmers`, src/sourmash/sig/__main__.py:1087-1310) ----------
 
@@ -376,8 +485,94 @@ SourmashSignature** smgpu_sketch_file_singleton(const char* path, const Sourmash
         if (!path || !n) throw err_internal("null argument");
         const ComputeParameters& cp = *CP(params);
         if (!cp.dna || cp.protein || cp.dayhoff || cp.hp) throw err_internal("smgpu_sketch_file_singleton takes DNA parameters");
+        return file_singleton(path, cp, false, n);
+    });
+}
+
+SourmashSignature** smgpu_sketch_file_singleton_residues(const char* path, const SourmashComputeParameters* params, int32_t input_is_protein,
+                                                         uintptr_t* n) {
+    return landing<SourmashSignature**>([&]() -> SourmashSignature** {
+        if (!path || !n) throw err_internal("null argument");
+        const ComputeParameters& cp = *CP(params);
+        if (input_is_protein && cp.dna) throw err_internal("smgpu_sketch_file_singleton_residues: protein input takes no DNA sketch");
+        return file_singleton(path, cp, input_is_protein != 0, n);
+    });
+}
+
+uint64_t smgpu_sketch_residue_records_workspace_bytes(uint64_t pair_capacity, uint64_t n_records, uint64_t len, int32_t translate) {
+    return residue_records_workspace(pair_capacity, n_records, len, translate != 0);
+}
+
+uint64_t smgpu_sketch_residue_records_raw(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, const uint64_t* d_ends, uint64_t n_records,
+                                          uint32_t ksize, uint32_t hash_function, int32_t translate, uint64_t seed, uint64_t max_hash,
+                                          uint64_t* d_hashes, uint64_t* d_abunds, uint64_t capacity, uint64_t* d_offsets, uint64_t* d_result,
+                                          void* d_workspace, uint64_t workspace_bytes, void* stream) {
+    uint64_t ret = ~0ull;
+    landing_void([&] {
+        ret = residue_records_run(d_seq, len, d_starts, d_ends, n_records, ksize, hash_function, translate != 0, seed, max_hash, d_hashes, d_abunds,
+                                  capacity, d_offsets, d_result, d_workspace, workspace_bytes, (hipStream_t)stream, nullptr);
+    });
+    return ret;
+}
+
+void smgpu_residue_records_kernel_raw(const uint8_t* d_aa, uint64_t n, const uint64_t* d_n, uint32_t ksize, uint64_t seed, uint64_t max_hash,
+                                      uint64_t* d_hashes, uint64_t* d_positions, uint64_t capacity, uint64_t* d_count, void* stream) {
+    landing_void([&] {
+        if (ksize < 1 || ksize > RESIDUE_RECORDS_MAX_K)
+            throw err_internal("per-record residue sketches take ksize 1 .. 79 residues, not " + std::to_string(ksize));
+        if (!d_aa || !d_hashes || !d_count || reinterpret_cast<uintptr_t>(d_aa) % 8)
+            throw err_internal("smgpu_residue_records_kernel_raw: null pointer or a residue buffer that is not 8-byte aligned");
+        const uint64_t thr = max_hash ? max_hash : ~0ull;
+        if (d_positions)
+            hip_check(residue_pairs_launch(d_aa, n, d_n, ksize, seed, thr, d_hashes, d_positions, (unsigned long long*)d_count, capacity,
+                                           (hipStream_t)stream), "residue_pairs");
+        else
+            hip_check(residue_windows_launch(d_aa, n, ksize, seed, thr, d_hashes, (unsigned long long*)d_count, capacity, false, (hipStream_t)stream),
+                      "residue_windows");
+    });
+}
+
+SmgpuSketchSet* smgpu_sketchset_sketch_residue_records(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, const uint64_t* d_ends,
+                                                       uint64_t n_records, uint32_t ksize, uint32_t hash_function, int32_t translate, uint64_t seed,
+                                                       uint64_t scaled) {
+    return landing<SmgpuSketchSet*>([&]() -> SmgpuSketchSet* {
+        DeviceCtx& ctx = DeviceCtx::get();
+        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+        return reinterpret_cast<SmgpuSketchSet*>(sketchset_from_residue_records(d_seq, len, d_starts, d_ends, n_records, ksize, hash_function,
+                                                                                translate != 0, seed, scaled, ctx.stream()));
+    });
+}
+
+SmgpuSketchSet* smgpu_sketchset_sketch_residue_file(const char* path, uint32_t ksize, uint32_t hash_function, int32_t translate, uint64_t seed,
+                                                    uint64_t scaled) {
+    return landing<SmgpuSketchSet*>([&]() -> SmgpuSketchSet* {
+        if (!path) throw err_internal("null path");
+        DeviceCtx& ctx = DeviceCtx::get();
+        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+        hipStream_t st = ctx.stream();
+        ParsedRecords pr;
+        parse_records_file(path, pr, st);
+        AsyncBuf ends;
+        file_record_ends(pr, ends, st);
+        std::unique_ptr<SketchSet> s(sketchset_from_residue_records(pr.comp.as<uint8_t>(), pr.len, pr.starts.as<uint64_t>(), ends.as<uint64_t>(),
+                                                                    pr.n_records, ksize, hash_function, translate != 0, seed, scaled, st));
+        for (uint64_t r = 0; r < pr.n_records; ++r) { s->rows[r].name = pr.names[r]; s->rows[r].filename = path; }
+        return reinterpret_cast<SmgpuSketchSet*>(s.release());
+    });
+}
+
+}  // extern "C"
+
+namespace {
+
+SourmashSignature** file_singleton(const char* path, const ComputeParameters& cp, bool input_is_protein, uintptr_t* n) {
+    {
         if (cp.scaled == 0) throw err_internal("smgpu_sketch_file_singleton takes scaled sketches");
-        for (uint32_t k : cp.ksizes) if (k < 1 || k > 88) throw err_internal("per-record sketches take ksize 1 .. 88, not " + std::to_string(k));
+        for (uint32_t k : cp.ksizes) {
+            if (cp.dna && (k < 1 || k > 88)) throw err_internal("per-record sketches take ksize 1 .. 88, not " + std::to_string(k));
+            if ((cp.protein || cp.dayhoff || cp.hp) && (k < 3 || k / 3 > RESIDUE_RECORDS_MAX_K))
+                throw err_internal("per-record residue sketches take ksize 1 .. 79 residues, not " + std::to_string(k / 3));
+        }
         DeviceCtx& ctx = DeviceCtx::get();
         std::lock_guard<std::recursive_mutex> g(ctx.mutex());
         hipStream_t st = ctx.stream();
@@ -393,10 +588,16 @@ SourmashSignature** smgpu_sketch_file_singleton(const char* path, const Sourmash
         // one kernel pass per sketch of the template over the same parsed buffer and the same starts
         const Signature tmpl = Signature::from_params(cp);
         std::vector<uint64_t> off(pr.n_records + 1), hs, as;
+        AsyncBuf ends;
+        if (cp.protein || cp.dayhoff || cp.hp) file_record_ends(pr, ends, st);
         for (size_t q = 0; q < tmpl.sketches.size(); ++q) {
             const KmerMinHash& t = tmpl.sketches[q];
             RecordsCsr csr;
-            sketch_records_csr(pr.comp.as<uint8_t>(), pr.len, pr.starts.as<uint64_t>(), pr.n_records, t.ksize, t.seed, t.max_hash, t.track_abundance, csr, st);
+            if (t.hash_function == HF_DNA)
+                sketch_records_csr(pr.comp.as<uint8_t>(), pr.len, pr.starts.as<uint64_t>(), pr.n_records, t.ksize, t.seed, t.max_hash, t.track_abundance, csr, st);
+            else
+                residue_records_csr(pr.comp.as<uint8_t>(), pr.len, pr.starts.as<uint64_t>(), ends.as<uint64_t>(), pr.n_records, t.ksize / 3, t.hash_function,
+                                    !input_is_protein, t.seed, t.max_hash, t.track_abundance, csr, st);
             hs.resize(csr.total); as.resize(t.track_abundance ? csr.total : 0);
             hip_check(hipMemcpyAsync(off.data(), csr.offsets.p, (pr.n_records + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
             if (csr.total) hip_check(hipMemcpyAsync(hs.data(), csr.hashes.p, csr.total * 8, hipMemcpyDeviceToHost, st), "D2H");
@@ -410,8 +611,12 @@ SourmashSignature** smgpu_sketch_file_singleton(const char* path, const Sourmash
             }
         }
         return sigs_out(std::move(sigs), n);
-    });
+    }
 }
+
+}  // namespace
+
+extern "C" {
 
 SmgpuKmerQuery* smgpu_kmerquery_new(const SourmashKmerMinHash* const* mhs, uintptr_t n) {
     return landing<SmgpuKmerQuery*>([&]() -> SmgpuKmerQuery* {

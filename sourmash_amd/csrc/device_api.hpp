@@ -128,6 +128,33 @@ hipError_t records_csr_launch(uint64_t* d_pair_hash, uint64_t* d_pair_pos, uint6
                               uint32_t k, uint64_t max_hash, uint64_t* d_hashes, uint64_t* d_abunds, uint64_t* d_offsets, uint64_t* d_n_out,
                               void* d_temp, size_t temp_bytes, hipStream_t stream);
 
+// the same for records with explicit ends (records_core.hpp: rec_assign_ends): record r = [d_starts[r], d_ends[r]), d_ends null
+// = records touch.  `k` and the positions are in the units of the buffer the pairs came from (residues for the residue passes).
+hipError_t records_csr_ends_launch(uint64_t* d_pair_hash, uint64_t* d_pair_pos, uint64_t n_pairs, const uint64_t* d_starts, const uint64_t* d_ends,
+                                   uint64_t n_records, uint32_t k, uint64_t max_hash, uint64_t* d_hashes, uint64_t* d_abunds, uint64_t* d_offsets,
+                                   uint64_t* d_n_out, void* d_temp, size_t temp_bytes, hipStream_t stream);
+// *d_bad |= 4 if some d_ends[r] lies outside [d_starts[r], d_starts[r + 1]] (the starts are checked by records_check_starts_launch)
+hipError_t records_check_ends_launch(const uint64_t* d_starts, const uint64_t* d_ends, uint64_t n_records, unsigned long long* d_bad,
+                                     hipStream_t stream);
+// the ends of a parsed file's records: d_ends[r] = d_starts[r + 1] - 1, the header byte fastx.hip keeps, for every record but the last
+hipError_t records_file_ends_launch(const uint64_t* d_starts, uint64_t n_records, uint64_t* d_ends, hipStream_t stream);
+
+// ---- protein_records.hip (one protein / dayhoff / hp sketch per record: the residue side of sketch_records.hip) -------------------
+// Every hash h of a window of k residues (1 <= k <= 79) of d_aa, with 1 <= h <= thr, appended to d_hash and the window's start to
+// d_pos (unordered); *d_count += pairs (keeps counting past `cap`, pairs past cap are dropped).  d_aa: 8-byte aligned, readable
+// in whole 8-byte words.  d_n not null: the translated buffer -- its size is *d_n (a size only the device knows), never above
+// n_bound, and windows touching a 0xFF do not exist.  d_n null: residues of protein input, n_bound of them, no separators.
+hipError_t residue_pairs_launch(const uint8_t* d_aa, uint64_t n_bound, const uint64_t* d_n, uint32_t k, uint64_t seed, uint64_t thr,
+                                uint64_t* d_hash, uint64_t* d_pos, unsigned long long* d_count, uint64_t cap, hipStream_t stream);
+// Six-frame translation of every record [d_starts[r], d_ends[r]) (d_ends null: records touch) of d_seq[0,len) into a block of its
+// own of d_aa (translate_records_core.hpp): d_block_starts[0 .. n_records] the blocks' starts, the last one the bytes written.
+// d_aa: 8-byte aligned, room for translated_records_bytes_bound(len, n_records) + 8 bytes.  The records must have been checked.
+uint64_t translated_records_bytes_bound(uint64_t len, uint64_t n_records);
+size_t translate_records_temp_bytes(uint64_t n_records);
+hipError_t translate_records_launch(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, const uint64_t* d_ends, uint64_t n_records,
+                                    uint32_t hash_function, uint64_t* d_block_starts, uint8_t* d_aa, void* d_temp, size_t temp_bytes,
+                                    hipStream_t stream);
+
 // ---- sketch_find.hip (a query sketch's k-mers in a buffer: rows of (position, hash), by record) ----------------------------------
 // d_dir[b] = first index of the sorted d_q[0,n) with d_q[i] >> shift >= b, for b = 0 .. n_buckets (find_core.hpp)
 hipError_t find_dir_launch(const uint64_t* d_q, uint64_t n, uint32_t shift, uint64_t n_buckets, uint32_t* d_dir, hipStream_t stream);

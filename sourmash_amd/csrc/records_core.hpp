@@ -1,6 +1,6 @@
-// records_core.hpp -- the two rules of per-record sketching (sketch_records.hip) that the host and the device share: which
-// record a k-mer belongs to, and whether (record, hash) fits one 64-bit sort key.  Plain C++ on the host
-// (tests/native/records_core_emul.cpp compiles it with g++).
+// records_core.hpp -- the rules of per-record sketching (sketch_records.hip) that the host and the device share: which
+// record a k-mer belongs to -- for records that touch and for records with explicit ends -- and whether (record, hash) fits one
+// 64-bit sort key.  Plain C++ on the host (tests/native/records_core_emul.cpp and residue_records_emul.cpp compile it with g++).
 #pragma once
 #include <stdint.h>
 
@@ -32,6 +32,29 @@ SMG_HD bool rec_assign(const uint64_t* starts, uint64_t n_records, uint64_t pos,
     const uint64_t r = lo - 1;                           // lo >= 1: starts[0] <= pos
     if (r >= n_records) return false;                    // at or behind starts[n_records]
     if (pos + k > starts[r + 1]) return false;
+    *rec = r;
+    return true;
+}
+
+// Records with explicit ends: record r is the bytes [starts[r], ends[r]) with starts[r] <= ends[r] <= starts[r + 1]; a null `ends`
+// means ends[r] = starts[r + 1] (records touch).  The bytes of [ends[r], starts[r + 1]) belong to no record -- the byte a file
+// parser leaves between two records, which is no base but would be a residue.  The window of k bytes that starts at pos belongs
+// to r = upper_bound(starts, pos) - 1, as above, and is kept only if it ends at or before ends[r].
+SMG_HD uint64_t rec_end(const uint64_t* starts, const uint64_t* ends, uint64_t r) { return ends ? ends[r] : starts[r + 1]; }
+SMG_HD uint64_t rec_len(const uint64_t* starts, const uint64_t* ends, uint64_t r) { return rec_end(starts, ends, r) - starts[r]; }
+SMG_HD bool rec_ends_valid(const uint64_t* starts, const uint64_t* ends, uint64_t r) {
+    return ends[r] >= starts[r] && ends[r] <= starts[r + 1];
+}
+SMG_HD bool rec_assign_ends(const uint64_t* starts, const uint64_t* ends, uint64_t n_records, uint64_t pos, uint32_t k, uint64_t* rec) {
+    if (n_records == 0 || pos < starts[0]) return false;
+    uint64_t lo = 0, hi = n_records + 1;                 // first index with starts[index] > pos
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (starts[mid] <= pos) lo = mid + 1; else hi = mid;
+    }
+    const uint64_t r = lo - 1;                           // lo >= 1: starts[0] <= pos
+    if (r >= n_records) return false;                    // at or behind starts[n_records]
+    if (pos + k > rec_end(starts, ends, r)) return false;
     *rec = r;
     return true;
 }

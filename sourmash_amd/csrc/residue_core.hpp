@@ -72,7 +72,8 @@ SMG_HD uint64_t residue_window_hash(const uint64_t* W, const uint64_t* F, const 
 
 // The RW_P windows starting at bytes 8 g .. 8 g + 7 of aa[0, n): emit(window start, hash) for every window that lies inside
 // [0, n) and touches no separator.  aa64: `aa` as aligned 8-byte words; words past ceil(n / 8) are not read.
-template <int NB, class Emit>
+// SEP = false: the buffer holds no separators -- protein input, where 0xFF is a byte like any other -- and every window is emitted.
+template <int NB, bool SEP = true, class Emit>
 SMG_HD void residue_windows_lane(const uint64_t* aa64, uint64_t n, uint64_t g, const ResidueTail& t, uint64_t seed, Emit&& emit) {
     constexpr int NWORDS = 2 * NB + 3;
     const uint64_t n_words = (n + 7) / 8;
@@ -81,7 +82,7 @@ SMG_HD void residue_windows_lane(const uint64_t* aa64, uint64_t n, uint64_t g, c
 #pragma unroll
     for (int m = 0; m < NWORDS; ++m) {
         W[m] = g + (uint64_t)m < n_words ? aa64[g + (uint64_t)m] : 0ull;
-        F[m] = ff_bytes(W[m]);
+        F[m] = SEP ? ff_bytes(W[m]) : 0ull;
         any_sep |= F[m];
     }
     const bool check_sep = any_sep != 0;

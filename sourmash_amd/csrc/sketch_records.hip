@@ -5,7 +5,8 @@
 //   pairs     the sketch kernel's walk with a (hash, position) sink (records_kernel.hpp): every kept hash together with the
 //             start of its k-mer in the caller's buffer.  The hot kernel knows nothing about records.
 //   assign    one lane per pair: the record of the position (binary search in the caller's ascending starts) and the rule
-//             that no k-mer spans two records (records_core.hpp: rec_assign).  A pair the rule drops gets key 0, which no kept
+//             that no k-mer spans two records (records_core.hpp: rec_assign; rec_assign_ends for records with explicit ends,
+//             which the residue passes of protein_records.hip use).  A pair the rule drops gets key 0, which no kept
 //             pair has (hashes are >= 1).
 //   sort      by (record, hash).  Packed form: the record number in the key bits above the hash, the library's 64-bit sort +
 //             run-length encode (device_sort.hip: sort_unique); wide form, when record and hash bits exceed 64: two stable radix
@@ -38,23 +39,49 @@ __global__ __launch_bounds__(RC_THREADS) void rec_check_starts_kernel(const uint
     if (i == n_records && starts[i] > len) atomicOr(bad, 2ull);
 }
 
+// *bad |= 4: an end outside [starts[r], starts[r + 1]]
+__global__ __launch_bounds__(RC_THREADS) void rec_check_ends_kernel(const uint64_t* __restrict__ starts, const uint64_t* __restrict__ ends,
+                                                                    uint64_t n_records, unsigned long long* __restrict__ bad) {
+    const uint64_t i = (uint64_t)blockIdx.x * RC_THREADS + threadIdx.x;
+    if (i < n_records && !rec_ends_valid(starts, ends, i)) atomicOr(bad, 4ull);
+}
+
+// a file's records (fastx.hip keeps the first byte of every header line in front of the next record's bytes): ends[r] =
+// starts[r + 1] - 1 for every record but the last
+__global__ __launch_bounds__(RC_THREADS) void rec_file_ends_kernel(const uint64_t* __restrict__ starts, uint64_t n_records, uint64_t* __restrict__ ends) {
+    const uint64_t r = (uint64_t)blockIdx.x * RC_THREADS + threadIdx.x;
+    if (r >= n_records) return;
+    const uint64_t s = starts[r], e = starts[r + 1];
+    ends[r] = r + 1 < n_records && e > s ? e - 1 : e;
+}
+
+// the rule of the DNA records (rec_assign) or, ENDS, the one with explicit ends (rec_assign_ends; ends may be null)
+template <bool ENDS>
+__device__ __forceinline__ bool rec_assign_by(const uint64_t* starts, const uint64_t* ends, uint64_t n_records, uint64_t pos, uint32_t k, uint64_t* rec) {
+    if constexpr (ENDS) return rec_assign_ends(starts, ends, n_records, pos, k, rec);
+    else return rec_assign(starts, n_records, pos, k, rec);
+}
+
 // packed: pos[i] becomes the key (record << hbits) | hash, or 0 for a dropped pair
+template <bool ENDS>
 __global__ __launch_bounds__(RC_THREADS) void rec_assign_packed_kernel(const uint64_t* __restrict__ hash, uint64_t* __restrict__ pos, uint64_t n,
-                                                                       const uint64_t* __restrict__ starts, uint64_t n_records, uint32_t k,
-                                                                       int hbits) {
+                                                                       const uint64_t* __restrict__ starts, const uint64_t* __restrict__ ends,
+                                                                       uint64_t n_records, uint32_t k, int hbits) {
     const uint64_t i = (uint64_t)blockIdx.x * RC_THREADS + threadIdx.x;
     if (i >= n) return;
     uint64_t r = 0;
-    const bool keep = rec_assign(starts, n_records, pos[i], k, &r);
+    const bool keep = rec_assign_by<ENDS>(starts, ends, n_records, pos[i], k, &r);
     pos[i] = keep ? ((hbits < 64 ? r << hbits : 0ull) | hash[i]) : 0ull;
 }
 // wide: pos[i] becomes the record number; a dropped pair becomes (record 0, hash 0)
+template <bool ENDS>
 __global__ __launch_bounds__(RC_THREADS) void rec_assign_wide_kernel(uint64_t* __restrict__ hash, uint64_t* __restrict__ pos, uint64_t n,
-                                                                     const uint64_t* __restrict__ starts, uint64_t n_records, uint32_t k) {
+                                                                     const uint64_t* __restrict__ starts, const uint64_t* __restrict__ ends,
+                                                                     uint64_t n_records, uint32_t k) {
     const uint64_t i = (uint64_t)blockIdx.x * RC_THREADS + threadIdx.x;
     if (i >= n) return;
     uint64_t r = 0;
-    const bool keep = rec_assign(starts, n_records, pos[i], k, &r);
+    const bool keep = rec_assign_by<ENDS>(starts, ends, n_records, pos[i], k, &r);
     pos[i] = keep ? r : 0ull;
     if (!keep) hash[i] = 0ull;
 }
@@ -125,9 +152,26 @@ size_t records_csr_temp_bytes(uint64_t n_pairs) {
     return 256 + 2 * al256(n * 8) + (packed > wide ? packed : wide) + 256;
 }
 
-hipError_t records_csr_launch(uint64_t* d_pair_hash, uint64_t* d_pair_pos, uint64_t n_pairs, const uint64_t* d_starts, uint64_t n_records,
-                              uint32_t k, uint64_t max_hash, uint64_t* d_hashes, uint64_t* d_abunds, uint64_t* d_offsets, uint64_t* d_n_out,
-                              void* d_temp, size_t temp_bytes, hipStream_t stream) {
+hipError_t records_check_ends_launch(const uint64_t* d_starts, const uint64_t* d_ends, uint64_t n_records, unsigned long long* d_bad,
+                                     hipStream_t stream) {
+    if (n_records == 0) return hipSuccess;
+    hipLaunchKernelGGL(rec_check_ends_kernel, dim3(rc_grid(n_records)), dim3(RC_THREADS), 0, stream, d_starts, d_ends, n_records, d_bad);
+    return hipGetLastError();
+}
+
+hipError_t records_file_ends_launch(const uint64_t* d_starts, uint64_t n_records, uint64_t* d_ends, hipStream_t stream) {
+    if (n_records == 0) return hipSuccess;
+    hipLaunchKernelGGL(rec_file_ends_kernel, dim3(rc_grid(n_records)), dim3(RC_THREADS), 0, stream, d_starts, n_records, d_ends);
+    return hipGetLastError();
+}
+
+namespace {
+
+// ENDS: assign by rec_assign_ends with d_ends (may be null); else by rec_assign
+template <bool ENDS>
+hipError_t records_csr_run(uint64_t* d_pair_hash, uint64_t* d_pair_pos, uint64_t n_pairs, const uint64_t* d_starts, const uint64_t* d_ends,
+                           uint64_t n_records, uint32_t k, uint64_t max_hash, uint64_t* d_hashes, uint64_t* d_abunds, uint64_t* d_offsets,
+                           uint64_t* d_n_out, void* d_temp, size_t temp_bytes, hipStream_t stream) {
     if (n_pairs == 0 || n_records == 0) {
         hipError_t e = hipMemsetAsync(d_offsets, 0, (n_records + 1) * 8, stream);
         return e != hipSuccess ? e : hipMemsetAsync(d_n_out, 0, 8, stream);
@@ -148,15 +192,16 @@ hipError_t records_csr_launch(uint64_t* d_pair_hash, uint64_t* d_pair_pos, uint6
     runs.packed = rec_packed(n_records, max_hash);
     hipError_t e;
     if (runs.packed) {
-        hipLaunchKernelGGL(rec_assign_packed_kernel, dim3(rc_grid(n)), dim3(RC_THREADS), 0, stream, (const uint64_t*)d_pair_hash, d_pair_pos, n,
-                           d_starts, n_records, k, hbits);
+        hipLaunchKernelGGL((rec_assign_packed_kernel<ENDS>), dim3(rc_grid(n)), dim3(RC_THREADS), 0, stream, (const uint64_t*)d_pair_hash, d_pair_pos,
+                           n, d_starts, d_ends, n_records, k, hbits);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         const int bits = rec_bits(n_records - 1) + hbits;
         if ((e = sort_unique(d_pair_pos, n, A, B, d_n_runs, rest, rest_bytes, bits, stream)) != hipSuccess) return e;
         runs.u_key = A;
         runs.counts = B;
     } else {
-        hipLaunchKernelGGL(rec_assign_wide_kernel, dim3(rc_grid(n)), dim3(RC_THREADS), 0, stream, d_pair_hash, d_pair_pos, n, d_starts, n_records, k);
+        hipLaunchKernelGGL((rec_assign_wide_kernel<ENDS>), dim3(rc_grid(n)), dim3(RC_THREADS), 0, stream, d_pair_hash, d_pair_pos, n, d_starts, d_ends,
+                           n_records, k);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         uint64_t* C = (uint64_t*)rest;
         void* prim = rest + al256(n * 8);
@@ -173,6 +218,22 @@ hipError_t records_csr_launch(uint64_t* d_pair_hash, uint64_t* d_pair_pos, uint6
     hipLaunchKernelGGL(rec_finish_kernel, dim3(rc_grid(n)), dim3(RC_THREADS), 0, stream, runs, d_hashes, d_abunds, d_n_out);
     hipLaunchKernelGGL(rec_offsets_kernel, dim3(rc_grid(n_records + 1)), dim3(RC_THREADS), 0, stream, runs, n_records, d_offsets);
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t records_csr_launch(uint64_t* d_pair_hash, uint64_t* d_pair_pos, uint64_t n_pairs, const uint64_t* d_starts, uint64_t n_records,
+                              uint32_t k, uint64_t max_hash, uint64_t* d_hashes, uint64_t* d_abunds, uint64_t* d_offsets, uint64_t* d_n_out,
+                              void* d_temp, size_t temp_bytes, hipStream_t stream) {
+    return records_csr_run<false>(d_pair_hash, d_pair_pos, n_pairs, d_starts, nullptr, n_records, k, max_hash, d_hashes, d_abunds, d_offsets, d_n_out,
+                                  d_temp, temp_bytes, stream);
+}
+
+hipError_t records_csr_ends_launch(uint64_t* d_pair_hash, uint64_t* d_pair_pos, uint64_t n_pairs, const uint64_t* d_starts, const uint64_t* d_ends,
+                                   uint64_t n_records, uint32_t k, uint64_t max_hash, uint64_t* d_hashes, uint64_t* d_abunds, uint64_t* d_offsets,
+                                   uint64_t* d_n_out, void* d_temp, size_t temp_bytes, hipStream_t stream) {
+    return records_csr_run<true>(d_pair_hash, d_pair_pos, n_pairs, d_starts, d_ends, n_records, k, max_hash, d_hashes, d_abunds, d_offsets, d_n_out,
+                                 d_temp, temp_bytes, stream);
 }
 
 }  // namespace smg

@@ -113,9 +113,17 @@ def sigjson_text_pad():
 
 def _records_error(code, message):
     "the exception of a failed per-record call: starts the library refuses are the caller's ValueError"
-    if "record starts" in message:
+    if "record starts" in message or "record ends" in message:
         return ValueError(message)
     return exceptions_by_code.get(code, SourmashError)(message)
+
+
+def _residue_hash_function(moltype):
+    "the library's hash_function number of a molecule type name (1 DNA, 2 protein, 3 dayhoff, 4 hp)"
+    try:
+        return {"DNA": 1, "PROTEIN": 2, "DAYHOFF": 3, "HP": 4}[str(moltype).upper()]
+    except KeyError:
+        raise ValueError(f"unknown moltype {moltype!r}") from None
 
 
 class DeviceSketcher:
@@ -167,8 +175,13 @@ class DeviceSketcher:
                 continue
             raise exceptions_by_code.get(code, SourmashError)(message)
 
-    def sketch_records(self, seq, starts, *, abund=False):
+    def sketch_records(self, seq, starts, *, abund=False, moltype="DNA", is_protein=False, ends=None):
         """One sketch per record of `seq` in one pass (smgpu_sketch_records_raw, csrc/sketch_records.hip).
+
+        moltype protein / dayhoff / hp (smgpu_sketch_residue_records_raw, csrc/protein_records.hip): the sketcher's ksize counts
+        residues, 1 .. 79; is_protein: the records are residues, otherwise DNA that is translated in six frames record by
+        record.  ends (these moltypes only): int64 device tensor of n_records offsets, record r = seq[starts[r]:ends[r]] with
+        starts[r] <= ends[r] <= starts[r + 1]; None: records touch.  An end outside its record raises ValueError.
 
         starts: int64 device tensor of n_records + 1 ascending offsets, record r = seq[starts[r]:starts[r + 1]]; records may
         touch, and a k-mer counts only for the record it lies in entirely.  -> (hashes, offsets[, abunds]): the CSR of
@@ -180,18 +193,36 @@ class DeviceSketcher:
         if starts.numel() < 1:
             raise ValueError("record starts: n_records + 1 offsets are needed")
         n, n_records = seq.numel(), starts.numel() - 1
-        expect = n / max(self.scaled, 1)
-        cap = max(1, min(n, int(expect * 2 + 16 * (expect + 1) ** 0.5) + 4096))   # the slack of the batched ingest (csrc/ingest.hpp)
+        hf = _residue_hash_function(moltype)
+        if hf == 1 and (is_protein or ends is not None):
+            raise ValueError("is_protein and ends go with moltype protein, dayhoff or hp")
+        if ends is not None:
+            assert ends.dtype == torch.int64 and ends.is_cuda and ends.is_contiguous()
+            if ends.numel() != n_records:
+                raise ValueError("record ends: n_records offsets are needed")
+        translate = hf != 1 and not is_protein
+        windows = 2 * n if translate else n
+        expect = windows / max(self.scaled, 1)
+        cap = max(1, min(windows, int(expect * 2 + 16 * (expect + 1) ** 0.5) + 4096))   # the slack of the batched ingest (csrc/ingest.hpp)
         result = torch.zeros(4, dtype=torch.int64, device=seq.device)
         offsets = _u64(torch, n_records + 1, seq.device)
         for attempt in range(2):
             hashes = _u64(torch, cap, seq.device)
             abunds = _u64(torch, cap, seq.device) if abund else None
-            ws = torch.empty(int(lib.smgpu_sketch_records_workspace_bytes(cap, n_records)), dtype=torch.uint8, device=seq.device)
-            lib.sourmash_err_clear()
-            got = lib.smgpu_sketch_records_raw(_ptr(seq), n, _ptr(starts), n_records, self.ksize, self.seed, self.max_hash,
-                                               _ptr(hashes), _ptr(abunds) if abund else None, cap, _ptr(offsets), _ptr(result),
-                                               _ptr(ws), ws.numel(), _stream(torch))
+            if hf == 1:
+                ws = torch.empty(int(lib.smgpu_sketch_records_workspace_bytes(cap, n_records)), dtype=torch.uint8, device=seq.device)
+                lib.sourmash_err_clear()
+                got = lib.smgpu_sketch_records_raw(_ptr(seq), n, _ptr(starts), n_records, self.ksize, self.seed, self.max_hash,
+                                                   _ptr(hashes), _ptr(abunds) if abund else None, cap, _ptr(offsets), _ptr(result),
+                                                   _ptr(ws), ws.numel(), _stream(torch))
+            else:
+                ws = torch.empty(int(lib.smgpu_sketch_residue_records_workspace_bytes(cap, n_records, n, int(translate))), dtype=torch.uint8,
+                                 device=seq.device)
+                lib.sourmash_err_clear()
+                got = lib.smgpu_sketch_residue_records_raw(_ptr(seq), n, _ptr(starts), _ptr(ends) if ends is not None else None, n_records,
+                                                           self.ksize, hf, int(translate), self.seed, self.max_hash, _ptr(hashes),
+                                                           _ptr(abunds) if abund else None, cap, _ptr(offsets), _ptr(result), _ptr(ws),
+                                                           ws.numel(), _stream(torch))
             code = lib.sourmash_err_get_last_code()
             if code == 0:
                 return (hashes[:got], offsets, abunds[:got]) if abund else (hashes[:got], offsets)
@@ -207,6 +238,15 @@ class DeviceSketcher:
         torch = self.torch
         rustcall(lib.smgpu_sketch_records_kernel_raw, _ptr(seq), seq.numel(), self.ksize, self.seed, self.max_hash,
                  _ptr(out_hashes), _ptr(out_positions), min(out_hashes.numel(), out_positions.numel()), _ptr(count), _stream(torch))
+
+    def residue_kernel_only(self, aa, out_hashes, out_positions, count, n_dev=None):
+        """Just the window kernel of the per-record residue sketches on a residue buffer `aa` (8-byte aligned): appends to the two
+        arrays, adds to `count` (int64[1], caller zeroes).  out_positions None: the hash-only kernel of the record-by-record route
+        on the same buffer.  n_dev (int64[1]): the buffer's size on the device; with it 0xFF bytes separate."""
+        torch = self.torch
+        cap = out_hashes.numel() if out_positions is None else min(out_hashes.numel(), out_positions.numel())
+        rustcall(lib.smgpu_residue_records_kernel_raw, _ptr(aa), aa.numel(), _ptr(n_dev) if n_dev is not None else None, self.ksize, self.seed,
+                 self.max_hash, _ptr(out_hashes), _ptr(out_positions) if out_positions is not None else None, cap, _ptr(count), _stream(torch))
 
     def kernel_only(self, seq, out, count, grid=0):
         """Just the k-mer kernel (no sort): appends to `out`, adds to `count` (int64[1], caller zeroes).  grid: 0 for the

@@ -190,46 +190,74 @@ class SketchSet(RustObject):
                                          _get_max_hash_for_scaled(int(scaled)) if scaled else 0, int(num), strings(names), strings(filenames)))
 
     @classmethod
-    def sketch_records(cls, seq, starts, *, ksize, scaled, seed=42):
-        """One flat scaled DNA sketch per record of a device buffer, in one pass (smgpu_sketchset_sketch_records).
+    def sketch_records(cls, seq, starts, *, ksize, scaled, seed=42, moltype="DNA", is_protein=False, ends=None):
+        """One flat scaled sketch per record of a device buffer, in one pass (smgpu_sketchset_sketch_records).
 
         seq: uint8 device tensor; starts: int64 device tensor of n_records + 1 ascending offsets, record r =
-        seq[starts[r]:starts[r + 1]].  ksize 1 .. 88 (longer k-mers: sketch the records one by one)."""
-        from .device import _ptr, _records_error, _torch
+        seq[starts[r]:starts[r + 1]].  ksize 1 .. 88 (longer k-mers: sketch the records one by one).
+        moltype protein / dayhoff / hp (smgpu_sketchset_sketch_residue_records): ksize counts residues, 1 .. 79; is_protein: the
+        records are residues, otherwise DNA translated in six frames record by record; ends: int64 device tensor of n_records
+        offsets, record r = seq[starts[r]:ends[r]] (None: records touch)."""
+        from .device import _ptr, _records_error, _residue_hash_function, _torch
         torch = _torch()
         assert seq.dtype == torch.uint8 and seq.is_cuda and seq.is_contiguous()
         assert starts.dtype == torch.int64 and starts.is_cuda and starts.is_contiguous()
         if starts.numel() < 1:
             raise ValueError("record starts: n_records + 1 offsets are needed")
+        hf = _residue_hash_function(moltype)
+        if hf == 1 and (is_protein or ends is not None):
+            raise ValueError("is_protein and ends go with moltype protein, dayhoff or hp")
+        if ends is not None:
+            assert ends.dtype == torch.int64 and ends.is_cuda and ends.is_contiguous()
+            if ends.numel() != starts.numel() - 1:
+                raise ValueError("record ends: n_records offsets are needed")
         torch.cuda.current_stream().synchronize()                   # the library works on its own stream
         lib.sourmash_err_clear()
-        ptr = lib.smgpu_sketchset_sketch_records(_ptr(seq), seq.numel(), _ptr(starts), starts.numel() - 1, int(ksize), int(seed),
-                                                 int(scaled))
+        if hf == 1:
+            ptr = lib.smgpu_sketchset_sketch_records(_ptr(seq), seq.numel(), _ptr(starts), starts.numel() - 1, int(ksize), int(seed),
+                                                     int(scaled))
+        else:
+            ptr = lib.smgpu_sketchset_sketch_residue_records(_ptr(seq), seq.numel(), _ptr(starts), _ptr(ends) if ends is not None else None,
+                                                             starts.numel() - 1, int(ksize), hf, int(not is_protein), int(seed), int(scaled))
         code = lib.sourmash_err_get_last_code()
         if code:
             raise _records_error(code, decode_str(lib.sourmash_err_get_last_message()))
         return cls._from_objptr(ptr)
 
     @classmethod
-    def sketch_file(cls, path, *, ksize=31, scaled=1000, seed=42):
-        """One flat scaled DNA sketch per record of a FASTA / FASTQ file (plain or gzip): the device parses the file and
+    def sketch_file(cls, path, *, ksize=31, scaled=1000, seed=42, moltype="DNA", input_is_protein=False):
+        """One flat scaled sketch per record of a FASTA / FASTQ file (plain or gzip): the device parses the file and
         sketches every record in one pass (smgpu_sketchset_sketch_file); manifest[row] carries the record's name and the
-        file name.  What that path does not take (k > 88, a file above its size limit) is sketched record by record."""
-        from .sketch import _records_path_takes, read_records
+        file name.  What that path does not take (k > 88, a file above its size limit) is sketched record by record.
+        moltype protein / dayhoff / hp (smgpu_sketchset_sketch_residue_file): ksize counts residues, the one-pass path takes
+        1 .. 79; input_is_protein: the records are residues, otherwise DNA translated in six frames."""
+        from .device import _residue_hash_function
+        from .sketch import _records_path_takes, _residue_records_path_takes, read_records
         path = os.fspath(path)
-        if _records_path_takes(path, [int(ksize)]):
+        hf = _residue_hash_function(moltype)
+        if hf == 1 and input_is_protein:
+            raise ValueError("input_is_protein goes with moltype protein, dayhoff or hp")
+        if hf == 1 and _records_path_takes(path, [int(ksize)]):
             return cls._from_objptr(rustcall(lib.smgpu_sketchset_sketch_file, os.fsencode(path), int(ksize), int(seed), int(scaled)))
+        if hf != 1 and _residue_records_path_takes(path, [int(ksize)]):
+            return cls._from_objptr(rustcall(lib.smgpu_sketchset_sketch_residue_file, os.fsencode(path), int(ksize), hf,
+                                             int(not input_is_protein), int(seed), int(scaled)))
         from .minhash import MinHash
         mhs, names = [], []
+        mol = {2: dict(is_protein=True), 3: dict(dayhoff=True), 4: dict(hp=True)}.get(hf, {})
         for name, seq in read_records(path):
-            mh = MinHash(0, int(ksize), scaled=int(scaled), seed=int(seed))
-            mh.add_sequence(seq, True)
+            mh = MinHash(0, int(ksize), scaled=int(scaled), seed=int(seed), **mol)
+            if input_is_protein:
+                mh.add_protein(seq)
+            else:
+                mh.add_sequence(seq, True)
             mhs.append(mh)
             names.append(name)
         out = cls(mhs)
         out.set_names(names, [path] * len(names))                   # (what to_json / save write; the manifest below says the same)
         sizes = out.sizes
-        out._manifest = [dict(internal_location="", md5="", md5short="", ksize=int(ksize), moltype="DNA", num=0, scaled=int(scaled),
+        out._manifest = [dict(internal_location="", md5="", md5short="", ksize=int(ksize), moltype={1: "DNA", 2: "protein", 3: "dayhoff", 4: "hp"}[hf],
+                              num=0, scaled=int(scaled),
                               n_hashes=int(sizes[i]), with_abundance=False, name=names[i], filename=path) for i in range(len(names))]
         return out
 

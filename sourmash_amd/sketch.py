@@ -374,13 +374,19 @@ def _add_buffer_to_signature(sig, buf):
 
 RECORDS_MAX_FILE = 2 << 30           # text bytes the per-record path keeps resident (csrc/capi_records.cpp: RECORDS_MAX_FILE)
 RECORDS_MAX_KSIZE = 88               # the longest k-mer of its kernel (csrc/sketch_kernel.hpp: SK_FAST_MAX_K)
+RESIDUE_RECORDS_MAX_KSIZE = 79       # the longest residue window of its kernel (csrc/residue_core.hpp: RW_MAX_NB)
 
 
-def _records_path_takes(path, ksizes):
+def _residue_records_path_takes(path, ksizes):
+    "_records_path_takes for protein / dayhoff / hp sketches (csrc/protein_records.hip); ksizes in residues"
+    return _records_path_takes(path, ksizes, max_ksize=RESIDUE_RECORDS_MAX_KSIZE)
+
+
+def _records_path_takes(path, ksizes, max_ksize=RECORDS_MAX_KSIZE):
     """Whether the one-pass per-record path (csrc/sketch_records.hip) takes this file at these DNA ksizes: every k within
     its kernel's range and the text within its size limit.  A gzip file's text is bounded from its compressed size
     (deflate's 1032:1 limit is far away from sequence text: 8:1 is allowed for)."""
-    if not ksizes or any(k < 1 or k > RECORDS_MAX_KSIZE for k in ksizes):
+    if not ksizes or any(k < 1 or k > max_ksize for k in ksizes):
         return False
     with open(path, "rb") as fh:
         gz = fh.read(2) == b"\x1f\x8b"
@@ -394,11 +400,24 @@ def sketch_file(path, param_str=DEFAULTS["dna"], *, name=None, check_sequence=Fa
 
     Default mode (one signature per file, force=True) runs the native streaming ingest
     (smgpu_signature_add_file: C++ FASTA/FASTQ(.gz) reader -> pinned buffers -> GPU, every ksize in one
-    pass).  --singleton with scaled DNA sketches of k <= 88 and a file of at most 2 GiB of text sketches every record
-    in one pass per ksize (smgpu_sketch_file_singleton: the device parses the file and reports the record starts, the
-    records become the rows of one CSR); every other --singleton case -- protein / dayhoff / hp, num sketches, k >= 89,
-    larger files -- and --check-sequence go record by record like the reference, with equal results."""
+    pass).  --singleton with scaled sketches and a file of at most 2 GiB of text sketches every record in one pass per
+    sketch of the template (the device parses the file and reports the record starts, the records become the rows of one
+    CSR): DNA sketches of k <= 88 (smgpu_sketch_file_singleton) and protein / dayhoff / hp sketches of at most 79 residues,
+    from protein input or from DNA translated in six frames record by record (smgpu_sketch_file_singleton_residues).  Every
+    other --singleton case -- num sketches, longer k-mers or windows, larger files -- and --check-sequence go record by
+    record like the reference, with equal results."""
     params = ComputeParameters.from_param_str(param_str, default_moltype=moltype)
+    residues = params.protein or params.dayhoff or params.hp
+    if (singleton and not check_sequence and residues and params.num_hashes == 0 and params.scaled
+            and not (params.dna and input_is_protein) and all(k % 3 == 0 for k in params.ksizes)
+            and _residue_records_path_takes(path, [k // 3 for k in params.ksizes])
+            and (not params.dna or _records_path_takes(path, params.ksizes))):
+        n = C.c_size_t(0)
+        ptr = rustcall(lib.smgpu_sketch_file_singleton_residues, str(path).encode("utf-8"), params._get_objptr(), int(bool(input_is_protein)),
+                       C.byref(n))
+        sigs = [SourmashSignature._from_objptr(ptr[i]) for i in range(n.value)]
+        lib.nodegraph_buffer_free(C.cast(ptr, C.POINTER(C.c_uint8)), max(n.value, 1) * C.sizeof(C.c_void_p))
+        return sigs
     if (singleton and not check_sequence and params.dna and params.num_hashes == 0 and params.scaled
             and _records_path_takes(path, params.ksizes)):
         n = C.c_size_t(0)
@@ -421,18 +440,30 @@ def sketch_file(path, param_str=DEFAULTS["dna"], *, name=None, check_sequence=Fa
                           singleton=singleton, moltype=moltype, input_is_protein=input_is_protein)
 
 
-def sketch_file_to(path, out, param_str=DEFAULTS["dna"], *, singleton=True, compression=1):
+def sketch_file_to(path, out, param_str=DEFAULTS["dna"], *, singleton=True, compression=1, moltype="dna", input_is_protein=False):
     """`sourmash sketch dna --singleton -p <param_str> <path> -o <out>`: the records' sketches written to `out` (.zip, .sig.gz,
     .sig) without a SourmashSignature object per record.  Where sketch_file(singleton=True) takes the one-pass per-record
-    path (scaled DNA sketches, k <= 88, a file within its size limit), every ksize becomes a SketchSet on the device and goes
-    straight into a SketchSetWriter (one set after the other: all records of the first ksize, then the next); every other
-    case is sketch_file followed by save_signatures_to_json (.sig, .sig.gz) or the same writer, a member per sketch (.zip).
-    -> number of sketches written."""
+    path (scaled flat sketches of one molecule type -- DNA of k <= 88, or protein / dayhoff / hp of at most 79 residues with
+    moltype and input_is_protein as for sketch_file -- and a file within its size limit), every ksize becomes a SketchSet on the
+    device and goes straight into a SketchSetWriter (one set after the other: all records of the first ksize, then the next);
+    every other case is sketch_file followed by save_signatures_to_json (.sig, .sig.gz) or the same writer, a member per
+    sketch (.zip).  -> number of sketches written."""
     import os
     from .index import SketchSet, SketchSetWriter
     from .signature import save_signatures_to_json
     path, out = os.fspath(path), os.fspath(out)
-    params = ComputeParameters.from_param_str(param_str)
+    params = ComputeParameters.from_param_str(param_str, default_moltype=moltype)
+    molecules = [m for m in ("protein", "dayhoff", "hp") if getattr(params, m)]
+    if (singleton and not params.dna and len(molecules) == 1 and params.num_hashes == 0 and params.scaled and not params.track_abundance
+            and all(k % 3 == 0 for k in params.ksizes) and _residue_records_path_takes(path, [k // 3 for k in params.ksizes])):
+        n = 0
+        with SketchSetWriter(out, compression=compression) as w:
+            for k in params.ksizes:
+                sset = SketchSet.sketch_file(path, ksize=k // 3, scaled=params.scaled, seed=params.seed, moltype=molecules[0],
+                                             input_is_protein=input_is_protein)
+                w.add(sset)
+                n += len(sset)
+        return n
     if (singleton and params.dna and params.num_hashes == 0 and params.scaled and not params.track_abundance
             and _records_path_takes(path, params.ksizes)):
         n = 0
@@ -442,7 +473,7 @@ def sketch_file_to(path, out, param_str=DEFAULTS["dna"], *, singleton=True, comp
                 w.add(sset)
                 n += len(sset)
         return n
-    sigs = sketch_file(path, param_str, singleton=singleton)
+    sigs = sketch_file(path, param_str, singleton=singleton, moltype=moltype, input_is_protein=input_is_protein)
     n = sum(len(sig.minhashes()) for sig in sigs)                    # a signature holds a sketch per ksize (and molecule)
     if out.endswith(".zip"):
         # a member per sketch, as the reference's zip writer flattens a signature (save_load.py:527)
