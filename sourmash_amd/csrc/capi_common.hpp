@@ -100,9 +100,6 @@ inline SourmashSignature** sigs_out(std::vector<Signature>&& sigs, uintptr_t* si
     return out;
 }
 
-// x rounded up to the 256-byte granule the workspaces are carved in
-inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-
 inline std::string upper_ascii(const uint8_t* p, size_t n) {
     std::string s((const char*)p, n);
     for (auto& c : s) if (c >= 'a' && c <= 'z') c = (char)(c - 32);

@@ -22,7 +22,7 @@ namespace {
 
 constexpr uint64_t RECORDS_MAX_FILE = (uint64_t)2 << 30;            // a file is resident as a whole (ingest.hpp: MAX_FILE)
 
-// ---- what the two passes over records (sketch_records_run here, find_kmers_run below) share ----
+// ---- what the passes over records (sketch_records_run and residue_records_run here, find_kmers_run below) share ----
 // The workspace of a pass, carved: [pair hashes: cap u64][pair positions: cap u64][the scratch of the pass's second step]
 struct PairWorkspace {
     uint64_t* d_pair_hash;
@@ -59,97 +59,77 @@ uint64_t read_back_rows(const uint64_t* d_result, hipStream_t st) {
     return n;
 }
 
-// d_result: 4 x u64 -- [0] kept (hash, position) pairs, [1] entries, [2] unused, [3] what is wrong with the starts.
-// *exceeded (may be null): instead of raising, report the pairs kept when they outnumber `cap`.
-uint64_t sketch_records_run(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, uint64_t n_records, uint32_t ksize, uint64_t seed,
-                            uint64_t max_hash, uint64_t* d_hashes, uint64_t* d_abunds, uint64_t cap, uint64_t* d_offsets, uint64_t* d_result,
-                            void* d_ws, uint64_t ws_bytes, hipStream_t st, uint64_t* exceeded) {
-    if (ksize < 1 || ksize > 88) throw err_internal("per-record sketches take ksize 1 .. 88, not " + std::to_string(ksize));
-    check_pass_arguments(d_starts, n_records, cap, ws_bytes, smgpu_sketch_records_workspace_bytes(cap, n_records), "smgpu_sketch_records_workspace_bytes");
+// What differs between the passes.  pairs_first: the pair kernel does not read what the records say and is launched in front of
+// the first read-back, so the pass synchronises twice; otherwise nothing is launched behind refused records, at a third
+// synchronisation.
+struct PassSpec {
+    uint64_t ws_needed;             // what the pass's workspace function answers,
+    const char* ws_function;        // and its name
+    const char* ws_aligned_for;     // the entry point whose workspace has to be 8-byte aligned, or null
+    const uint64_t* d_ends;         // checked against the starts when given
+    bool pairs_first;
+    const char* what;               // the pairs of the capacity error: "kept" / "matched"
+};
+
+// One pass over the records of a buffer: arguments, starts and ends checked, pairs(ws) produces (hash, position) pairs and counts
+// them in d_result[0], rows(ws, n_pairs) makes the output from them and leaves its count in d_result[1].  -> that count.
+// d_result: 4 x u64 -- [0] pairs, [1] the second step's count, [2] unused, [3] what is wrong with the records (1, 2: the starts;
+// 4: an end outside its record).  *exceeded (may be null): instead of raising, report the pairs when they outnumber `cap`, and
+// return ~0.  The errors come in this order: starts, ends, capacity.
+template <class Pairs, class Rows>
+uint64_t records_pass(const PassSpec& p, uint64_t len, const uint64_t* d_starts, uint64_t n_records, uint64_t cap, uint64_t* d_result, void* d_ws,
+                      uint64_t ws_bytes, hipStream_t st, uint64_t* exceeded, Pairs&& pairs, Rows&& rows) {
+    check_pass_arguments(d_starts, n_records, cap, ws_bytes, p.ws_needed, p.ws_function);
+    if (p.ws_aligned_for && reinterpret_cast<uintptr_t>(d_ws) % 8) throw err_internal(std::string(p.ws_aligned_for) + ": the workspace must be 8-byte aligned");
     const PairWorkspace ws(d_ws, ws_bytes, cap);
     hip_check(hipMemsetAsync(d_result, 0, 32, st), "memset");
     hip_check(records_check_starts_launch(d_starts, n_records, len, (unsigned long long*)d_result + 3, st), "record starts");
-    hip_check(records_pairs_launch(d_seq, len, ksize, seed, max_hash ? max_hash : ~0ull, ws.d_pair_hash, ws.d_pair_pos, (unsigned long long*)d_result, cap, st),
-              "sketch_records");
+    if (p.d_ends) hip_check(records_check_ends_launch(d_starts, p.d_ends, n_records, (unsigned long long*)d_result + 3, st), "record ends");
+    if (p.pairs_first) pairs(ws);
     unsigned long long head[4] = {0, 0, 0, 0};
     hip_check(hipMemcpyAsync(head, d_result, 32, hipMemcpyDeviceToHost, st), "D2H");
     hip_check(hipStreamSynchronize(st), "sync");
     raise_bad_starts(head, len);
-    if (!pairs_fit(head[0], cap, "kept", exceeded)) return ~0ull;
-    hip_check(records_csr_launch(ws.d_pair_hash, ws.d_pair_pos, head[0], d_starts, n_records, ksize, max_hash, d_hashes, d_abunds, d_offsets, d_result + 1,
-                                 ws.d_tmp, ws.tmp_bytes, st), "records_csr");
+    if (head[3] & 4) throw err_internal("record ends: an end lies outside its record, [starts[r], starts[r + 1]]");
+    if (!p.pairs_first) {
+        pairs(ws);
+        hip_check(hipMemcpyAsync(head, d_result, 8, hipMemcpyDeviceToHost, st), "D2H");
+        hip_check(hipStreamSynchronize(st), "sync");
+    }
+    if (!pairs_fit(head[0], cap, p.what, exceeded)) return ~0ull;
+    rows(ws, head[0]);
     return read_back_rows(d_result, st);
 }
 
-// pairs a buffer of len bytes is expected to keep, with the slack of sketch_slices_batched (ingest.hpp); never more than len
-uint64_t records_pair_estimate(uint64_t len, uint64_t max_hash) {
-    const double frac = max_hash ? (double)max_hash / 18446744073709551616.0 : 1.0;
-    const double l = (double)len;
-    const uint64_t est = (uint64_t)(l * frac * 2.0 + 16.0 * std::sqrt(l * frac + 1.0)) + 4096;
-    return std::max<uint64_t>(1, std::min<uint64_t>(len, est));
-}
-
-// the CSR of one (ksize, seed, max_hash) over the records of a device buffer, in blocks of its own; one retry with the reported
-// count when the estimate is exceeded
-struct RecordsCsr { DevBuf hashes, abunds, offsets; uint64_t total = 0; };
-void sketch_records_csr(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, uint64_t n_records, uint32_t ksize, uint64_t seed,
-                        uint64_t max_hash, bool want_abunds, RecordsCsr& out, hipStream_t st) {
-    out.offsets.reserve((n_records + 1) * 8 + 16, st);
-    AsyncBuf result(64, st);
-    uint64_t cap = records_pair_estimate(len, max_hash);
+// run(cap, exceeded) is a pass at a capacity: with the estimate first, where too many pairs are reported through *exceeded, and
+// then once more with the reported count, where they are raised.  -> what the pass returns
+template <class Run>
+uint64_t with_pair_capacity(uint64_t estimate, Run&& run) {
+    uint64_t cap = estimate;
     for (int attempt = 0;; ++attempt) {
-        out.hashes.reserve(cap * 8 + 16, st);
-        if (want_abunds) out.abunds.reserve(cap * 8 + 16, st);
-        const uint64_t ws_bytes = smgpu_sketch_records_workspace_bytes(cap, n_records);
-        AsyncBuf ws((size_t)ws_bytes, st);
         uint64_t exceeded = 0;
-        const uint64_t n = sketch_records_run(d_seq, len, d_starts, n_records, ksize, seed, max_hash, out.hashes.as<uint64_t>(),
-                                              want_abunds ? out.abunds.as<uint64_t>() : nullptr, cap, out.offsets.as<uint64_t>(),
-                                              result.as<uint64_t>(), ws.p, ws_bytes, st, attempt == 0 ? &exceeded : nullptr);
-        if (n != ~0ull) { out.total = n; return; }
+        const uint64_t n = run(cap, attempt == 0 ? &exceeded : nullptr);
+        if (n != ~0ull) return n;
         cap = exceeded;                                              // repetitive input beat the estimate: once more with the count
     }
 }
 
-// a set that takes over the blocks of a CSR; ksize in units of the molecule
-SketchSet* sketchset_of_csr(RecordsCsr& csr, uint64_t n_records, uint32_t ksize, uint32_t hf, uint64_t seed, uint64_t scaled, hipStream_t st);
-// sketch_records_csr for residue windows (below, with its pass)
-void residue_records_csr(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, const uint64_t* d_ends, uint64_t n_records, uint32_t ksize,
-                         uint32_t hf, bool translate, uint64_t seed, uint64_t max_hash, bool want_abunds, RecordsCsr& out, hipStream_t st);
-
-SketchSet* sketchset_from_records(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, uint64_t n_records, uint32_t ksize, uint64_t seed,
-                                  uint64_t scaled, hipStream_t st) {
-    if (scaled == 0) throw err_internal("per-record sketches are scaled sketches: scaled must not be 0");
-    RecordsCsr csr;
-    sketch_records_csr(d_seq, len, d_starts, n_records, ksize, seed, max_hash_for_scaled(scaled), false, csr, st);
-    return sketchset_of_csr(csr, n_records, ksize, HF_DNA, seed, scaled, st);
-}
-
-SketchSet* sketchset_from_residue_records(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, const uint64_t* d_ends, uint64_t n_records,
-                                          uint32_t ksize, uint32_t hf, bool translate, uint64_t seed, uint64_t scaled, hipStream_t st) {
-    if (scaled == 0) throw err_internal("per-record sketches are scaled sketches: scaled must not be 0");
-    RecordsCsr csr;
-    residue_records_csr(d_seq, len, d_starts, d_ends, n_records, ksize, hf, translate, seed, max_hash_for_scaled(scaled), false, csr, st);
-    return sketchset_of_csr(csr, n_records, ksize, hf, seed, scaled, st);
-}
-
-SketchSet* sketchset_of_csr(RecordsCsr& csr, uint64_t n_records, uint32_t ksize, uint32_t hf, uint64_t seed, uint64_t scaled, hipStream_t st) {
-    std::unique_ptr<SketchSet> s(new SketchSet());
-    const uint64_t max_hash = max_hash_for_scaled(scaled);
-    s->n = n_records; s->total = csr.total;
-    s->ksize = ksize; s->hash_function = hf; s->seed = seed; s->max_hash = max_hash; s->num = 0;
-    s->host_offsets.assign(n_records + 1, 0);
-    hip_check(hipMemcpyAsync(s->host_offsets.data(), csr.offsets.p, (n_records + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
-    hip_check(hipStreamSynchronize(st), "sync");
-    std::swap(s->hashes.p, csr.hashes.p); std::swap(s->hashes.cap, csr.hashes.cap); std::swap(s->hashes.st, csr.hashes.st);
-    std::swap(s->offsets.p, csr.offsets.p); std::swap(s->offsets.cap, csr.offsets.cap); std::swap(s->offsets.st, csr.offsets.st);
-    s->rows.resize(n_records);
-    for (uint64_t r = 0; r < n_records; ++r) {
-        ManifestRow& m = s->rows[r];
-        m.ksize = ksize; m.moltype = molecule_name(hf); m.scaled = scaled;
-        m.n_hashes = s->host_offsets[r + 1] - s->host_offsets[r];
-    }
-    return s.release();
+// DNA: the pair kernel runs in front of the verdict on the starts, which it does not read
+uint64_t sketch_records_run(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, uint64_t n_records, uint32_t ksize, uint64_t seed,
+                            uint64_t max_hash, uint64_t* d_hashes, uint64_t* d_abunds, uint64_t cap, uint64_t* d_offsets, uint64_t* d_result,
+                            void* d_ws, uint64_t ws_bytes, hipStream_t st, uint64_t* exceeded) {
+    if (ksize < 1 || ksize > 88) throw err_internal("per-record sketches take ksize 1 .. 88, not " + std::to_string(ksize));
+    const PassSpec spec{smgpu_sketch_records_workspace_bytes(cap, n_records), "smgpu_sketch_records_workspace_bytes", nullptr, nullptr, true, "kept"};
+    return records_pass(
+        spec, len, d_starts, n_records, cap, d_result, d_ws, ws_bytes, st, exceeded,
+        [&](const PairWorkspace& ws) {
+            hip_check(records_pairs_launch(d_seq, len, ksize, seed, max_hash ? max_hash : ~0ull, ws.d_pair_hash, ws.d_pair_pos, (unsigned long long*)d_result, cap, st),
+                      "sketch_records");
+        },
+        [&](const PairWorkspace& ws, uint64_t n_pairs) {
+            hip_check(records_csr_launch(ws.d_pair_hash, ws.d_pair_pos, n_pairs, d_starts, n_records, ksize, max_hash, d_hashes, d_abunds, d_offsets, d_result + 1,
+                                         ws.d_tmp, ws.tmp_bytes, st), "records_csr");
+        });
 }
 
 // ---- one protein / dayhoff / hp sketch per record (protein_records.hip) -------------------------------------------------------
@@ -164,74 +144,97 @@ uint64_t residue_records_workspace(uint64_t cap, uint64_t n_records, uint64_t le
            (translate ? al256((n_records + 2) * 8) + al256(translate_records_temp_bytes(n_records)) : 0) + 512;
 }
 
-// The pass of sketch_records_run for residue windows: d_result, the starts' errors, the capacity error and `exceeded` as there;
-// d_result[3] & 4: an end outside its record.  The workspace behind the pairs and the CSR scratch: [residue buffer][translated:
-// block starts, n_records + 1 u64][translated: the scan's scratch].
+// Residue windows: the translation reads what the records say, so the verdict comes first.  The workspace behind the pairs: [CSR
+// scratch][residue buffer][translated: block starts, n_records + 1 u64][translated: the scan's scratch].
 uint64_t residue_records_run(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, const uint64_t* d_ends, uint64_t n_records, uint32_t ksize,
                              uint32_t hf, bool translate, uint64_t seed, uint64_t max_hash, uint64_t* d_hashes, uint64_t* d_abunds, uint64_t cap,
                              uint64_t* d_offsets, uint64_t* d_result, void* d_ws, uint64_t ws_bytes, hipStream_t st, uint64_t* exceeded) {
     if (ksize < 1 || ksize > RESIDUE_RECORDS_MAX_K)
         throw err_internal("per-record residue sketches take ksize 1 .. 79 residues, not " + std::to_string(ksize));
     if (hf != HF_PROTEIN && hf != HF_DAYHOFF && hf != HF_HP) throw err_internal("per-record residue sketches are protein, dayhoff or hp sketches");
-    check_pass_arguments(d_starts, n_records, cap, ws_bytes, residue_records_workspace(cap, n_records, len, translate),
-                         "smgpu_sketch_residue_records_workspace_bytes");
-    if (reinterpret_cast<uintptr_t>(d_ws) % 8) throw err_internal("smgpu_sketch_residue_records_raw: the workspace must be 8-byte aligned");
-    const PairWorkspace ws(d_ws, ws_bytes, cap);
-    char* at = (char*)ws.d_tmp;
-    void* d_csr_tmp = at;
     const size_t csr_bytes = al256(records_csr_temp_bytes(cap));
-    at += csr_bytes;
-    uint8_t* d_aa = (uint8_t*)at;
-    at += residue_buffer_bytes(len, n_records, translate);
-    uint64_t* d_blocks = (uint64_t*)at;
-    void* d_scan = at + al256((n_records + 2) * 8);
-    hip_check(hipMemsetAsync(d_result, 0, 32, st), "memset");
-    hip_check(records_check_starts_launch(d_starts, n_records, len, (unsigned long long*)d_result + 3, st), "record starts");
-    if (d_ends) hip_check(records_check_ends_launch(d_starts, d_ends, n_records, (unsigned long long*)d_result + 3, st), "record ends");
-    unsigned long long head[4] = {0, 0, 0, 0};
-    hip_check(hipMemcpyAsync(head, d_result, 32, hipMemcpyDeviceToHost, st), "D2H");
-    hip_check(hipStreamSynchronize(st), "sync");                    // the translation reads what the records say: checked first
-    raise_bad_starts(head, len);
-    if (head[3] & 4) throw err_internal("record ends: an end lies outside its record, [starts[r], starts[r + 1]]");
-    const uint64_t thr = max_hash ? max_hash : ~0ull;
-    if (translate) {
-        hip_check(translate_records_launch(d_seq, len, d_starts, d_ends, n_records, hf, d_blocks, d_aa, d_scan, al256(translate_records_temp_bytes(n_records)), st),
-                  "translate_records");
-        if (n_records)
-            hip_check(residue_pairs_launch(d_aa, translated_records_bytes_bound(len, n_records), d_blocks + n_records, ksize, seed, thr, ws.d_pair_hash,
-                                           ws.d_pair_pos, (unsigned long long*)d_result, cap, st), "residue_pairs");
-    } else {
-        hip_check(residues_launch(d_seq, len, hf, d_aa, st), "residues");
-        hip_check(residue_pairs_launch(d_aa, len, nullptr, ksize, seed, thr, ws.d_pair_hash, ws.d_pair_pos, (unsigned long long*)d_result, cap, st),
-                  "residue_pairs");
-    }
-    hip_check(hipMemcpyAsync(head, d_result, 8, hipMemcpyDeviceToHost, st), "D2H");
-    hip_check(hipStreamSynchronize(st), "sync");
-    if (!pairs_fit(head[0], cap, "kept", exceeded)) return ~0ull;
-    // translated: a window's record is the block of its start, and no window reaches out of a block (every block ends in 0xFF)
-    hip_check(records_csr_ends_launch(ws.d_pair_hash, ws.d_pair_pos, head[0], translate ? d_blocks : d_starts, translate ? nullptr : d_ends, n_records, ksize,
-                                      max_hash, d_hashes, d_abunds, d_offsets, d_result + 1, d_csr_tmp, csr_bytes, st), "records_csr");
-    return read_back_rows(d_result, st);
+    uint64_t* d_blocks = nullptr;                                   // (translated) the records' blocks in the residue buffer
+    const PassSpec spec{residue_records_workspace(cap, n_records, len, translate), "smgpu_sketch_residue_records_workspace_bytes",
+                        "smgpu_sketch_residue_records_raw", d_ends, false, "kept"};
+    return records_pass(
+        spec, len, d_starts, n_records, cap, d_result, d_ws, ws_bytes, st, exceeded,
+        [&](const PairWorkspace& ws) {
+            uint8_t* d_aa = (uint8_t*)ws.d_tmp + csr_bytes;
+            char* at = (char*)d_aa + residue_buffer_bytes(len, n_records, translate);
+            const uint64_t thr = max_hash ? max_hash : ~0ull;
+            if (translate) {
+                d_blocks = (uint64_t*)at;
+                void* d_scan = at + al256((n_records + 2) * 8);
+                hip_check(translate_records_launch(d_seq, len, d_starts, d_ends, n_records, hf, d_blocks, d_aa, d_scan, al256(translate_records_temp_bytes(n_records)), st),
+                          "translate_records");
+                if (n_records)
+                    hip_check(residue_pairs_launch(d_aa, translated_records_bytes_bound(len, n_records), d_blocks + n_records, ksize, seed, thr, ws.d_pair_hash,
+                                                   ws.d_pair_pos, (unsigned long long*)d_result, cap, st), "residue_pairs");
+            } else {
+                hip_check(residues_launch(d_seq, len, hf, d_aa, st), "residues");
+                hip_check(residue_pairs_launch(d_aa, len, nullptr, ksize, seed, thr, ws.d_pair_hash, ws.d_pair_pos, (unsigned long long*)d_result, cap, st),
+                          "residue_pairs");
+            }
+        },
+        [&](const PairWorkspace& ws, uint64_t n_pairs) {
+            // translated: a window's record is the block of its start, and no window reaches out of a block (every block ends in 0xFF)
+            hip_check(records_csr_ends_launch(ws.d_pair_hash, ws.d_pair_pos, n_pairs, translate ? d_blocks : d_starts, translate ? nullptr : d_ends, n_records, ksize,
+                                              max_hash, d_hashes, d_abunds, d_offsets, d_result + 1, ws.d_tmp, csr_bytes, st), "records_csr");
+        });
 }
 
-// windows a buffer is expected to keep: translated input has two residues per base
-void residue_records_csr(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, const uint64_t* d_ends, uint64_t n_records, uint32_t ksize,
-                         uint32_t hf, bool translate, uint64_t seed, uint64_t max_hash, bool want_abunds, RecordsCsr& out, hipStream_t st) {
+// pairs a buffer of len bytes is expected to keep, with the slack of sketch_slices_batched (ingest.hpp); never more than len
+uint64_t records_pair_estimate(uint64_t len, uint64_t max_hash) {
+    const double frac = max_hash ? (double)max_hash / 18446744073709551616.0 : 1.0;
+    const double l = (double)len;
+    const uint64_t est = (uint64_t)(l * frac * 2.0 + 16.0 * std::sqrt(l * frac + 1.0)) + 4096;
+    return std::max<uint64_t>(1, std::min<uint64_t>(len, est));
+}
+
+// The CSR of one (ksize, hf, seed, max_hash) over the records of a device buffer, in blocks of its own.  residue: the residue
+// pass, windows of ksize residues (translated input has two residues per base), which refuses an hf that is not protein, dayhoff
+// or hp; else the DNA pass, k-mers, with hf, d_ends and translate unused.  The caller says which: a C-ABI entry serves one of
+// the two, whatever hash_function it is handed.
+struct RecordsCsr { DevBuf hashes, abunds, offsets; uint64_t total = 0; };
+void records_csr(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, const uint64_t* d_ends, uint64_t n_records, uint32_t ksize, bool residue,
+                 uint32_t hf, bool translate, uint64_t seed, uint64_t max_hash, bool want_abunds, RecordsCsr& out, hipStream_t st) {
+    const bool dna = !residue;
     out.offsets.reserve((n_records + 1) * 8 + 16, st);
     AsyncBuf result(64, st);
-    uint64_t cap = records_pair_estimate(translate ? 2 * len : len, max_hash);
-    for (int attempt = 0;; ++attempt) {
+    out.total = with_pair_capacity(records_pair_estimate(!dna && translate ? 2 * len : len, max_hash), [&](uint64_t cap, uint64_t* exceeded) {
         out.hashes.reserve(cap * 8 + 16, st);
         if (want_abunds) out.abunds.reserve(cap * 8 + 16, st);
-        const uint64_t ws_bytes = residue_records_workspace(cap, n_records, len, translate);
+        const uint64_t ws_bytes = dna ? smgpu_sketch_records_workspace_bytes(cap, n_records) : residue_records_workspace(cap, n_records, len, translate);
         AsyncBuf ws((size_t)ws_bytes, st);
-        uint64_t exceeded = 0;
-        const uint64_t n = residue_records_run(d_seq, len, d_starts, d_ends, n_records, ksize, hf, translate, seed, max_hash, out.hashes.as<uint64_t>(),
-                                               want_abunds ? out.abunds.as<uint64_t>() : nullptr, cap, out.offsets.as<uint64_t>(),
-                                               result.as<uint64_t>(), ws.p, ws_bytes, st, attempt == 0 ? &exceeded : nullptr);
-        if (n != ~0ull) { out.total = n; return; }
-        cap = exceeded;                                              // repetitive input beat the estimate: once more with the count
+        uint64_t *h = out.hashes.as<uint64_t>(), *a = want_abunds ? out.abunds.as<uint64_t>() : nullptr, *o = out.offsets.as<uint64_t>();
+        return dna ? sketch_records_run(d_seq, len, d_starts, n_records, ksize, seed, max_hash, h, a, cap, o, result.as<uint64_t>(), ws.p, ws_bytes, st, exceeded)
+                   : residue_records_run(d_seq, len, d_starts, d_ends, n_records, ksize, hf, translate, seed, max_hash, h, a, cap, o, result.as<uint64_t>(), ws.p,
+                                         ws_bytes, st, exceeded);
+    });
+}
+
+// a set that takes over the blocks of the records' CSR; ksize in units of the molecule
+SketchSet* sketchset_from_records(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, const uint64_t* d_ends, uint64_t n_records, uint32_t ksize,
+                                  bool residue, uint32_t hf, bool translate, uint64_t seed, uint64_t scaled, hipStream_t st) {
+    if (scaled == 0) throw err_internal("per-record sketches are scaled sketches: scaled must not be 0");
+    const uint64_t max_hash = max_hash_for_scaled(scaled);
+    RecordsCsr csr;
+    records_csr(d_seq, len, d_starts, d_ends, n_records, ksize, residue, hf, translate, seed, max_hash, false, csr, st);
+    std::unique_ptr<SketchSet> s(new SketchSet());
+    s->n = n_records; s->total = csr.total;
+    s->ksize = ksize; s->hash_function = hf; s->seed = seed; s->max_hash = max_hash; s->num = 0;
+    s->host_offsets.assign(n_records + 1, 0);
+    hip_check(hipMemcpyAsync(s->host_offsets.data(), csr.offsets.p, (n_records + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
+    hip_check(hipStreamSynchronize(st), "sync");
+    std::swap(s->hashes.p, csr.hashes.p); std::swap(s->hashes.cap, csr.hashes.cap); std::swap(s->hashes.st, csr.hashes.st);
+    std::swap(s->offsets.p, csr.offsets.p); std::swap(s->offsets.cap, csr.offsets.cap); std::swap(s->offsets.st, csr.offsets.st);
+    s->rows.resize(n_records);
+    for (uint64_t r = 0; r < n_records; ++r) {
+        ManifestRow& m = s->rows[r];
+        m.ksize = ksize; m.moltype = molecule_name(hf); m.scaled = scaled;
+        m.n_hashes = s->host_offsets[r + 1] - s->host_offsets[r];
     }
+    return s.release();
 }
 
 // the whole file in host memory (gzip: through the host inflater); throws when it is larger than RECORDS_MAX_FILE
@@ -340,8 +343,67 @@ void file_record_ends(const ParsedRecords& pr, AsyncBuf& ends, hipStream_t st) {
     hip_check(records_file_ends_launch(pr.starts.as<uint64_t>(), pr.n_records, ends.as<uint64_t>(), st), "record ends");
 }
 
+// sketchset_from_records over the records of a file, the rows named after them; the DNA pass takes no ends
+SketchSet* sketchset_from_file(const char* path, uint32_t ksize, bool residue, uint32_t hf, bool translate, uint64_t seed, uint64_t scaled) {
+    if (!path) throw err_internal("null path");
+    DeviceCtx& ctx = DeviceCtx::get();
+    std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+    hipStream_t st = ctx.stream();
+    ParsedRecords pr;
+    parse_records_file(path, pr, st);
+    AsyncBuf ends;
+    if (residue) file_record_ends(pr, ends, st);
+    std::unique_ptr<SketchSet> s(sketchset_from_records(pr.comp.as<uint8_t>(), pr.len, pr.starts.as<uint64_t>(), residue ? ends.as<uint64_t>() : nullptr,
+                                                        pr.n_records, ksize, residue, hf, translate, seed, scaled, st));
+    for (uint64_t r = 0; r < pr.n_records; ++r) { s->rows[r].name = pr.names[r]; s->rows[r].filename = path; }
+    return s.release();
+}
+
 // every record of a file as a signature holding every sketch of `cp`: what smgpu_sketch_file_singleton and its residue sibling run
-SourmashSignature** file_singleton(const char* path, const ComputeParameters& cp, bool input_is_protein, uintptr_t* n);
+SourmashSignature** file_singleton(const char* path, const ComputeParameters& cp, bool input_is_protein, uintptr_t* n) {
+    if (cp.scaled == 0) throw err_internal("smgpu_sketch_file_singleton takes scaled sketches");
+    for (uint32_t k : cp.ksizes) {
+        if (cp.dna && (k < 1 || k > 88)) throw err_internal("per-record sketches take ksize 1 .. 88, not " + std::to_string(k));
+        if ((cp.protein || cp.dayhoff || cp.hp) && (k < 3 || k / 3 > RESIDUE_RECORDS_MAX_K))
+            throw err_internal("per-record residue sketches take ksize 1 .. 79 residues, not " + std::to_string(k / 3));
+    }
+    DeviceCtx& ctx = DeviceCtx::get();
+    std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+    hipStream_t st = ctx.stream();
+    ParsedRecords pr;
+    parse_records_file(path, pr, st);
+    std::vector<Signature> sigs;
+    sigs.reserve(pr.n_records);
+    for (uint64_t r = 0; r < pr.n_records; ++r) {
+        sigs.push_back(Signature::from_params(cp));
+        sigs.back().name = pr.names[r];
+        sigs.back().filename = std::string(path);
+    }
+    // one kernel pass per sketch of the template over the same parsed buffer and the same starts
+    const Signature tmpl = Signature::from_params(cp);
+    std::vector<uint64_t> off(pr.n_records + 1), hs, as;
+    AsyncBuf ends;
+    if (cp.protein || cp.dayhoff || cp.hp) file_record_ends(pr, ends, st);
+    for (size_t q = 0; q < tmpl.sketches.size(); ++q) {
+        const KmerMinHash& t = tmpl.sketches[q];
+        const bool dna = t.hash_function == HF_DNA;
+        RecordsCsr csr;
+        records_csr(pr.comp.as<uint8_t>(), pr.len, pr.starts.as<uint64_t>(), ends.as<uint64_t>(), pr.n_records, dna ? t.ksize : t.ksize / 3, !dna, t.hash_function,
+                    !input_is_protein, t.seed, t.max_hash, t.track_abundance, csr, st);
+        hs.resize(csr.total); as.resize(t.track_abundance ? csr.total : 0);
+        hip_check(hipMemcpyAsync(off.data(), csr.offsets.p, (pr.n_records + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
+        if (csr.total) hip_check(hipMemcpyAsync(hs.data(), csr.hashes.p, csr.total * 8, hipMemcpyDeviceToHost, st), "D2H");
+        if (csr.total && t.track_abundance) hip_check(hipMemcpyAsync(as.data(), csr.abunds.p, csr.total * 8, hipMemcpyDeviceToHost, st), "D2H");
+        hip_check(hipStreamSynchronize(st), "sync");
+        for (uint64_t r = 0; r < pr.n_records; ++r) {
+            KmerMinHash& mh = sigs[r].sketches[q];
+            mh.mins.assign(hs.begin() + (long)off[r], hs.begin() + (long)off[r + 1]);
+            if (t.track_abundance) mh.abunds.assign(as.begin() + (long)off[r], as.begin() + (long)off[r + 1]);
+            mh.touch();
+        }
+    }
+    return sigs_out(std::move(sigs), n);
+}
 
 // ---- a sketch's k-mers in sequences (sketch_find.hip; `sourmash sig kmers`, src/sourmash/sig/__main__.py:1087-1310) ----------
 
@@ -354,8 +416,6 @@ struct KmerQuery {
     DevBuf d_q, d_dir;
     FindQuery dev{nullptr, nullptr, 0, 0};
 };
-
-const char* moltype_name(uint32_t hf) { return hf == HF_PROTEIN ? "protein" : hf == HF_DAYHOFF ? "dayhoff" : hf == HF_HP ? "hp" : "DNA"; }
 
 FindQuery query_on_device(const KmerQuery* cq) {
     KmerQuery* q = const_cast<KmerQuery*>(cq);
@@ -386,22 +446,19 @@ uint64_t find_kmers_run(const KmerQuery* q, const uint8_t* d_seq, uint64_t len, 
     if (!q) throw err_internal("null query");
     const uint32_t ksize = q->mh.ksize;
     if (ksize < 1 || ksize > 88) throw err_internal("k-mer finding takes ksize 1 .. 88, not " + std::to_string(ksize));
-    check_pass_arguments(d_starts, n_records, cap, ws_bytes, smgpu_find_kmers_workspace_bytes(cap, n_records), "smgpu_find_kmers_workspace_bytes");
-    const FindQuery dev = query_on_device(q);
-    const PairWorkspace ws(d_ws, ws_bytes, cap);
-    hip_check(hipMemsetAsync(d_result, 0, 32, st), "memset");
-    hip_check(records_check_starts_launch(d_starts, n_records, len, (unsigned long long*)d_result + 3, st), "record starts");
-    unsigned long long head[4] = {0, 0, 0, 0};
-    hip_check(hipMemcpyAsync(head, d_result, 32, hipMemcpyDeviceToHost, st), "D2H");
-    hip_check(hipStreamSynchronize(st), "sync");
-    raise_bad_starts(head, len);
-    hip_check(find_pairs_launch(d_seq, len, ksize, q->mh.seed, dev, ws.d_pair_hash, ws.d_pair_pos, (unsigned long long*)d_result, cap, 0, st), "find_kmers");
-    hip_check(hipMemcpyAsync(head, d_result, 8, hipMemcpyDeviceToHost, st), "D2H");
-    hip_check(hipStreamSynchronize(st), "sync");
-    if (!pairs_fit(head[0], cap, "matched", exceeded)) return ~0ull;
-    hip_check(find_rows_launch(d_seq, len, ws.d_pair_hash, ws.d_pair_pos, head[0], d_starts, n_records, ksize, d_positions, d_hashes, d_kmers, d_offsets,
-                               d_result + 1, ws.d_tmp, ws.tmp_bytes, st), "find_rows");
-    return read_back_rows(d_result, st);
+    const PassSpec spec{smgpu_find_kmers_workspace_bytes(cap, n_records), "smgpu_find_kmers_workspace_bytes", nullptr, nullptr, false, "matched"};
+    return records_pass(
+        spec, len, d_starts, n_records, cap, d_result, d_ws, ws_bytes, st, exceeded,
+        [&](const PairWorkspace& ws) {
+            // the query goes to the device here, behind the verdict on the starts: refused starts upload nothing, and where both
+            // are wrong the starts' error is the one raised
+            hip_check(find_pairs_launch(d_seq, len, ksize, q->mh.seed, query_on_device(q), ws.d_pair_hash, ws.d_pair_pos, (unsigned long long*)d_result, cap, 0, st),
+                      "find_kmers");
+        },
+        [&](const PairWorkspace& ws, uint64_t n_pairs) {
+            hip_check(find_rows_launch(d_seq, len, ws.d_pair_hash, ws.d_pair_pos, n_pairs, d_starts, n_records, ksize, d_positions, d_hashes, d_kmers, d_offsets,
+                                       d_result + 1, ws.d_tmp, ws.tmp_bytes, st), "find_rows");
+        });
 }
 
 // what a file's search leaves on the host
@@ -462,21 +519,13 @@ SmgpuSketchSet* smgpu_sketchset_sketch_records(const uint8_t* d_seq, uint64_t le
     return landing<SmgpuSketchSet*>([&]() -> SmgpuSketchSet* {
         DeviceCtx& ctx = DeviceCtx::get();
         std::lock_guard<std::recursive_mutex> g(ctx.mutex());
-        return reinterpret_cast<SmgpuSketchSet*>(sketchset_from_records(d_seq, len, d_starts, n_records, ksize, seed, scaled, ctx.stream()));
+        return reinterpret_cast<SmgpuSketchSet*>(sketchset_from_records(d_seq, len, d_starts, nullptr, n_records, ksize, false, HF_DNA, false, seed, scaled, ctx.stream()));
     });
 }
 
 SmgpuSketchSet* smgpu_sketchset_sketch_file(const char* path, uint32_t ksize, uint64_t seed, uint64_t scaled) {
     return landing<SmgpuSketchSet*>([&]() -> SmgpuSketchSet* {
-        if (!path) throw err_internal("null path");
-        DeviceCtx& ctx = DeviceCtx::get();
-        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
-        hipStream_t st = ctx.stream();
-        ParsedRecords pr;
-        parse_records_file(path, pr, st);
-        std::unique_ptr<SketchSet> s(sketchset_from_records(pr.comp.as<uint8_t>(), pr.len, pr.starts.as<uint64_t>(), pr.n_records, ksize, seed, scaled, st));
-        for (uint64_t r = 0; r < pr.n_records; ++r) { s->rows[r].name = pr.names[r]; s->rows[r].filename = path; }
-        return reinterpret_cast<SmgpuSketchSet*>(s.release());
+        return reinterpret_cast<SmgpuSketchSet*>(sketchset_from_file(path, ksize, false, HF_DNA, false, seed, scaled));
     });
 }
 
@@ -538,85 +587,17 @@ SmgpuSketchSet* smgpu_sketchset_sketch_residue_records(const uint8_t* d_seq, uin
     return landing<SmgpuSketchSet*>([&]() -> SmgpuSketchSet* {
         DeviceCtx& ctx = DeviceCtx::get();
         std::lock_guard<std::recursive_mutex> g(ctx.mutex());
-        return reinterpret_cast<SmgpuSketchSet*>(sketchset_from_residue_records(d_seq, len, d_starts, d_ends, n_records, ksize, hash_function,
-                                                                                translate != 0, seed, scaled, ctx.stream()));
+        return reinterpret_cast<SmgpuSketchSet*>(sketchset_from_records(d_seq, len, d_starts, d_ends, n_records, ksize, true, hash_function, translate != 0, seed, scaled,
+                                                                        ctx.stream()));
     });
 }
 
 SmgpuSketchSet* smgpu_sketchset_sketch_residue_file(const char* path, uint32_t ksize, uint32_t hash_function, int32_t translate, uint64_t seed,
                                                     uint64_t scaled) {
     return landing<SmgpuSketchSet*>([&]() -> SmgpuSketchSet* {
-        if (!path) throw err_internal("null path");
-        DeviceCtx& ctx = DeviceCtx::get();
-        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
-        hipStream_t st = ctx.stream();
-        ParsedRecords pr;
-        parse_records_file(path, pr, st);
-        AsyncBuf ends;
-        file_record_ends(pr, ends, st);
-        std::unique_ptr<SketchSet> s(sketchset_from_residue_records(pr.comp.as<uint8_t>(), pr.len, pr.starts.as<uint64_t>(), ends.as<uint64_t>(),
-                                                                    pr.n_records, ksize, hash_function, translate != 0, seed, scaled, st));
-        for (uint64_t r = 0; r < pr.n_records; ++r) { s->rows[r].name = pr.names[r]; s->rows[r].filename = path; }
-        return reinterpret_cast<SmgpuSketchSet*>(s.release());
+        return reinterpret_cast<SmgpuSketchSet*>(sketchset_from_file(path, ksize, true, hash_function, translate != 0, seed, scaled));
     });
 }
-
-}  // extern "C"
-
-namespace {
-
-SourmashSignature** file_singleton(const char* path, const ComputeParameters& cp, bool input_is_protein, uintptr_t* n) {
-    {
-        if (cp.scaled == 0) throw err_internal("smgpu_sketch_file_singleton takes scaled sketches");
-        for (uint32_t k : cp.ksizes) {
-            if (cp.dna && (k < 1 || k > 88)) throw err_internal("per-record sketches take ksize 1 .. 88, not " + std::to_string(k));
-            if ((cp.protein || cp.dayhoff || cp.hp) && (k < 3 || k / 3 > RESIDUE_RECORDS_MAX_K))
-                throw err_internal("per-record residue sketches take ksize 1 .. 79 residues, not " + std::to_string(k / 3));
-        }
-        DeviceCtx& ctx = DeviceCtx::get();
-        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
-        hipStream_t st = ctx.stream();
-        ParsedRecords pr;
-        parse_records_file(path, pr, st);
-        std::vector<Signature> sigs;
-        sigs.reserve(pr.n_records);
-        for (uint64_t r = 0; r < pr.n_records; ++r) {
-            sigs.push_back(Signature::from_params(cp));
-            sigs.back().name = pr.names[r];
-            sigs.back().filename = std::string(path);
-        }
-        // one kernel pass per sketch of the template over the same parsed buffer and the same starts
-        const Signature tmpl = Signature::from_params(cp);
-        std::vector<uint64_t> off(pr.n_records + 1), hs, as;
-        AsyncBuf ends;
-        if (cp.protein || cp.dayhoff || cp.hp) file_record_ends(pr, ends, st);
-        for (size_t q = 0; q < tmpl.sketches.size(); ++q) {
-            const KmerMinHash& t = tmpl.sketches[q];
-            RecordsCsr csr;
-            if (t.hash_function == HF_DNA)
-                sketch_records_csr(pr.comp.as<uint8_t>(), pr.len, pr.starts.as<uint64_t>(), pr.n_records, t.ksize, t.seed, t.max_hash, t.track_abundance, csr, st);
-            else
-                residue_records_csr(pr.comp.as<uint8_t>(), pr.len, pr.starts.as<uint64_t>(), ends.as<uint64_t>(), pr.n_records, t.ksize / 3, t.hash_function,
-                                    !input_is_protein, t.seed, t.max_hash, t.track_abundance, csr, st);
-            hs.resize(csr.total); as.resize(t.track_abundance ? csr.total : 0);
-            hip_check(hipMemcpyAsync(off.data(), csr.offsets.p, (pr.n_records + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
-            if (csr.total) hip_check(hipMemcpyAsync(hs.data(), csr.hashes.p, csr.total * 8, hipMemcpyDeviceToHost, st), "D2H");
-            if (csr.total && t.track_abundance) hip_check(hipMemcpyAsync(as.data(), csr.abunds.p, csr.total * 8, hipMemcpyDeviceToHost, st), "D2H");
-            hip_check(hipStreamSynchronize(st), "sync");
-            for (uint64_t r = 0; r < pr.n_records; ++r) {
-                KmerMinHash& mh = sigs[r].sketches[q];
-                mh.mins.assign(hs.begin() + (long)off[r], hs.begin() + (long)off[r + 1]);
-                if (t.track_abundance) mh.abunds.assign(as.begin() + (long)off[r], as.begin() + (long)off[r + 1]);
-                mh.touch();
-            }
-        }
-        return sigs_out(std::move(sigs), n);
-    }
-}
-
-}  // namespace
-
-extern "C" {
 
 SmgpuKmerQuery* smgpu_kmerquery_new(const SourmashKmerMinHash* const* mhs, uintptr_t n) {
     return landing<SmgpuKmerQuery*>([&]() -> SmgpuKmerQuery* {
@@ -625,7 +606,7 @@ SmgpuKmerQuery* smgpu_kmerquery_new(const SourmashKmerMinHash* const* mhs, uintp
             if (!mhs[i]) throw err_internal("null sketch");
         const KmerMinHash& first = *MH(mhs[0]);
         if (first.hash_function != HF_DNA)
-            throw Error(E_MISMATCH_DNA_PROT, std::string("k-mer finding takes DNA sketches, not ") + moltype_name(first.hash_function));
+            throw Error(E_MISMATCH_DNA_PROT, std::string("k-mer finding takes DNA sketches, not ") + molecule_name(first.hash_function));
         std::unique_ptr<KmerQuery> q(new KmerQuery());
         q->mh = KmerMinHash(first.scaled(), first.ksize, first.hash_function, first.seed, false, first.num);   // copy_and_clear, flat
         q->mh.max_hash = first.max_hash;
@@ -664,7 +645,6 @@ uint64_t smgpu_find_kmers_raw(const SmgpuKmerQuery* query, const uint8_t* d_seq,
                               uint64_t* d_result, void* d_workspace, uint64_t workspace_bytes, void* stream) {
     uint64_t ret = ~0ull;
     landing_void([&] {
-        ret = ~0ull;
         ret = find_kmers_run(reinterpret_cast<const KmerQuery*>(query), d_seq, len, d_starts, n_records, d_positions, d_hashes, d_kmers, capacity,
                              d_offsets, d_result, d_workspace, workspace_bytes, (hipStream_t)stream, nullptr);
     });
@@ -705,19 +685,14 @@ SmgpuKmerMatches* smgpu_find_kmers_file(const SmgpuKmerQuery* query, const char*
         hip_check(hipMemcpyAsync(m->starts.data(), pr.starts.p, (pr.n_records + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
         // pairs the buffer is expected to match: the sketch's share of its positions, never more than the query could place
         AsyncBuf result(64, st), d_offsets((pr.n_records + 1) * 8 + 16, st);
-        uint64_t cap = records_pair_estimate(pr.len, q->mh.max_hash);
         AsyncBuf d_pos, d_hash, d_kmers;
-        for (int attempt = 0;; ++attempt) {
+        m->n_rows = with_pair_capacity(records_pair_estimate(pr.len, q->mh.max_hash), [&](uint64_t cap, uint64_t* exceeded) {
             d_pos.reset(cap * 8 + 16, st); d_hash.reset(cap * 8 + 16, st); d_kmers.reset(cap * k + 16, st);
             const uint64_t ws_bytes = smgpu_find_kmers_workspace_bytes(cap, pr.n_records);
             AsyncBuf ws((size_t)ws_bytes, st);
-            uint64_t exceeded = 0;
-            const uint64_t n = find_kmers_run(q, pr.comp.as<uint8_t>(), pr.len, pr.starts.as<uint64_t>(), pr.n_records, d_pos.as<uint64_t>(),
-                                              d_hash.as<uint64_t>(), d_kmers.as<uint8_t>(), cap, d_offsets.as<uint64_t>(), result.as<uint64_t>(),
-                                              ws.p, ws_bytes, st, attempt == 0 ? &exceeded : nullptr);
-            if (n != ~0ull) { m->n_rows = n; break; }
-            cap = exceeded;                                          // repetitive input beat the estimate: once more with the count
-        }
+            return find_kmers_run(q, pr.comp.as<uint8_t>(), pr.len, pr.starts.as<uint64_t>(), pr.n_records, d_pos.as<uint64_t>(), d_hash.as<uint64_t>(),
+                                  d_kmers.as<uint8_t>(), cap, d_offsets.as<uint64_t>(), result.as<uint64_t>(), ws.p, ws_bytes, st, exceeded);
+        });
         m->positions.resize(m->n_rows); m->hashes.resize(m->n_rows); m->kmers.resize(m->n_rows * k);
         hip_check(hipMemcpyAsync(m->offsets.data(), d_offsets.p, (pr.n_records + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
         if (m->n_rows) {

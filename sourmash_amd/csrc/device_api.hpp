@@ -8,6 +8,14 @@
 
 namespace smg {
 
+// x rounded up to the 256-byte granule the workspaces are carved in
+inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
+// workgroups for n items at `per` items each: at least one, at most `cap` (the kernels stride over the rest)
+inline unsigned grid_for(uint64_t n, unsigned per, unsigned cap) {
+    const uint64_t b = (n + per - 1) / per;
+    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
 // ---- sketch.hip ---------------------------------------------------------------
 // Append every hash h of a canonical DNA k-mer of d_seq[0,len) with 1 <= h <= thr
 // to d_out (unordered, duplicates kept); *d_count += number appended (keeps

@@ -15,8 +15,8 @@ namespace smg {
 // reach HBM.  The walk's append is LdsSink's -- a slot from the LDS counter, two LDS stores -- so the membership test, with its
 // dependent reads of the directory and of q, is not in the per-lane walk, where one lane of a wave keeps a hash once in a while
 // and the other 63 would wait for its loads; it is paid at flush time, by all BLOCK lanes at once, one staged pair each.
-// *out_count keeps counting past out_cap, entries past it are dropped.  The kernel declares the LDS and zeroes *s_cnt in front of
-// its first barrier.
+// *out_count keeps counting past out_cap, entries past it are dropped.  The kernel declares the LDS; pair_walk zeroes *s_cnt in
+// front of its first barrier.
 template <int CAP, int BLOCK>
 struct FilterSink {
     uint64_t* s_hash;
@@ -86,65 +86,28 @@ struct FilterSink {
     }
 };
 
-// records_dna_kernel's walk (records_kernel.hpp: the same staging, the same tiles, the same per-lane code and the same emit, which
-// only appends (hash, position) to LDS staging) with the filtering sink: every k-mer of seq whose canonical hash h, 1 <= h <=
-// query.max_hash, is a member of the query is appended to out_hash together with the position of its first byte in the caller's
-// buffer, in out_pos.  Unordered; *out_count keeps counting past out_cap.  seq is 16-byte aligned, its first `skip` bytes precede
-// the caller's buffer (len includes them).
+// pair_walk (records_kernel.hpp) with the filtering sink: every k-mer of seq whose canonical hash h, 1 <= h <= query.max_hash, is
+// a member of the query is appended to out_hash together with the position of its first byte in the caller's buffer, in out_pos.
+// Unordered; *out_count keeps counting past out_cap.  seq is 16-byte aligned, its first `skip` bytes precede the caller's buffer
+// (len includes them).
 template <int K, int P>
 __global__ __launch_bounds__(SK_BLOCK) void find_dna_kernel(
     const uint8_t* __restrict__ seq, uint64_t len, uint64_t seed, FindQuery query,
     uint64_t* __restrict__ out_hash, uint64_t* __restrict__ out_pos, unsigned long long* __restrict__ out_count, uint64_t out_cap,
     uint64_t n_tiles, uint32_t skip) {
-    using T = TileGeom<K, P, SK_BLOCK>;
-    constexpr int TILE = T::TILE, LANE_RD = T::LANE_RD, IN_CHUNKS = T::IN_CHUNKS;
-    constexpr bool STAGED = sk_staged(K);
-    static_assert(P == 16, "lane runs of 16 positions");
-
+    constexpr int IN_CHUNKS = TileGeom<K, P, SK_BLOCK>::IN_CHUNKS;
     __shared__ __attribute__((aligned(16))) uint32_t s_in[IN_CHUNKS * 4];
-    __shared__ __attribute__((aligned(16))) uint32_t s_comp[STAGED ? IN_CHUNKS * 4 : 4];
+    __shared__ __attribute__((aligned(16))) uint32_t s_comp[sk_staged(K) ? IN_CHUNKS * 4 : 4];
     __shared__ unsigned int s_dirty;
     __shared__ uint64_t s_hash[REC_OUT_CAP];
     __shared__ uint64_t s_pos[REC_OUT_CAP];
     __shared__ unsigned int s_cnt;
     const FilterSink<REC_OUT_CAP, SK_BLOCK> sink{s_hash, s_pos, &s_cnt, query, out_hash, out_pos, out_count, out_cap};
-    const uint64_t thr = query.max_hash;
-
-    const int tid = threadIdx.x;
-    if (tid == 0) s_cnt = 0;
-
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint64_t base = tile * (uint64_t)TILE;
-        if constexpr (STAGED) {
-            if (tid == 0) s_dirty = 0;
-        }
-        __syncthreads();
-        stage_tile<IN_CHUNKS, STAGED, SK_BLOCK>(seq, base, len, skip, s_in, s_comp, &s_dirty);
-        __syncthreads();
-        uint32_t raw[LANE_RD];
-        read_window<LANE_RD, P>(s_in, tid, raw);
-        auto emit = [&](int o, uint64_t h) {
-            // the position is made here, behind opaque(), as in records_dna_kernel: see the note there
-            const uint64_t pos = base + (uint64_t)(opaque(threadIdx.x) * P + (uint32_t)o) - skip;
-            sink.append(h, pos);
-        };
-        if constexpr (STAGED) {
-            uint32_t comp[LANE_RD];
-            read_window<LANE_RD, P>(s_comp, tid, comp);
-            const bool dirty = __builtin_amdgcn_readfirstlane(s_dirty) != 0;
-            process_lane_staged<K, P, true, sk_plain_mul(K, false)>(raw, comp, dirty, seed, thr, emit);
-        } else {
-            process_lane<K, P, true, sk_plain_mul(K, false)>(raw, seed, thr, emit);
-        }
-        __syncthreads();
-        sink.flush(REC_OUT_CAP / 2);
-    }
-    __syncthreads();
-    sink.flush(1);
+    pair_walk<K, P>(seq, len, seed, query.max_hash, n_tiles, skip, sink, s_in, s_comp, &s_dirty, &s_cnt);
 }
 
-// The launchers of find_dna_kernel<K, 16>, one per ksize: six parts in sketch_find_k.hip (tile_launch.hpp).  grid: 0, the
-// launcher's own number of workgroups, or exactly that many (a test's way to many tiles per workgroup on a small input).
+// The launchers of find_dna_kernel<K, 16>, one per ksize: six parts in sketch_find_k.hip (tile_launch.hpp).  grid: as in
+// launch_pair_kernel.
 struct FindLaunch {
     using fn = hipError_t (*)(const uint8_t*, uint64_t, uint64_t, FindQuery, uint64_t*, uint64_t*, unsigned long long*, uint64_t, uint32_t,
                               hipStream_t);
@@ -152,11 +115,10 @@ struct FindLaunch {
     template <int K>
     static hipError_t launch(const uint8_t* d_seq, uint64_t len, uint64_t seed, FindQuery query, uint64_t* d_hash, uint64_t* d_pos,
                              unsigned long long* d_count, uint64_t cap, uint32_t grid, hipStream_t stream) {
-        const TileSpan t = align_to_tiles(d_seq, len, (uint64_t)SK_BLOCK * 16);
-        if (t.n_tiles == 0) return hipSuccess;
-        hipLaunchKernelGGL((find_dna_kernel<K, 16>), dim3(grid ? grid : sk_grid(t.n_tiles)), dim3(SK_BLOCK), 0, stream, t.seq, t.len, seed,
-                           query, d_hash, d_pos, d_count, cap, t.n_tiles, t.skip);
-        return hipGetLastError();
+        return launch_pair_kernel(d_seq, len, grid, [&](dim3 g, const TileSpan& t) {
+            hipLaunchKernelGGL((find_dna_kernel<K, 16>), g, dim3(SK_BLOCK), 0, stream, t.seq, t.len, seed, query, d_hash, d_pos, d_count,
+                               cap, t.n_tiles, t.skip);
+        });
     }
 };
 

@@ -23,8 +23,6 @@ namespace smg {
 
 namespace {
 
-static size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-
 // Per query q of [0, m): its hits [qlo[q], qlo[q + 1]) among the hits ordered by query (query numbers start at q_base), its hashes
 // <= cutoff, whether the LDS form takes it; for those it takes, rounds = 0 and the launch's largest sizes in maxes[0 .. 1].
 // sums (may be null): the sum of common over its hits.

@@ -475,6 +475,9 @@ struct LdsSink {
     uint64_t* out[NV];
     unsigned long long* out_count;
     uint64_t out_cap;
+    // The staging store names its address space.  As a generic pointer it has the type of the spill's store to HBM, and with
+    // NV = 2 the optimiser then merges the last store of the two branches into one flat store through a selected pointer.
+    using lds_u64 = __attribute__((address_space(3))) uint64_t;
 
     template <class... V>
     __device__ __forceinline__ void append(V... v) const {
@@ -483,7 +486,7 @@ struct LdsSink {
         const unsigned int idx = atomicAdd(s_cnt, 1u);
         if (idx < (unsigned)CAP) {
 #pragma unroll
-            for (int j = 0; j < NV; ++j) s_val[j][idx] = e[j];
+            for (int j = 0; j < NV; ++j) ((lds_u64*)s_val[j])[idx] = e[j];
         } else {  // pathological density (e.g. scaled == 1): spill straight to HBM
             const unsigned long long g = atomicAdd(out_count, 1ull);
             if (g < out_cap) {

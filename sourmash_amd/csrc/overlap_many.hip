@@ -21,8 +21,6 @@ namespace smg {
 
 namespace {
 
-static size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-
 // keys[j] / vals[j]: the hashes of the query rows back to back and the number of the row each came from
 __global__ __launch_bounds__(256) void many_expand_kernel(const uint64_t* __restrict__ hashes, const uint64_t* __restrict__ offsets, uint64_t m,
                                                           uint64_t total, uint64_t* __restrict__ keys, uint64_t* __restrict__ vals) {

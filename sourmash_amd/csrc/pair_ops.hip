@@ -202,11 +202,6 @@ __global__ __launch_bounds__(256) void argmax_kernel(const unsigned long long* _
     if ((threadIdx.x & 63) == 0 && k) atomicMax(best, k);
 }
 
-static unsigned grid_for(uint64_t n, unsigned per = 256, unsigned cap = 2048) {
-    const uint64_t b = (n + per - 1) / per;
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 hipError_t pair_match_launch(const uint64_t* A, uint64_t na, const uint64_t* B, uint64_t nb, const uint64_t* abA,
                              const uint64_t* abB, uint8_t* flags, unsigned long long* sums, int invert,
                              hipStream_t stream) {
@@ -214,21 +209,21 @@ hipError_t pair_match_launch(const uint64_t* A, uint64_t na, const uint64_t* B, 
         if (flags && na) return hipMemsetAsync(flags, invert ? 1 : 0, na, stream);
         return hipSuccess;
     }
-    hipLaunchKernelGGL(pair_match_kernel, dim3(grid_for(na)), dim3(256), 0, stream, A, na, B, nb, abA, abB, flags, sums,
+    hipLaunchKernelGGL(pair_match_kernel, dim3(grid_for(na, 256, 2048)), dim3(256), 0, stream, A, na, B, nb, abA, abB, flags, sums,
                        invert);
     return hipGetLastError();
 }
 
 hipError_t sumsq_launch(const uint64_t* a, uint64_t n, unsigned long long* dst, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for(n)), dim3(256), 0, stream, a, n, dst);
+    hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, stream, a, n, dst);
     return hipGetLastError();
 }
 
 hipError_t num_rank_launch(const uint64_t* I, uint64_t ni, const uint64_t* A, uint64_t na, const uint64_t* B,
                            uint64_t nb, uint64_t num, unsigned long long* dst, hipStream_t stream) {
     if (ni == 0) return hipSuccess;
-    hipLaunchKernelGGL(num_rank_kernel, dim3(grid_for(ni)), dim3(256), 0, stream, I, ni, A, na, B, nb, num, dst);
+    hipLaunchKernelGGL(num_rank_kernel, dim3(grid_for(ni, 256, 2048)), dim3(256), 0, stream, I, ni, A, na, B, nb, num, dst);
     return hipGetLastError();
 }
 
@@ -297,7 +292,7 @@ hipError_t copy_rows_launch(const uint64_t* src, const uint64_t* src_off, const 
 hipError_t argmax_launch(const unsigned long long* overlap, uint64_t ndb, uint64_t index_base,
                          unsigned long long* best, hipStream_t stream) {
     if (ndb == 0) return hipSuccess;
-    hipLaunchKernelGGL(argmax_kernel, dim3(grid_for(ndb)), dim3(256), 0, stream, overlap, ndb, index_base, best);
+    hipLaunchKernelGGL(argmax_kernel, dim3(grid_for(ndb, 256, 2048)), dim3(256), 0, stream, overlap, ndb, index_base, best);
     return hipGetLastError();
 }
 

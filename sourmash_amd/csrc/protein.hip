@@ -21,6 +21,7 @@
 #include "murmur3.hpp"
 #include "residues.hpp"
 #include "residue_core.hpp"
+#include "residue_kernel.hpp"
 #include "translate_core.hpp"
 
 namespace smg {
@@ -61,17 +62,7 @@ __global__ __launch_bounds__(256) void residues_kernel(const uint8_t* __restrict
 __global__ __launch_bounds__(256) void translate_kernel(const uint8_t* __restrict__ seq, uint64_t len, uint32_t hf,
                                                         uint8_t* __restrict__ aa, uint64_t total) {
     __shared__ uint8_t code_f[256], code_r[256], codon[216];
-    {
-        const uint8_t c = ascii_upper((uint8_t)threadIdx.x);
-        code_f[threadIdx.x] = (uint8_t)nt_code(c);
-        code_r[threadIdx.x] = (uint8_t)nt_code(dna_complement_or_nul(c));
-        if (threadIdx.x < 216) {
-            const char* letters = "ACGTN?";                            // '?' stands for every byte that is no base
-            const int x = threadIdx.x / 36, y = (threadIdx.x / 6) % 6, z = threadIdx.x % 6;
-            codon[threadIdx.x] = residue_encode(translate_codon((uint8_t)letters[x], (uint8_t)letters[y], (uint8_t)letters[z]), hf);
-        }
-    }
-    __syncthreads();
+    fill_translate_tables(code_f, code_r, codon, hf);
     uint64_t start[7];
     start[0] = 0;
     for (int s = 0; s < 6; ++s) start[s + 1] = start[s] + frame_residues(len, s >> 1) + 1;
@@ -97,17 +88,7 @@ __global__ __launch_bounds__(256) void translate_kernel(const uint8_t* __restric
 __global__ __launch_bounds__(256) void translate_words_kernel(const uint8_t* __restrict__ seq, uint64_t len, uint32_t hf,
                                                               uint8_t* __restrict__ aa, uint64_t total) {
     __shared__ uint8_t code_f[256], code_r[256], codon[216];
-    {
-        const uint8_t c = ascii_upper((uint8_t)threadIdx.x);
-        code_f[threadIdx.x] = (uint8_t)nt_code(c);
-        code_r[threadIdx.x] = (uint8_t)nt_code(dna_complement_or_nul(c));
-        if (threadIdx.x < 216) {
-            const char* letters = "ACGTN?";                            // '?' stands for every byte that is no base
-            const int x = threadIdx.x / 36, y = (threadIdx.x / 6) % 6, z = threadIdx.x % 6;
-            codon[threadIdx.x] = residue_encode(translate_codon((uint8_t)letters[x], (uint8_t)letters[y], (uint8_t)letters[z]), hf);
-        }
-    }
-    __syncthreads();
+    fill_translate_tables(code_f, code_r, codon, hf);
     const TranslateLayout L = translate_layout(len);
     const TranslateTables T{code_f, code_r, codon};
     const uint64_t n_words = (total + 3) / 4;
@@ -145,75 +126,33 @@ __global__ __launch_bounds__(256) void window_kernel(const uint8_t* __restrict__
     }
 }
 
-constexpr int RW_BLOCK = 256;
 constexpr int RW_OUT_CAP = 2048;     // LDS staging entries for kept hashes (16 KiB)
 
+// residue_kernel.hpp's rounds: the dense form writes every window's hash at its start, the other keeps 1 <= h <= thr in an LdsSink
 template <int NB, bool DENSE>
 __global__ __launch_bounds__(RW_BLOCK) void window_fast_kernel(const uint64_t* __restrict__ aa64, uint64_t n, ResidueTail t, uint64_t seed,
                                                                uint64_t thr, uint64_t* __restrict__ out,
-                                                               unsigned long long* __restrict__ out_count, uint64_t cap, uint64_t n_lanes) {
-    __shared__ uint64_t s_out[RW_OUT_CAP];
-    __shared__ unsigned int s_cnt;
-    __shared__ unsigned long long s_base;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_cnt = 0;
-    __syncthreads();
-    auto flush = [&](unsigned int at_least) {                            // (called by every thread of the block)
+                                                               unsigned long long* __restrict__ out_count, uint64_t cap) {
+    if constexpr (DENSE) {
+        residue_rounds<NB, true>(aa64, n, t, seed, [&](uint64_t start, uint64_t h) { if (start < cap) out[start] = h; }, [] {});
+    } else {
+        __shared__ uint64_t s_out[RW_OUT_CAP];
+        __shared__ unsigned int s_cnt;
+        __shared__ unsigned long long s_base;
+        const LdsSink<RW_OUT_CAP, RW_BLOCK, 1> sink{{s_out}, &s_cnt, &s_base, {out}, out_count, cap};
+        if (threadIdx.x == 0) s_cnt = 0;
         __syncthreads();
-        const unsigned int cnt = s_cnt;
-        if (cnt >= at_least && cnt) {
-            const unsigned int m = cnt < (unsigned)RW_OUT_CAP ? cnt : (unsigned)RW_OUT_CAP;
-            if (tid == 0) s_base = atomicAdd(out_count, (unsigned long long)m);
-            __syncthreads();
-            const unsigned long long b = s_base;
-            for (unsigned int i = tid; i < m; i += RW_BLOCK)
-                if (b + i < cap) out[b + i] = s_out[i];
-            __syncthreads();
-            if (tid == 0) s_cnt = 0;
-        }
-        __syncthreads();
-    };
-    const uint64_t rounds = (n_lanes + (uint64_t)gridDim.x * RW_BLOCK - 1) / ((uint64_t)gridDim.x * RW_BLOCK);
-    for (uint64_t r = 0; r < rounds; ++r) {                              // (uniform trip count: the flush has barriers)
-        const uint64_t g = (r * gridDim.x + blockIdx.x) * RW_BLOCK + tid;
-        if (g < n_lanes)
-            residue_windows_lane<NB>(aa64, n, g, t, seed, [&](uint64_t start, uint64_t h) {
-                if constexpr (DENSE) {
-                    if (start < cap) out[start] = h;
-                } else if ((h - 1) < thr) {
-                    const unsigned int idx = atomicAdd(&s_cnt, 1u);
-                    if (idx < (unsigned)RW_OUT_CAP) {
-                        s_out[idx] = h;
-                    } else {                                             // pathological density: straight to HBM
-                        const unsigned long long gi = atomicAdd(out_count, 1ull);
-                        if (gi < cap) out[gi] = h;
-                    }
-                }
-            });
-        if constexpr (!DENSE) flush(RW_OUT_CAP / 2);
+        residue_rounds_kept<NB, true>(aa64, n, t, seed, thr, sink);
     }
-    if constexpr (!DENSE) flush(1);
 }
 
 template <int NB>
 hipError_t window_fast_launch(const uint8_t* d_aa, uint64_t n, uint32_t k, uint64_t seed, uint64_t thr, uint64_t* d_out,
                               unsigned long long* d_count, uint64_t cap, bool dense, hipStream_t stream) {
-    const uint64_t n_lanes = (n - k + 1 + RW_P - 1) / RW_P;              // lanes that own at least one window start
-    const uint64_t blocks = (n_lanes + RW_BLOCK - 1) / RW_BLOCK;
-    const unsigned grid = (unsigned)(blocks < 1 ? 1 : (blocks > 256 * 8 ? 256 * 8 : blocks));
-    const ResidueTail t = residue_tail(k);
-    if (dense)
-        hipLaunchKernelGGL((window_fast_kernel<NB, true>), dim3(grid), dim3(RW_BLOCK), 0, stream, (const uint64_t*)d_aa, n, t, seed, thr, d_out,
-                           d_count, cap, n_lanes);
-    else
-        hipLaunchKernelGGL((window_fast_kernel<NB, false>), dim3(grid), dim3(RW_BLOCK), 0, stream, (const uint64_t*)d_aa, n, t, seed, thr, d_out,
-                           d_count, cap, n_lanes);
+    const auto kernel = dense ? window_fast_kernel<NB, true> : window_fast_kernel<NB, false>;
+    hipLaunchKernelGGL(kernel, dim3(residue_grid(n, k)), dim3(RW_BLOCK), 0, stream, (const uint64_t*)d_aa, n, residue_tail(k), seed, thr, d_out,
+                       d_count, cap);
     return hipGetLastError();
-}
-
-unsigned grid_for(uint64_t n) {
-    const uint64_t b = (n + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
 }  // namespace
@@ -222,16 +161,16 @@ uint64_t translated_bytes(uint64_t len) { return translate_layout(len).start[6];
 
 hipError_t residues_launch(const uint8_t* d_seq, uint64_t len, uint32_t hash_function, uint8_t* d_aa, hipStream_t stream) {
     if (len == 0) return hipSuccess;
-    hipLaunchKernelGGL(residues_kernel, dim3(grid_for(len)), dim3(256), 0, stream, d_seq, len, hash_function, d_aa);
+    hipLaunchKernelGGL(residues_kernel, dim3(grid_for(len, 256, 8192)), dim3(256), 0, stream, d_seq, len, hash_function, d_aa);
     return hipGetLastError();
 }
 
 hipError_t translate_launch(const uint8_t* d_seq, uint64_t len, uint32_t hash_function, uint8_t* d_aa, hipStream_t stream) {
     const uint64_t total = translated_bytes(len);                       // (len < 3: six separators, no base is read)
     if ((((uintptr_t)d_seq | (uintptr_t)d_aa) & 3) == 0)
-        hipLaunchKernelGGL(translate_words_kernel, dim3(grid_for((total + 3) / 4)), dim3(256), 0, stream, d_seq, len, hash_function, d_aa, total);
+        hipLaunchKernelGGL(translate_words_kernel, dim3(grid_for((total + 3) / 4, 256, 8192)), dim3(256), 0, stream, d_seq, len, hash_function, d_aa, total);
     else
-        hipLaunchKernelGGL(translate_kernel, dim3(grid_for(total)), dim3(256), 0, stream, d_seq, len, hash_function, d_aa, total);
+        hipLaunchKernelGGL(translate_kernel, dim3(grid_for(total, 256, 8192)), dim3(256), 0, stream, d_seq, len, hash_function, d_aa, total);
     return hipGetLastError();
 }
 
@@ -250,7 +189,7 @@ hipError_t residue_windows_launch(const uint8_t* d_aa, uint64_t n, uint32_t k, u
         default: return window_fast_launch<4>(d_aa, n, k, seed, thr, d_out, d_count, cap, dense, stream);
         }
     }
-    hipLaunchKernelGGL(window_kernel, dim3(grid_for(n - k + 1)), dim3(256), 0, stream, d_aa, n, k, seed, thr, d_out, d_count,
+    hipLaunchKernelGGL(window_kernel, dim3(grid_for(n - k + 1, 256, 8192)), dim3(256), 0, stream, d_aa, n, k, seed, thr, d_out, d_count,
                        cap, dense ? 1 : 0);
     return hipGetLastError();
 }

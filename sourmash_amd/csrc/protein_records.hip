@@ -7,8 +7,8 @@
 //   translate  (DNA input) translate_records_kernel: every record's six frames into a block of its own of one residue buffer
 //              (translate_records_core.hpp); the block starts are an exclusive scan of the block sizes.  Protein input goes
 //              through residues_kernel (protein.hip) as a whole: positions in the residue buffer are positions in the input.
-//   pairs      window_pairs_kernel<NB>: window_fast_kernel's walk (protein.hip; residue_core.hpp holds the lane) with a
-//              (hash, window start) sink.  The kernel knows nothing about records.
+//   pairs      window_pairs_kernel<NB>: the round loop of the residue window kernels (residue_kernel.hpp; residue_core.hpp holds
+//              the lane) with a (hash, window start) sink.  The kernel knows nothing about records.
 //   the rest   records_csr_ends_launch (sketch_records.hip): assign by the rule with explicit ends (records_core.hpp), sort by
 //              (record, hash), offsets.
 #include <hip/hip_runtime.h>
@@ -18,6 +18,7 @@
 #include "murmur3.hpp"
 #include "residues.hpp"
 #include "residue_core.hpp"
+#include "residue_kernel.hpp"
 #include "records_core.hpp"
 #include "translate_records_core.hpp"
 
@@ -25,75 +26,35 @@ namespace smg {
 
 namespace {
 
-constexpr int RWP_BLOCK = 256;
 // LDS staging entries for kept (hash, start) pairs: 2 x 8 KiB, the 16 KiB of window_fast_kernel's 2,048 hashes.  A round of a
 // workgroup covers 2,048 window starts; at scaled = 200 it keeps about ten of them.
 constexpr int RWP_OUT_CAP = 1024;
 
-// n: the bytes of the residue buffer, *d_n when d_n is not null (the translated size is known on the device only), else n_host.
-// The buffer is read as aligned 8-byte words up to ceil(n / 8).  SEP: 0xFF bytes separate (the translated buffer); protein input
-// has no separators -- the records' ends do that work -- and a 0xFF byte in it is hashed as the reference hashes it.
+// residue_kernel.hpp's rounds with a (hash, window start) sink.  n: residue_n(n_host, d_n); the buffer is read as aligned 8-byte
+// words up to ceil(n / 8).  SEP: 0xFF bytes separate (the translated buffer); protein input has no separators -- the records'
+// ends do that work -- and a 0xFF byte in it is hashed as the reference hashes it.
 template <int NB, bool SEP>
-__global__ __launch_bounds__(RWP_BLOCK) void window_pairs_kernel(const uint64_t* __restrict__ aa64, uint64_t n_host, const uint64_t* __restrict__ d_n,
-                                                                 ResidueTail t, uint64_t seed, uint64_t thr, uint64_t* __restrict__ out_hash,
-                                                                 uint64_t* __restrict__ out_pos, unsigned long long* __restrict__ out_count,
-                                                                 uint64_t cap) {
+__global__ __launch_bounds__(RW_BLOCK) void window_pairs_kernel(const uint64_t* __restrict__ aa64, uint64_t n_host, const uint64_t* __restrict__ d_n,
+                                                                ResidueTail t, uint64_t seed, uint64_t thr, uint64_t* __restrict__ out_hash,
+                                                                uint64_t* __restrict__ out_pos, unsigned long long* __restrict__ out_count,
+                                                                uint64_t cap) {
     __shared__ uint64_t s_hash[RWP_OUT_CAP];
     __shared__ uint64_t s_pos[RWP_OUT_CAP];
     __shared__ unsigned int s_cnt;
     __shared__ unsigned long long s_base;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_cnt = 0;
+    const LdsSink<RWP_OUT_CAP, RW_BLOCK, 2> sink{{s_hash, s_pos}, &s_cnt, &s_base, {out_hash, out_pos}, out_count, cap};
+    if (threadIdx.x == 0) s_cnt = 0;
     __syncthreads();
-    auto flush = [&](unsigned int at_least) {                            // (called by every thread of the block)
-        __syncthreads();
-        const unsigned int cnt = s_cnt;
-        if (cnt >= at_least && cnt) {
-            const unsigned int m = cnt < (unsigned)RWP_OUT_CAP ? cnt : (unsigned)RWP_OUT_CAP;
-            if (tid == 0) s_base = atomicAdd(out_count, (unsigned long long)m);
-            __syncthreads();
-            const unsigned long long b = s_base;
-            for (unsigned int i = tid; i < m; i += RWP_BLOCK)
-                if (b + i < cap) { out_hash[b + i] = s_hash[i]; out_pos[b + i] = s_pos[i]; }
-            __syncthreads();
-            if (tid == 0) s_cnt = 0;
-        }
-        __syncthreads();
-    };
-    const uint64_t n = d_n ? *d_n : n_host;
-    const uint64_t n_lanes = n >= (uint64_t)t.k ? (n - t.k + 1 + RW_P - 1) / RW_P : 0;     // lanes that own at least one window start
-    const uint64_t rounds = (n_lanes + (uint64_t)gridDim.x * RWP_BLOCK - 1) / ((uint64_t)gridDim.x * RWP_BLOCK);
-    for (uint64_t r = 0; r < rounds; ++r) {                              // (uniform trip count: the flush has barriers)
-        const uint64_t g = (r * gridDim.x + blockIdx.x) * RWP_BLOCK + tid;
-        if (g < n_lanes)
-            residue_windows_lane<NB, SEP>(aa64, n, g, t, seed, [&](uint64_t start, uint64_t h) {
-                if ((h - 1) < thr) {
-                    const unsigned int idx = atomicAdd(&s_cnt, 1u);
-                    if (idx < (unsigned)RWP_OUT_CAP) {
-                        s_hash[idx] = h; s_pos[idx] = start;
-                    } else {                                             // pathological density: straight to HBM
-                        const unsigned long long gi = atomicAdd(out_count, 1ull);
-                        if (gi < cap) { out_hash[gi] = h; out_pos[gi] = start; }
-                    }
-                }
-            });
-        flush(RWP_OUT_CAP / 2);
-    }
-    flush(1);
+    residue_rounds_kept<NB, SEP>(aa64, residue_n(n_host, d_n), t, seed, thr, sink);
 }
 
 template <int NB>
 hipError_t window_pairs_launch(const uint8_t* d_aa, uint64_t n_bound, const uint64_t* d_n, uint32_t k, uint64_t seed, uint64_t thr,
                                uint64_t* d_hash, uint64_t* d_pos, unsigned long long* d_count, uint64_t cap, hipStream_t stream) {
-    const uint64_t n_lanes = (n_bound - k + 1 + RW_P - 1) / RW_P;
-    const uint64_t blocks = (n_lanes + RWP_BLOCK - 1) / RWP_BLOCK;
-    const unsigned grid = (unsigned)(blocks < 1 ? 1 : (blocks > 256 * 8 ? 256 * 8 : blocks));
-    if (d_n)                                                             // (the translated buffer: a size on the device, separators)
-        hipLaunchKernelGGL((window_pairs_kernel<NB, true>), dim3(grid), dim3(RWP_BLOCK), 0, stream, (const uint64_t*)d_aa, n_bound, d_n,
-                           residue_tail(k), seed, thr, d_hash, d_pos, d_count, cap);
-    else
-        hipLaunchKernelGGL((window_pairs_kernel<NB, false>), dim3(grid), dim3(RWP_BLOCK), 0, stream, (const uint64_t*)d_aa, n_bound, d_n,
-                           residue_tail(k), seed, thr, d_hash, d_pos, d_count, cap);
+    // (d_n: the translated buffer -- a size on the device, separators)
+    const auto kernel = d_n ? window_pairs_kernel<NB, true> : window_pairs_kernel<NB, false>;
+    hipLaunchKernelGGL(kernel, dim3(residue_grid(n_bound, k)), dim3(RW_BLOCK), 0, stream, (const uint64_t*)d_aa, n_bound, d_n, residue_tail(k), seed,
+                       thr, d_hash, d_pos, d_count, cap);
     return hipGetLastError();
 }
 
@@ -110,35 +71,18 @@ __global__ __launch_bounds__(256) void translate_records_kernel(const uint8_t* _
                                                                 const uint64_t* __restrict__ ends, const uint64_t* __restrict__ block_starts,
                                                                 uint64_t n_records, uint32_t hf, uint64_t* __restrict__ aa64) {
     __shared__ uint8_t code_f[256], code_r[256], codon[216];
-    {
-        const uint8_t c = ascii_upper((uint8_t)threadIdx.x);
-        code_f[threadIdx.x] = (uint8_t)nt_code(c);
-        code_r[threadIdx.x] = (uint8_t)nt_code(dna_complement_or_nul(c));
-        if (threadIdx.x < 216) {
-            const char* letters = "ACGTN?";                            // '?' stands for every byte that is no base
-            const int x = threadIdx.x / 36, y = (threadIdx.x / 6) % 6, z = threadIdx.x % 6;
-            codon[threadIdx.x] = residue_encode(translate_codon((uint8_t)letters[x], (uint8_t)letters[y], (uint8_t)letters[z]), hf);
-        }
-    }
-    __syncthreads();
+    fill_translate_tables(code_f, code_r, codon, hf);
     const TranslateTables T{code_f, code_r, codon};
     const uint64_t n_words = (block_starts[n_records] + 7) / 8;
     for (uint64_t G = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; G < n_words; G += (uint64_t)gridDim.x * blockDim.x)
         aa64[G] = translate_records_word(seq, starts, ends, block_starts, n_records, T, G);
 }
 
-size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-
 size_t scan_temp_bytes(uint64_t n) {
     size_t bytes = 0;
     (void)rocprim::exclusive_scan(nullptr, bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)(n ? n : 1), rocprim::plus<uint64_t>(),
                                   (hipStream_t)0);
     return bytes;
-}
-
-unsigned grid_for(uint64_t n) {
-    const uint64_t b = (n + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
 }  // namespace
@@ -166,7 +110,7 @@ hipError_t translate_records_launch(const uint8_t* d_seq, uint64_t len, const ui
                                     hipStream_t stream) {
     if (((uintptr_t)d_aa & 7) != 0 || temp_bytes < translate_records_temp_bytes(n_records)) return hipErrorInvalidValue;
     uint64_t* d_sizes = (uint64_t*)d_temp;
-    hipLaunchKernelGGL(block_sizes_kernel, dim3(grid_for(n_records + 1)), dim3(256), 0, stream, d_starts, d_ends, n_records, d_sizes);
+    hipLaunchKernelGGL(block_sizes_kernel, dim3(grid_for(n_records + 1, 256, 8192)), dim3(256), 0, stream, d_starts, d_ends, n_records, d_sizes);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     size_t bytes = temp_bytes - al256((n_records + 1) * 8);
@@ -175,7 +119,7 @@ hipError_t translate_records_launch(const uint8_t* d_seq, uint64_t len, const ui
     if (e != hipSuccess) return e;
     if (n_records == 0) return hipSuccess;
     const uint64_t words_bound = (translated_records_bound(len, n_records) + 7) / 8;
-    hipLaunchKernelGGL(translate_records_kernel, dim3(grid_for(words_bound)), dim3(256), 0, stream, d_seq, d_starts, d_ends,
+    hipLaunchKernelGGL(translate_records_kernel, dim3(grid_for(words_bound, 256, 8192)), dim3(256), 0, stream, d_seq, d_starts, d_ends,
                        (const uint64_t*)d_block_starts, n_records, hash_function, reinterpret_cast<uint64_t*>(d_aa));
     return hipGetLastError();
 }

@@ -28,7 +28,6 @@ namespace {
 
 constexpr int FD_THREADS = 256;
 
-size_t fd_al256(size_t x) { return (x + 255) / 256 * 256; }
 unsigned fd_grid(uint64_t n) { return (unsigned)((n + FD_THREADS - 1) / FD_THREADS); }
 
 // dir[b] for b = 0 .. nb
@@ -96,7 +95,7 @@ hipError_t find_pairs_launch(const uint8_t* d_seq, uint64_t len, uint32_t k, uin
     return launcher<FindLaunch>(k)(d_seq, len, seed, query, d_hash, d_pos, d_count, cap, grid, stream);
 }
 
-size_t find_rows_temp_bytes(uint64_t n_pairs) { return fd_al256(sort_pairs_temp_bytes(n_pairs ? n_pairs : 1)) + 256; }
+size_t find_rows_temp_bytes(uint64_t n_pairs) { return al256(sort_pairs_temp_bytes(n_pairs ? n_pairs : 1)) + 256; }
 
 hipError_t find_rows_launch(const uint8_t* d_seq, uint64_t len, uint64_t* d_pair_hash, uint64_t* d_pair_pos, uint64_t n_pairs,
                             const uint64_t* d_starts, uint64_t n_records, uint32_t k, uint64_t* d_positions, uint64_t* d_hashes,

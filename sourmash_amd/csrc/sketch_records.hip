@@ -28,7 +28,6 @@ namespace {
 
 constexpr int RC_THREADS = 256;
 
-size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 unsigned rc_grid(uint64_t n) { return (unsigned)((n + RC_THREADS - 1) / RC_THREADS); }
 
 // *bad |= 1: starts not ascending; |= 2: starts[n_records] > len

@@ -123,12 +123,6 @@ __global__ __launch_bounds__(256) void rare_pairs_kernel(const uint32_t* __restr
     }
 }
 
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-unsigned grid_for(uint64_t n, unsigned per = 256, unsigned cap = 8192) {
-    const uint64_t b = (n + per - 1) / per;
-    return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
 }  // namespace
 
 size_t inverted_temp_bytes(uint64_t total) {
@@ -140,7 +134,7 @@ size_t inverted_temp_bytes(uint64_t total) {
     (void)rocprim::exclusive_scan(nullptr, c, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)total + 1,
                                   rocprim::plus<uint64_t>(), (hipStream_t)0);
     size_t m = a > b ? a : b;
-    return align256(m > c ? m : c) + 256;
+    return al256(m > c ? m : c) + 256;
 }
 
 // (hash, row) of the whole CSR sorted by hash -> d_rows_sorted; runs: d_counts[u] elements each, *d_n_runs of them.
@@ -151,7 +145,7 @@ hipError_t inverted_sort_launch(const uint64_t* d_hashes, const uint64_t* d_offs
     if (total == 0 || total > 0xffffffffull) return hipErrorInvalidValue;
     hipError_t e = hipMemcpyAsync(d_keys_a, d_hashes, total * 8, hipMemcpyDeviceToDevice, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(row_ids_kernel, dim3(grid_for(((uint64_t)n + 3) / 4, 1)), dim3(256), 0, stream, d_offsets, n, d_rows_tmp);
+    hipLaunchKernelGGL(row_ids_kernel, dim3(grid_for(((uint64_t)n + 3) / 4, 1, 8192)), dim3(256), 0, stream, d_offsets, n, d_rows_tmp);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     size_t tb = temp_bytes;
@@ -176,7 +170,7 @@ hipError_t inverted_classify_launch(const uint32_t* d_counts, const uint64_t* d_
                                     uint32_t* d_freq_flag, uint64_t* d_run_off, uint64_t* d_freq_rank, unsigned long long* d_out,
                                     void* d_temp, size_t temp_bytes, hipStream_t stream) {
     if (max_runs == 0) return hipSuccess;
-    hipLaunchKernelGGL(classify_runs_kernel, dim3(grid_for(max_runs)), dim3(256), 0, stream, d_counts, d_n_runs, threshold,
+    hipLaunchKernelGGL(classify_runs_kernel, dim3(grid_for(max_runs, 256, 8192)), dim3(256), 0, stream, d_counts, d_n_runs, threshold,
                        d_freq_flag, d_out + 2);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -200,7 +194,7 @@ hipError_t inverted_apply_launch(const uint64_t* d_run_off, const uint32_t* d_fr
                            d_freq_rank, n_runs, total, d_rows_sorted, d_run_end, d_bits, words_per_row);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(runs_apply_kernel, dim3(grid_for(n_runs)), dim3(256), 0, stream, d_run_off, d_freq_flag, d_freq_rank,
+    hipLaunchKernelGGL(runs_apply_kernel, dim3(grid_for(n_runs, 256, 8192)), dim3(256), 0, stream, d_run_off, d_freq_flag, d_freq_rank,
                        n_runs, d_rows_sorted, d_run_end, d_bits, words_per_row);
     return hipGetLastError();
 }

@@ -11,6 +11,9 @@
 // the per-residue path (a handful per record).
 #pragma once
 #include <stdint.h>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
 #include "residues.hpp"
 
 namespace smg {
@@ -20,6 +23,21 @@ struct TranslateTables {          // filled from the scalar functions of residue
     const uint8_t* code_r;        // [256] byte -> code of its complement
     const uint8_t* codon;         // [216] three codes -> residue of the sketch's alphabet
 };
+
+#if defined(__HIPCC__)
+// The tables in LDS, filled by a workgroup of 256 lanes at its start; ends with the barrier behind which they are read
+__device__ __forceinline__ void fill_translate_tables(uint8_t* code_f, uint8_t* code_r, uint8_t* codon, uint32_t hf) {
+    const uint8_t c = ascii_upper((uint8_t)threadIdx.x);
+    code_f[threadIdx.x] = (uint8_t)nt_code(c);
+    code_r[threadIdx.x] = (uint8_t)nt_code(dna_complement_or_nul(c));
+    if (threadIdx.x < 216) {
+        const char* letters = "ACGTN?";                            // '?' stands for every byte that is no base
+        const int x = threadIdx.x / 36, y = (threadIdx.x / 6) % 6, z = threadIdx.x % 6;
+        codon[threadIdx.x] = residue_encode(translate_codon((uint8_t)letters[x], (uint8_t)letters[y], (uint8_t)letters[z]), hf);
+    }
+    __syncthreads();
+}
+#endif
 
 struct TranslateLayout {
     uint64_t len;

@@ -126,6 +126,22 @@ def _residue_hash_function(moltype):
         raise ValueError(f"unknown moltype {moltype!r}") from None
 
 
+def _check_records(torch, seq, starts, moltype, is_protein, ends):
+    "the argument checks of the two sketch_records (DeviceSketcher, SketchSet) -> the library's hash_function number"
+    assert seq.dtype == torch.uint8 and seq.is_cuda and seq.is_contiguous()
+    assert starts.dtype == torch.int64 and starts.is_cuda and starts.is_contiguous()
+    if starts.numel() < 1:
+        raise ValueError("record starts: n_records + 1 offsets are needed")
+    hf = _residue_hash_function(moltype)
+    if hf == 1 and (is_protein or ends is not None):
+        raise ValueError("is_protein and ends go with moltype protein, dayhoff or hp")
+    if ends is not None:
+        assert ends.dtype == torch.int64 and ends.is_cuda and ends.is_contiguous()
+        if ends.numel() != starts.numel() - 1:
+            raise ValueError("record ends: n_records offsets are needed")
+    return hf
+
+
 class DeviceSketcher:
     """Reusable scratch for sketching device-resident sequence buffers.
 
@@ -188,18 +204,8 @@ class DeviceSketcher:
         sorted distinct kept hashes (int64 tensors of u64 bit patterns; row r is hashes[offsets[r]:offsets[r + 1]]), new
         tensors.  ksize 1 .. 88.  Starts that are not ascending or end behind the buffer raise ValueError."""
         torch = self.torch
-        assert seq.dtype == torch.uint8 and seq.is_cuda and seq.is_contiguous()
-        assert starts.dtype == torch.int64 and starts.is_cuda and starts.is_contiguous()
-        if starts.numel() < 1:
-            raise ValueError("record starts: n_records + 1 offsets are needed")
+        hf = _check_records(torch, seq, starts, moltype, is_protein, ends)
         n, n_records = seq.numel(), starts.numel() - 1
-        hf = _residue_hash_function(moltype)
-        if hf == 1 and (is_protein or ends is not None):
-            raise ValueError("is_protein and ends go with moltype protein, dayhoff or hp")
-        if ends is not None:
-            assert ends.dtype == torch.int64 and ends.is_cuda and ends.is_contiguous()
-            if ends.numel() != n_records:
-                raise ValueError("record ends: n_records offsets are needed")
         translate = hf != 1 and not is_protein
         windows = 2 * n if translate else n
         expect = windows / max(self.scaled, 1)

@@ -198,19 +198,9 @@ class SketchSet(RustObject):
         moltype protein / dayhoff / hp (smgpu_sketchset_sketch_residue_records): ksize counts residues, 1 .. 79; is_protein: the
         records are residues, otherwise DNA translated in six frames record by record; ends: int64 device tensor of n_records
         offsets, record r = seq[starts[r]:ends[r]] (None: records touch)."""
-        from .device import _ptr, _records_error, _residue_hash_function, _torch
+        from .device import _check_records, _ptr, _records_error, _torch
         torch = _torch()
-        assert seq.dtype == torch.uint8 and seq.is_cuda and seq.is_contiguous()
-        assert starts.dtype == torch.int64 and starts.is_cuda and starts.is_contiguous()
-        if starts.numel() < 1:
-            raise ValueError("record starts: n_records + 1 offsets are needed")
-        hf = _residue_hash_function(moltype)
-        if hf == 1 and (is_protein or ends is not None):
-            raise ValueError("is_protein and ends go with moltype protein, dayhoff or hp")
-        if ends is not None:
-            assert ends.dtype == torch.int64 and ends.is_cuda and ends.is_contiguous()
-            if ends.numel() != starts.numel() - 1:
-                raise ValueError("record ends: n_records offsets are needed")
+        hf = _check_records(torch, seq, starts, moltype, is_protein, ends)
         torch.cuda.current_stream().synchronize()                   # the library works on its own stream
         lib.sourmash_err_clear()
         if hf == 1:

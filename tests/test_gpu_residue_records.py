@@ -226,6 +226,61 @@ def test_unaligned_pointer(sm, shift):
         check(sm, buf, starts, ends, 16 if is_protein else 10, "protein", 20, is_protein, seq_t=view)
 
 
+# ---- 4b. the pair kernel alone: a workgroup appends in the round behind a flush ---------------------------------------------------------
+# The staged pairs leave LDS through LdsSink, whose flush zeroes the counter behind its own last barrier: the round loop
+# (csrc/residue_kernel.hpp) has to put one barrier between that and the next round's appends.  2,048 workgroups of 2,048 window
+# starts make a round; workgroup 0 owns starts [0, 2048) in the first and [ROUND, ROUND + 2048) in the second.
+WG_STARTS = 2048
+ROUND = 2048 * WG_STARTS
+FLUSH_AT = 512                      # half of the 1,024 staged pairs
+
+
+@functools.lru_cache(maxsize=2)
+def two_round_hashes(k):
+    "n = one round + one workgroup + k residues, and the oracle's hash of every window by start (read-only)"
+    data = AMINO[np.random.default_rng(40 + k).integers(0, len(AMINO), size=ROUND + WG_STARTS + k)].tobytes()
+    h = oracle.seq_to_hashes_protein(data, k, "protein", 42, True)
+    assert len(h) == ROUND + WG_STARTS + 1
+    h.setflags(write=False)
+    return data, h
+
+
+@pytest.mark.parametrize("k,sep", [(10, False), (42, False), (10, True)])
+def test_pair_kernel_appends_behind_a_flush(sm, k, sep):
+    """sep: the size comes from the device and a 0xFF byte in workgroup 0's second round separates (the windows over it are
+    dropped); otherwise every byte is a residue."""
+    import torch
+    from sourmash_amd.device import DeviceSketcher
+    data, h = two_round_hashes(k)
+    keep = (h >= 1) & (h <= np.uint64(oracle.max_hash_for_scaled(2)))
+    ff = ROUND + 1000
+    if sep:
+        keep = keep.copy()
+        keep[ff - k + 1:ff + 1] = False
+    assert keep[:WG_STARTS].sum() >= FLUSH_AT, "workgroup 0 flushes behind its first round"
+    assert keep[ROUND:ROUND + WG_STARTS].sum() >= 1, "workgroup 0 appends behind that flush"
+    want_pos = np.flatnonzero(keep).astype(np.uint64)
+    n = len(data)
+    aa = torch.zeros((n + 7) // 8 * 8, dtype=torch.uint8, device="cuda")[:n]
+    aa.copy_(torch.frombuffer(bytearray(data), dtype=torch.uint8))
+    if sep:
+        aa[ff] = 0xFF
+    cap = len(h)
+    out_h = torch.zeros(cap, dtype=torch.int64, device="cuda")
+    out_p = torch.zeros(cap, dtype=torch.int64, device="cuda")
+    count = torch.zeros(1, dtype=torch.int64, device="cuda")
+    n_dev = torch.tensor([n], dtype=torch.int64, device="cuda") if sep else None
+    DeviceSketcher(ksize=k, scaled=2).residue_kernel_only(aa, out_h, out_p, count, n_dev=n_dev)
+    torch.cuda.synchronize()
+    got_n = int(count.item())
+    assert got_n == len(want_pos)
+    got_p = out_p[:got_n].cpu().numpy().view(np.uint64)
+    got_h = out_h[:got_n].cpu().numpy().view(np.uint64)
+    order = np.argsort(got_p, kind="stable")
+    assert np.array_equal(got_p[order], want_pos)
+    assert np.array_equal(got_h[order], h[keep])
+
+
 # ---- 5. SketchSet from a buffer and from files ---------------------------------------------------------------------------------------
 def fasta_text(recs, width=60, eol=b"\n"):
     out = []
@@ -428,6 +483,38 @@ def test_errors(sm):
     assert "output capacity too small: 991 kept pairs > capacity 100" in message, message
     assert int(result[0].item()) == 991
     lib.sourmash_err_clear()
+
+
+def test_residue_entries_refuse_a_dna_hash_function(sm, files):
+    """The residue entries of the C-ABI serve protein, dayhoff and hp alone: hash_function 1 (DNA; also 0 and 5) is an error with
+    the residue pass's text, and the window length is held to 1 .. 79 residues whatever the hash_function.  (Python sends DNA
+    to the DNA entries, so only a direct call gets here.)"""
+    import os
+    import torch
+    from sourmash_amd._lowlevel import decode_str, lib
+    from sourmash_amd.device import _ptr
+    seq = to_dev(torch, protein_record(np.random.default_rng(4), 1000))
+    starts = to_dev(torch, np.asarray([0, 400, 1000], dtype=np.int64))
+    path = os.fsencode(files["faa"][0])
+    torch.cuda.synchronize()
+
+    def refused(call, text):
+        lib.sourmash_err_clear()
+        ptr = call()
+        assert not ptr and lib.sourmash_err_get_last_code() != 0
+        message = decode_str(lib.sourmash_err_get_last_message())
+        lib.sourmash_err_clear()
+        assert text in message, message
+
+    not_residue = "per-record residue sketches are protein, dayhoff or hp sketches"
+    for hf in (1, 0, 5):
+        for translate in (0, 1):
+            refused(lambda: lib.smgpu_sketchset_sketch_residue_records(_ptr(seq), 1000, _ptr(starts), None, 2, 10, hf, translate, 42, 20), not_residue)
+            refused(lambda: lib.smgpu_sketchset_sketch_residue_file(path, 10, hf, translate, 42, 20), not_residue)
+    too_long = "per-record residue sketches take ksize 1 .. 79 residues, not 80"
+    for hf in (1, 2):
+        refused(lambda: lib.smgpu_sketchset_sketch_residue_records(_ptr(seq), 1000, _ptr(starts), None, 2, 80, hf, 0, 42, 20), too_long)
+        refused(lambda: lib.smgpu_sketchset_sketch_residue_file(path, 80, hf, 0, 42, 20), too_long)
 
 
 # ---- 9. downstream -----------------------------------------------------------------------------------------------------------------
