@@ -805,6 +805,58 @@ uint64_t        smgpu_manygather_scaled(const SmgpuManyGather *ptr);
 void            smgpu_manygather_stats(const SmgpuManyGather *ptr, double *out8);
 /* Test support: the caps and the batch budget smgpu_sketchset_gather_many works with (0: the default of each). */
 void smgpu_gather_many_set_limits(uint32_t max_query_hashes, uint32_t max_candidates, uint64_t batch_common);
+/* ---- the result rows of gather for many queries (csrc/gather_rows.hip, csrc/gather_rows_core.hpp) ----
+ * The reference builds a gather row per round from MinHash objects and a {hash: abundance} dictionary (GatherDatabases,
+ * src/sourmash/search.py:877-949; GatherResult.build_gather_result :480-505).  Every number of such a row is a function of a few
+ * integers per pick and the abundances of the query hashes the pick covered first; one pass over resident data gives them for the
+ * picks of every query.  The picks of query q are d_pick_rows[d_pick_offsets[q], d_pick_offsets[q + 1]) in rank order.  The OWNER
+ * of a query hash is the lowest rank among its query's picks whose row holds it: "remaining query ∩ match" of that round.
+ * Everything is taken at `cutoff` (the smaller max_hash of the two sets).  Per pick: orig_common = |query ∩ row|, unique = hashes
+ * it owns, weighted = the sum of their abundances, and abund_values[abund_offsets[p], abund_offsets[p + 1]) their abundances in
+ * ascending hash order.  Per query: query_sizes = hashes <= cutoff, total_weighted = the sum of their abundances.
+ * workspace_bytes: for m queries of q_total hashes in all with n_picks picks (UINT64_MAX with an error set: 2^32 of either). */
+uint64_t smgpu_gather_rows_workspace_bytes(uint64_t m, uint64_t q_total, uint64_t n_picks);
+/* Everything in device memory.  d_qoffsets (m + 1) are positions in d_qhashes[0, q_total); d_qabunds is aligned with d_qhashes
+ * (NULL: every abundance is 1).  Outputs: d_owner (q_total; the owning rank, 0xffffffff for none), d_orig_common / d_unique /
+ * d_weighted (n_picks), d_abund_offsets (n_picks + 1), d_abund_values (room for q_total), d_query_sizes / d_total_weighted (m).
+ * grid: workgroups of the launches (0: the library's numbers).  Returns the number of owned hashes (= d_abund_offsets[n_picks]).
+ * Synchronises the stream.  UINT64_MAX with an error set: a refused argument (a null pointer, a workspace smaller than
+ * smgpu_gather_rows_workspace_bytes says, grid above 1048576, 2^32 queries, query hashes, rows or picks, a pick row >= n_rows,
+ * offsets that descend or leave their arrays), or no device. */
+uint64_t smgpu_gather_rows_raw(const uint64_t *d_qhashes, const uint64_t *d_qabunds, const uint64_t *d_qoffsets, uint64_t m, uint64_t q_total,
+                               const uint64_t *d_hashes, const uint64_t *d_offsets, uint64_t n_rows,
+                               const uint64_t *d_pick_offsets, const uint32_t *d_pick_rows, uint64_t n_picks,
+                               uint64_t cutoff, uint32_t grid,
+                               uint32_t *d_owner, uint32_t *d_orig_common, uint32_t *d_unique, uint64_t *d_weighted,
+                               uint64_t *d_abund_offsets, uint64_t *d_abund_values, uint64_t *d_query_sizes, uint64_t *d_total_weighted,
+                               void *d_workspace, uint64_t workspace_bytes, void *stream);
+/* smgpu_sketchset_gather_many, then the pass above on the same resident buffers; compatibility as for
+ * smgpu_sketchset_overlaps_many.  abunds: host array aligned with the queries' hashes (all of them, in row order), or NULL.  The
+ * pass is checked against the gather: a pick that owns another number of hashes than the gather reported is an error.
+ * smgpu_sketchset_gather_rows: one query through the one-query gather (smgpu_counter_new / smgpu_counter_gather on the resident
+ * set), abundances from the sketch when it tracks them.  The getters borrow from the handle: offsets (queries + 1) into the
+ * per-pick arrays rows / isect / orig_common / weighted; abund_offsets (picks + 1) into abund_values; query_sizes and
+ * total_weighted per query, row_sizes per row of the set, all at the common scaled; stats: out[0] ms of the gather (host),
+ * [1 .. 4) of the owner pass, the tally pass and the pair sort (device), [4] of the whole call (host). */
+typedef struct SmgpuGatherRows SmgpuGatherRows;
+SmgpuGatherRows *smgpu_sketchset_gather_rows_many(const SmgpuSketchSet *db, const SmgpuSketchSet *queries, const uint64_t *abunds,
+                                                  uint64_t threshold_hashes);
+SmgpuGatherRows *smgpu_sketchset_gather_rows(const SmgpuSketchSet *db, const SourmashKmerMinHash *query, uint64_t threshold_hashes);
+void            smgpu_gatherrows_free(SmgpuGatherRows *ptr);
+uint64_t        smgpu_gatherrows_queries(const SmgpuGatherRows *ptr);
+uint64_t        smgpu_gatherrows_n_rows(const SmgpuGatherRows *ptr);
+const uint64_t *smgpu_gatherrows_offsets(const SmgpuGatherRows *ptr);
+const uint32_t *smgpu_gatherrows_rows(const SmgpuGatherRows *ptr);
+const uint32_t *smgpu_gatherrows_isect(const SmgpuGatherRows *ptr);
+const uint32_t *smgpu_gatherrows_orig_common(const SmgpuGatherRows *ptr);
+const uint64_t *smgpu_gatherrows_weighted(const SmgpuGatherRows *ptr);
+const uint64_t *smgpu_gatherrows_abund_offsets(const SmgpuGatherRows *ptr);
+const uint64_t *smgpu_gatherrows_abund_values(const SmgpuGatherRows *ptr);
+const uint64_t *smgpu_gatherrows_query_sizes(const SmgpuGatherRows *ptr);
+const uint64_t *smgpu_gatherrows_row_sizes(const SmgpuGatherRows *ptr);
+const uint64_t *smgpu_gatherrows_total_weighted(const SmgpuGatherRows *ptr);
+uint64_t        smgpu_gatherrows_scaled(const SmgpuGatherRows *ptr);
+void            smgpu_gatherrows_stats(const SmgpuGatherRows *ptr, double *out5);
 SmgpuCounter *smgpu_counter_new(const SmgpuSketchSet *set, const SourmashKmerMinHash *query);
 void smgpu_counter_free(SmgpuCounter *ptr);
 void smgpu_counter_get(const SmgpuCounter *ptr, uint64_t *counts_out);

@@ -16,7 +16,7 @@ from .signature import (SourmashSignature, FrozenSourmashSignature, load_signatu
 from .hll import HLL  # noqa: E402
 from .nodegraph import Nodegraph  # noqa: E402
 from .kmers import KmerQuery, KmerMatches, find_kmers  # noqa: E402
-from .index import SketchSet, SketchSetWriter  # noqa: E402
+from .index import GatherStats, SketchSet, SketchSetWriter  # noqa: E402
 
 DEFAULT_SEED = get_minhash_default_seed()
 MAX_HASH = get_minhash_max_hash()
@@ -28,5 +28,5 @@ def gpu_available():
 
 
 __all__ = ["MinHash", "FrozenMinHash", "HLL", "Nodegraph", "SourmashSignature", "FrozenSourmashSignature", "hash_murmur",
-           "load_signatures_from_json", "load_one_signature_from_json", "save_signatures_to_json", "KmerQuery", "KmerMatches", "find_kmers", "SketchSet", "SketchSetWriter",
+           "load_signatures_from_json", "load_one_signature_from_json", "save_signatures_to_json", "KmerQuery", "KmerMatches", "find_kmers", "SketchSet", "GatherStats", "SketchSetWriter",
            "gpu_available", "DEFAULT_SEED", "MAX_HASH", "VERSION"]

@@ -34,7 +34,7 @@ _SCALARS = {
     "SourmashStr": SourmashStr,
 }
 _OPAQUE = {"SourmashKmerMinHash", "SourmashSignature", "SourmashHyperLogLog", "SourmashNodegraph", "SourmashComputeParameters", "SmgpuSketchSet", "SmgpuCounter", "SmgpuBitIndex",
-           "SmgpuGather", "SmgpuCollection", "SmgpuGatherXchg", "SmgpuKmerQuery", "SmgpuKmerMatches", "SmgpuSigWriter", "SmgpuManyHits", "SmgpuManyGather"}
+           "SmgpuGather", "SmgpuCollection", "SmgpuGatherXchg", "SmgpuKmerQuery", "SmgpuKmerMatches", "SmgpuSigWriter", "SmgpuManyHits", "SmgpuManyGather", "SmgpuGatherRows"}
 
 
 def _ctype(decl, is_arg=False):

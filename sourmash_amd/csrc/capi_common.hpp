@@ -131,6 +131,8 @@ struct SketchSet {
 // ---- helpers of the many-queries unit (capi_many.cpp) and the gather unit (capi_gather.cpp) that the gather-many unit uses too
 // throws the reference's mismatch error for two sets that cannot meet (many_core.hpp: many_compat_code)
 void check_sets_compatible(const SketchSet& db, const SketchSet& q);
+// the same for one query sketch against a set
+void check_sketch_compatible(const SketchSet& db, const KmerMinHash& mh);
 // the hits of the many-queries pass left on the device, ordered by (query, row); ms3: index build, passes, final sort
 struct ManyDeviceHits {
     AsyncBuf queries, rows, common;

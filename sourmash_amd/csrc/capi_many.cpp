@@ -26,14 +26,15 @@ void check_raw(const void* p, const char* what) {
     if (!p) throw err_internal(std::string("smgpu_many_overlap_raw: null pointer (") + what + ")");
 }
 
-}  // namespace
+// (a set keeps its ksize in residues; the reference compares the sketches' own, three times that for the amino acid alphabets)
+ManyParams params_of(const SketchSet& s) {
+    if (s.ksize == 0) throw err_internal("the set's sketches do not share one set of parameters");
+    return ManyParams{s.ksize * (s.hash_function == HF_DNA ? 1u : 3u), s.hash_function, s.seed, s.max_hash, s.num};
+}
 
 // the reference's order (check_compatible, minhash.rs:886-912): ksize, hash function, max_hash only when a side is num, seed
-void smg::check_sets_compatible(const SketchSet& db, const SketchSet& q) {
-    if (db.ksize == 0 || q.ksize == 0) throw err_internal("the set's sketches do not share one set of parameters");
-    // (a set keeps its ksize in residues; the reference compares the sketches' own, three times that for the amino acid alphabets)
-    auto params = [](const SketchSet& s) { return ManyParams{s.ksize * (s.hash_function == HF_DNA ? 1u : 3u), s.hash_function, s.seed, s.max_hash, s.num}; };
-    switch (many_compat_code(params(db), params(q))) {
+void check_params_compatible(const ManyParams& a, const ManyParams& b) {
+    switch (many_compat_code(a, b)) {
     case 0: return;
     case E_MISMATCH_KSIZES: throw err_mismatch_ksizes();
     case E_MISMATCH_DNA_PROT: throw err_mismatch_dnaprot();
@@ -41,6 +42,17 @@ void smg::check_sets_compatible(const SketchSet& db, const SketchSet& q) {
     case E_MISMATCH_SEED: throw err_mismatch_seed();
     default: throw Error(E_MISMATCH_NUM, "a search of many queries requires scaled signatures");
     }
+}
+
+}  // namespace
+
+void smg::check_sets_compatible(const SketchSet& db, const SketchSet& q) {
+    const ManyParams a = params_of(db), b = params_of(q);
+    check_params_compatible(a, b);
+}
+
+void smg::check_sketch_compatible(const SketchSet& db, const KmerMinHash& mh) {
+    check_params_compatible(params_of(db), ManyParams{mh.ksize, mh.hash_function, mh.seed, mh.max_hash, mh.num});
 }
 
 // Room for the hits: a few per query and row is what a thresholded search leaves; every pair at most.  A result that does not fit

@@ -243,6 +243,32 @@ hipError_t gather_many_plan(const uint64_t* d_qhashes, const uint64_t* d_qoffset
                             const uint32_t* d_hit_common, uint64_t n_hits, uint64_t cutoff, uint32_t max_query_hashes, uint32_t max_candidates,
                             uint32_t* d_qlo, uint32_t* d_qn, uint32_t* d_status, uint64_t* d_sums, hipStream_t stream);
 
+// ---- gather_rows.hip (from the picks of gather to the integers of its result rows; gather_rows_core.hpp holds its rules) ----------
+// Both CSRs on the device; d_qoffsets (m + 1) are positions in d_qhashes[0, q_total), d_qabunds (may be null: every abundance is 1)
+// is aligned with d_qhashes.  The picks of query q are d_pick_rows[d_pick_offsets[q], d_pick_offsets[q + 1]) in rank order.
+// Outputs: d_owner (q_total: the rank that owns the hash, or GM_NONE), d_orig_common / d_unique / d_weighted (n_picks),
+// d_abund_offsets (n_picks + 1), d_abund_values (room for q_total), d_query_sizes / d_total_weighted (m).
+struct GatherRowsArgs {
+    const uint64_t *d_qhashes, *d_qabunds, *d_qoffsets;
+    uint64_t m, q_total;
+    const uint64_t *d_hashes, *d_offsets;
+    uint64_t n_rows;
+    const uint64_t* d_pick_offsets;
+    const uint32_t* d_pick_rows;
+    uint64_t n_picks;
+    uint64_t cutoff;
+    uint32_t grid;
+    uint32_t *d_owner, *d_orig_common, *d_unique;
+    uint64_t *d_weighted, *d_abund_offsets, *d_abund_values, *d_query_sizes, *d_total_weighted;
+    void* d_workspace;
+    uint64_t workspace_bytes;
+};
+size_t gather_rows_workspace_bytes(uint64_t m, uint64_t q_total, uint64_t n_picks);
+// Synchronises the stream.  *n_owned = query hashes that a pick owns (the entries of d_abund_values); *trouble: 0, or the bits of
+// gather_rows_core.hpp (GR_BAD_*) -- then the outputs hold nothing; ms3 (may be null): milliseconds of the owner pass, the tally
+// pass and the pair sort.  hipErrorInvalidValue: an argument smgpu_gather_rows_raw refuses.
+hipError_t gather_rows_run(const GatherRowsArgs& args, uint64_t* n_owned, uint32_t* trouble, float* ms3, hipStream_t stream);
+
 // ---- synth.hip --------------------------------------------------------------------
 hipError_t synth_dna_launch(uint8_t* d_out, uint64_t start, uint64_t n, uint64_t seed, uint64_t record_len,
                             hipStream_t stream);

@@ -26,7 +26,7 @@ from .search import calc_threshold_from_bp, make_containment_query, make_jaccard
 from .signature import SourmashSignature, load_signatures_from_json, save_signatures_to_json
 from .utils import RustObject, decode_str, objptr_array, rustcall
 
-__all__ = ["IndexSearchResult", "Collection", "SketchSet", "many_need", "score_hits", "rank_scored", "SketchSetWriter", "select_signature", "Index", "LinearIndex", "CounterGather"]
+__all__ = ["IndexSearchResult", "Collection", "SketchSet", "GatherStats", "many_need", "score_hits", "rank_scored", "SketchSetWriter", "select_signature", "Index", "LinearIndex", "CounterGather"]
 
 IndexSearchResult = namedtuple("Result", "score, signature, location")
 
@@ -473,6 +473,47 @@ class SketchSet(RustObject):
         return self._many_gather(queries, threshold_bp).per_query()
 
 
+    # ---- the result rows of gather (csrc/gather_rows.hip) ------------------------------------------------------------------------
+    def gather_stats_many(self, queries, threshold_bp=0, abunds=None):
+        """gather_many, and for every pick the integers its result row is made of -> GatherStats.  One more pass over the resident
+        sets: per pick |query ∩ row|, the query hashes it covered first (the rank's "remaining query ∩ match") and the sum of
+        their abundances, and those abundances in hash order.  abunds: a flat uint64 array aligned with the queries' hashes (row
+        after row, ascending within a row), or one array per query; None: every abundance is 1 and rows() gives the columns of
+        an ignore-abundance gather."""
+        if not isinstance(queries, SketchSet):
+            raise TypeError("the queries of a many-query search are a SketchSet")
+        common_scaled = max(queries.params[3], self.params[3])
+        thr = math.ceil(float(threshold_bp) / common_scaled) if threshold_bp and common_scaled else 0
+        flat = None
+        if abunds is not None:
+            if isinstance(abunds, (list, tuple)):
+                if len(abunds) != len(queries):
+                    raise ValueError("one abundance array per query is needed")
+                sizes = queries.sizes
+                if any(len(a) != int(n) for a, n in zip(abunds, sizes)):
+                    raise ValueError("a query's abundances must be as many as its hashes")
+                abunds = np.concatenate([np.asarray(a, dtype=np.uint64) for a in abunds]) if len(abunds) else np.zeros(0, dtype=np.uint64)
+            flat = np.ascontiguousarray(abunds, dtype=np.uint64)
+            if flat.shape != (queries.total_hashes,):
+                raise ValueError("the abundances must be as many as the queries' hashes")
+        ptr = rustcall(lib.smgpu_sketchset_gather_rows_many, self._get_objptr(), queries._get_objptr(),
+                       flat.ctypes.data_as(C.c_void_p) if flat is not None and len(flat) else None, int(thr))
+        return GatherStats._from_handle(ptr, self, queries=queries, with_abundance=abunds is not None, query_scaled=queries.params[3])
+
+    def gather_stats(self, query_mh, threshold_bp=0, ignore_abundance=False):
+        """gather(query_mh), and the integers of its result rows -> GatherStats of one query: the one-query gather, then the same
+        pass.  The abundances are the sketch's own when it tracks them and ignore_abundance is not set."""
+        scaled = query_mh.scaled
+        if not scaled:
+            raise ValueError("gather requires scaled signatures")
+        with_abundance = bool(query_mh.track_abundance and not ignore_abundance)
+        common_scaled = max(scaled, self.params[3])
+        thr = math.ceil(float(threshold_bp) / common_scaled) if threshold_bp else 0
+        mh = query_mh if with_abundance else query_mh.flatten()
+        ptr = rustcall(lib.smgpu_sketchset_gather_rows, self._get_objptr(), mh._get_objptr(), int(thr))
+        return GatherStats._from_handle(ptr, self, queries=None, with_abundance=with_abundance, query_scaled=scaled)
+
+
 class _ManyGather(RustObject):
     "the picks of a many-query gather on the host (smgpu_manygather_*): offsets per query into rows / isect, in rank order"
     __dealloc_func__ = lib.smgpu_manygather_free
@@ -504,6 +545,138 @@ class _ManyGather(RustObject):
         rows = self._array(lib.smgpu_manygather_rows, total, C.c_uint32, np.uint32).tolist()
         isect = self._array(lib.smgpu_manygather_isect, total, C.c_uint32, np.uint32).tolist()
         return [list(zip(rows[int(off[q]):int(off[q + 1])], isect[int(off[q]):int(off[q + 1])])) for q in range(self._n_queries)]
+
+
+class GatherStats:
+    """The integers behind the rows of `sourmash gather` for the picks of one or many queries, as numpy arrays (what
+    smgpu_sketchset_gather_rows_many / smgpu_sketchset_gather_rows leave on the host), and the rows themselves.
+
+    offsets (queries + 1) cuts the per-pick arrays: pick_rows, isect (= the hashes the pick owns), orig_common, weighted;
+    abund_offsets (picks + 1) cuts abund_values; query_sizes and total_weighted are per query, row_sizes per row of the set, all at
+    `scaled`, the scaled the two sets meet at.  with_abundance: the queries' abundances were given."""
+    FIELDS = ("offsets", "pick_rows", "isect", "orig_common", "weighted", "abund_offsets", "abund_values", "query_sizes", "row_sizes", "total_weighted")
+
+    def __init__(self, *, offsets, pick_rows, isect, orig_common, weighted, abund_offsets, abund_values, query_sizes, row_sizes, total_weighted,
+                 scaled, with_abundance, ksize=None, moltype=None, query_scaled=None, match_info=None, query_info=None, stats=None):
+        self.offsets, self.abund_offsets = np.asarray(offsets, dtype=np.uint64), np.asarray(abund_offsets, dtype=np.uint64)
+        self.pick_rows, self.isect, self.orig_common = (np.asarray(a, dtype=np.uint32) for a in (pick_rows, isect, orig_common))
+        self.weighted, self.abund_values = np.asarray(weighted, dtype=np.uint64), np.asarray(abund_values, dtype=np.uint64)
+        self.query_sizes, self.row_sizes, self.total_weighted = (np.asarray(a, dtype=np.uint64) for a in (query_sizes, row_sizes, total_weighted))
+        self.scaled, self.with_abundance = int(scaled), bool(with_abundance)
+        self.query_scaled = int(query_scaled) if query_scaled else int(scaled)
+        self.ksize, self.moltype = ksize, moltype
+        self.match_info, self.query_info = match_info, query_info
+        self.stats = stats or {}
+        self._db = self._queries = None
+
+    @classmethod
+    def _from_handle(cls, ptr, db, *, queries, with_abundance, query_scaled):
+        try:
+            m, n = lib.smgpu_gatherrows_queries(ptr), lib.smgpu_gatherrows_n_rows(ptr)
+
+            def array(func, count, ctype, dtype):
+                if not count:
+                    return np.zeros(0, dtype=dtype)
+                return np.ctypeslib.as_array(C.cast(func(ptr), C.POINTER(ctype)), shape=(count,)).copy()
+            offsets = array(lib.smgpu_gatherrows_offsets, m + 1, C.c_uint64, np.uint64)
+            picks = int(offsets[-1])
+            abund_offsets = array(lib.smgpu_gatherrows_abund_offsets, picks + 1, C.c_uint64, np.uint64)
+            stats = (C.c_double * 5)()
+            lib.smgpu_gatherrows_stats(ptr, stats)
+            ksize, moltype = db.params[0], db.params[1]
+            out = cls(offsets=offsets, pick_rows=array(lib.smgpu_gatherrows_rows, picks, C.c_uint32, np.uint32),
+                      isect=array(lib.smgpu_gatherrows_isect, picks, C.c_uint32, np.uint32),
+                      orig_common=array(lib.smgpu_gatherrows_orig_common, picks, C.c_uint32, np.uint32),
+                      weighted=array(lib.smgpu_gatherrows_weighted, picks, C.c_uint64, np.uint64), abund_offsets=abund_offsets,
+                      abund_values=array(lib.smgpu_gatherrows_abund_values, int(abund_offsets[-1]), C.c_uint64, np.uint64),
+                      query_sizes=array(lib.smgpu_gatherrows_query_sizes, m, C.c_uint64, np.uint64),
+                      row_sizes=array(lib.smgpu_gatherrows_row_sizes, n, C.c_uint64, np.uint64),
+                      total_weighted=array(lib.smgpu_gatherrows_total_weighted, m, C.c_uint64, np.uint64),
+                      scaled=lib.smgpu_gatherrows_scaled(ptr), with_abundance=with_abundance, ksize=ksize, moltype=moltype, query_scaled=query_scaled,
+                      stats=dict(zip(("gather_ms", "owner_ms", "tally_ms", "sort_ms", "call_ms"), stats)))
+        finally:
+            lib.smgpu_gatherrows_free(ptr)
+        out._db, out._queries = db, queries
+        return out
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    def per_query(self):
+        "[(row, |intersect|)] in rank order for query 0, 1, ..: what gather_many returns"
+        off, rows, isect = self.offsets.tolist(), self.pick_rows.tolist(), self.isect.tolist()
+        return [list(zip(rows[off[q]:off[q + 1]], isect[off[q]:off[q + 1]])) for q in range(len(self))]
+
+    def _set_info(self):
+        "name / filename / md5 of the set's rows and of the query set's rows, from the manifests and md5sums"
+        if self.match_info is None and self._db is not None:
+            used = sorted(set(self.pick_rows.tolist()))
+            if used and getattr(self._db, "_md5_of_rows", None) is None:
+                self._db._md5_of_rows = self._db.md5sums()              # (the rows of a set do not change: kept for the next call)
+            md5, man = (self._db._md5_of_rows, self._db.manifest) if used else ([], [])
+            self.match_info = {r: dict(name=man[r]["name"], filename=man[r]["filename"], md5=md5[r]) for r in used}
+        if self.query_info is None and self._queries is not None:
+            md5, man = self._queries.md5sums(), self._queries.manifest
+            self.query_info = [dict(query_name=man[q]["name"], query_filename=man[q]["filename"], query_md5=md5[q][:8]) for q in range(len(self))]
+
+    def rows_of(self, q, with_abundance=None):
+        """The rows of query q: a list of dicts with the columns of GatherResult.gather_write_cols, == to the gatherresultdict of the
+        reference's loop round by round.  with_abundance: whether this query's abundances count (None: as the call was made).  Integer and ratio columns are the expressions of GatherResult.build_gather_result on the
+        device's integers, the abundance statistics np.mean / np.median / np.std of the pick's abundances in hash order, the ANI
+        columns distance_utils.containment_to_distance on the containments of (original query, match), None -- not written -- when
+        either sketch is too small for its size to be trusted (MinHash.size_is_accurate)."""
+        from .distance_utils import containment_to_distance, set_size_exact_prob
+        from .minhash import MinHash
+        self._set_info()
+        if with_abundance is None:
+            with_abundance = self.with_abundance
+        S, off = self.scaled, self.offsets
+        accurate = {}
+
+        def size_is_accurate(n):
+            "MinHash.size_is_accurate of a sketch of n hashes at the common scaled"
+            if n not in accurate:
+                accurate[n] = set_size_exact_prob(n * S, S, relative_error=0.20) >= 0.95
+            return accurate[n]
+        q_len, total_w = int(self.query_sizes[q]), int(self.total_weighted[q])
+        qinfo = dict(self.query_info[q]) if self.query_info is not None else {}
+        ksize, moltype = qinfo.pop("ksize", self.ksize), qinfo.pop("moltype", self.moltype)
+        remaining, sum_found, out = q_len, 0, []
+        for rank, p in enumerate(range(int(off[q]), int(off[q + 1]))):
+            row, oc, u = int(self.pick_rows[p]), int(self.orig_common[p]), int(self.isect[p])
+            r_len, w = int(self.row_sizes[row]), int(self.weighted[p])
+            sum_found += w
+            d = dict(self.match_info[row]) if self.match_info is not None else {}
+            d.update(qinfo)
+            d.update(intersect_bp=oc * S, f_orig_query=oc / q_len, f_match=MinHash._debias(u, r_len, S) if r_len else 0.0,
+                     f_unique_to_query=u / q_len, f_match_orig=MinHash._debias(oc, r_len, S) if r_len else 0.0, unique_intersect_bp=u * S,
+                     gather_result_rank=rank, remaining_bp=remaining * S - u * S, query_bp=q_len * self.query_scaled, ksize=ksize, moltype=moltype,
+                     scaled=S, query_n_hashes=q_len, sum_weighted_found=sum_found, total_weighted_hashes=total_w)
+            if with_abundance:
+                values = self.abund_values[int(self.abund_offsets[p]):int(self.abund_offsets[p + 1])].tolist()
+                d.update(average_abund=float(np.mean(values)), median_abund=float(np.median(values)), std_abund=float(np.std(values)),
+                         query_abundance=True, n_unique_weighted_found=w, f_unique_weighted=w / total_w)
+            else:
+                d.update(f_unique_weighted=d["f_unique_to_query"], query_abundance=False)
+            # the ANI columns of (original query, match): FracMinHashComparison.estimate_all_containment_ani on these numbers
+            q_ani = containment_to_distance(MinHash._debias(oc, q_len, S) if q_len else 0.0, ksize, S, n_unique_kmers=q_len * S,
+                                            confidence=0.95, estimate_ci=False, prob_threshold=1e-3)
+            m_ani = containment_to_distance(MinHash._debias(oc, r_len, S) if r_len else 0.0, ksize, S, n_unique_kmers=r_len * S,
+                                            confidence=0.95, estimate_ci=False, prob_threshold=1e-3)
+            if not size_is_accurate(q_len) or not size_is_accurate(r_len):
+                q_ani.size_is_inaccurate = m_ani.size_is_inaccurate = True      # (MinHash.containment_ani: no ANI from such a pair)
+            pair = None if None in (q_ani.ani, m_ani.ani) else (q_ani.ani, m_ani.ani)
+            d.update(query_containment_ani=q_ani.ani, match_containment_ani=m_ani.ani,
+                     average_containment_ani=None if pair is None else (pair[0] + pair[1]) / 2,
+                     max_containment_ani=None if pair is None else max(pair),
+                     potential_false_negative=bool(q_ani.p_exceeds_threshold or m_ani.p_exceeds_threshold))
+            out.append({k: v for k, v in d.items() if v is not None})
+            remaining -= u
+        return out
+
+    def rows(self):
+        "[self.rows_of(q)] for query 0, 1, .."
+        return [self.rows_of(q) for q in range(len(self))]
 
 
 class _ManyHits(RustObject):
@@ -939,19 +1112,16 @@ class LinearIndex(Index):
             self._packed = (key,) + Index._subject_set(self, query_scaled, items)
         return self._packed[1], self._packed[2]
 
-    def gather_many(self, queries, threshold_bp=0):
-        """[self.counter_gather(q, threshold_bp).gather_all(threshold_bp) for q in queries]: per query [(md5, |intersect|)] in rank
-        order.  One native call (SketchSet.gather_many over the subjects' device CSR) when the queries are flat, scaled and of one
-        scaled and every subject is at that scaled once flattened and downsampled; otherwise that loop itself.  What the loop
-        raises -- an empty index, an empty query, an unattainable threshold_bp -- is raised for the first offending query, before
-        any device work."""
-        queries = list(queries)
-
-        def loop():
-            return [self.counter_gather(q, threshold_bp).gather_all(threshold_bp) for q in queries]
+    def _native_gather_inputs(self, queries, threshold_bp, abundance_queries):
+        """What one native many-query gather works on -> (items of the walk, their SketchSet at the queries' scaled, the queries'
+        sketches), or None when the per-query loop has to be taken: the queries are not all scaled and of one scaled (and flat,
+        unless abundance_queries), or a query or subject differs in its parameters or is coarser.  What the loop raises on the host
+        -- an empty index, an empty query, an unattainable threshold_bp, a subject that cannot be read -- is raised here for the
+        first offending query, before any device work."""
         mhs = [q.minhash for q in queries]
-        if not queries or not all(mh.scaled and not mh.track_abundance for mh in mhs) or any(mh.scaled != mhs[0].scaled for mh in mhs):
-            return loop()
+        if not queries or not all(mh.scaled and (abundance_queries or not mh.track_abundance) for mh in mhs) \
+                or any(mh.scaled != mhs[0].scaled for mh in mhs):
+            return None
         scaled = mhs[0].scaled
         items, pending = self._walk()
 
@@ -959,16 +1129,33 @@ class LinearIndex(Index):
             "the sketch can stand in one set with the first query: the same parameters, and not coarser"
             return mh.scaled and mh.scaled <= scaled and (mh.ksize, mh.moltype, mh.seed) == (mhs[0].ksize, mhs[0].moltype, mhs[0].seed)
         if not all(meets(mh) for mh in mhs) or not all(meets(mh) for _, _, mh in items):
-            return loop()                                           # (whatever a mismatch raises, the loop raises it)
+            return None                                             # (whatever a mismatch raises, the loop raises it)
         for i, (query, mh) in enumerate(zip(queries, mhs)):
             # what counter_gather checks on the host, in its order (the counter takes any scaled query): the index, then the
-            # prefetch's search object
+            # prefetch's search object, on the flattened query it works with
             if not self:
                 raise ValueError("no signatures to search")
+            if mh.track_abundance:
+                mh = mh.flatten()
+                query = query.to_mutable()
+                query.minhash = mh
             make_containment_query(mh, threshold_bp, best_only=False).check_is_compatible(query)
             if i == 0 and pending is not None:
                 raise pending                                       # (the walk of the first query's prefetch ends on it)
         sset, _ = self._subject_set(scaled, items)
+        return items, sset, mhs
+
+    def gather_many(self, queries, threshold_bp=0):
+        """[self.counter_gather(q, threshold_bp).gather_all(threshold_bp) for q in queries]: per query [(md5, |intersect|)] in rank
+        order.  One native call (SketchSet.gather_many over the subjects' device CSR) when the queries are flat, scaled and of one
+        scaled and every subject is at that scaled once flattened and downsampled; otherwise that loop itself.  What the loop
+        raises -- an empty index, an empty query, an unattainable threshold_bp -- is raised for the first offending query, before
+        any device work."""
+        queries = list(queries)
+        native = self._native_gather_inputs(queries, threshold_bp, abundance_queries=False)
+        if native is None:
+            return [self.counter_gather(q, threshold_bp).gather_all(threshold_bp) for q in queries]
+        items, sset, mhs = native
         # The prefetch inside counter_gather keeps a subject by a float containment test, the device by the integer count
         # ceil(threshold_bp / scaled).  Correctly rounded division by the same positive len(query) is monotone, so the two can only
         # disagree on a subject whose count is below the integer threshold: never picked, and it changes no other counter.  Subjects
@@ -982,6 +1169,46 @@ class LinearIndex(Index):
                     md5[row] = items[row][0].md5sum()
             out.append([(md5[row], n) for row, n in rows])
         return out
+
+    def gather_results_many(self, queries, threshold_bp=0, *, ignore_abundance=False):
+        """[[r.gatherresultdict for r in GatherDatabases(q, [self.counter_gather(q, threshold_bp)], threshold_bp=threshold_bp,
+        ignore_abundance=ignore_abundance)] for q in queries]: per query the rows of `sourmash gather`, every column.  One native
+        call (SketchSet.gather_stats_many over the subjects' device CSR) under the conditions of gather_many -- scaled queries of
+        one scaled and one set of parameters, every subject at that scaled once flattened and downsampled -- and queries with
+        abundances are taken there too; otherwise that loop itself, with whatever it raises, in its order.  noident_mh / ident_mh
+        and estimate_ani_ci=True are not offered here: they stay with GatherDatabases."""
+        from .search import GatherDatabases
+        queries = list(queries)
+        native = self._native_gather_inputs(queries, threshold_bp, abundance_queries=True)
+        if native is None:
+            return [[r.gatherresultdict for r in GatherDatabases(q, [self.counter_gather(q, threshold_bp)], threshold_bp=threshold_bp,
+                                                                 ignore_abundance=ignore_abundance)] for q in queries]
+        items, sset, mhs = native
+        with_abundance = [bool(mh.track_abundance and not ignore_abundance) for mh in mhs]
+        abunds = None
+        if any(with_abundance):
+            # MinHash.hashes is ascending, as the set's rows are; a query whose abundances do not count carries ones
+            abunds = [np.fromiter(mh.hashes.values(), dtype=np.uint64, count=len(mh)) if w else np.ones(len(mh), dtype=np.uint64)
+                      for mh, w in zip(mhs, with_abundance)]
+        stats = sset.gather_stats_many(SketchSet([mh.flatten() for mh in mhs]), threshold_bp, abunds=abunds)
+        # Subjects with the same md5 are one entry of the loop's counter: it keeps the first one's place and the LAST one's
+        # signature and location (CounterGather._register), so a picked row -- the first of its kind -- reports the last subject
+        # of the walk with its md5.  The same md5 means the same hashes, hence the same size at the common scaled: only rows of
+        # a picked row's size are asked for their md5.
+        md5 = {}
+
+        def md5_of(row):
+            if row not in md5:
+                md5[row] = items[row][0].md5sum()
+            return md5[row]
+        stats.match_info = {}
+        for row in sorted(set(stats.pick_rows.tolist())):
+            same_size = np.flatnonzero(stats.row_sizes == stats.row_sizes[row]).tolist()
+            ss, loc, _ = items[max(j for j in same_size if md5_of(j) == md5_of(row))]
+            stats.match_info[row] = dict(name=ss.name, filename=loc if loc is not None else ss.filename, md5=md5_of(row))
+        stats.query_info = [dict(query_name=q.name, query_filename=q.filename, query_md5=q.md5sum()[:8], ksize=mh.ksize, moltype=mh.moltype)
+                            for q, mh in zip(queries, mhs)]
+        return [stats.rows_of(q, with_abundance=w) for q, w in enumerate(with_abundance)]
 
 
 class CounterGather:
