@@ -943,6 +943,11 @@ bool smgpu_gather_launch_shared(SmgpuGather *ptr, SmgpuGatherXchg *xchg, uint32_
 /* Test support: `n_wg` workgroups that keep `lds_bytes` of LDS each and spin for `micros` microseconds on `stream` -- "somebody
  * else's kernel holds CUs of this device" (the resident gather loop must step aside for the two-kernel rounds, not fail). */
 void smgpu_debug_hold_cus(uint32_t n_wg, uint32_t lds_bytes, uint64_t micros, void *stream);
+/* Test support: d_pos_out[i] = position of d_probes[i] in the sorted distinct query d_query[0 .. nq) (nq >= 1), or 0xffffffff when it
+ * is not there, through the query index of the overlap and gather passes.  form 0: the table lookup, 1: the bucket-record lookup,
+ * 2: the record lookup in its two-step form (load, then match).  Stream-ordered; scratch comes from the arena. */
+void smgpu_debug_qindex_find(const uint64_t *d_query, uint64_t nq, const uint64_t *d_probes, uint64_t n, int32_t form,
+                             uint32_t *d_pos_out, void *stream);
 uint64_t smgpu_gather_longest_row(const SmgpuGather *ptr);   /* hashes in the shard's longest row: stride >= 3 + the longest row of any shard */
 void smgpu_gather_topk_export_raw(SmgpuGather *ptr, uint64_t *d_records, uint32_t k, uint64_t stride, void *stream);
 void smgpu_gather_cands_load_raw(SmgpuGather *ptr, const uint64_t *d_records, uint32_t n_records, uint64_t stride,

@@ -464,6 +464,10 @@ bool smgpu_gather_launch_shared(SmgpuGather* p, SmgpuGatherXchg* xp, uint32_t ra
 void smgpu_debug_hold_cus(uint32_t n_wg, uint32_t lds_bytes, uint64_t micros, void* stream) {
     landing_void([&] { hip_check(debug_hold_cus(n_wg, lds_bytes, micros, (hipStream_t)stream), "hold CUs"); });
 }
+void smgpu_debug_qindex_find(const uint64_t* d_query, uint64_t nq, const uint64_t* d_probes, uint64_t n, int32_t form,
+                             uint32_t* d_pos_out, void* stream) {
+    landing_void([&] { hip_check(debug_qindex_find(d_query, nq, d_probes, n, form, d_pos_out, (hipStream_t)stream), "query index probe"); });
+}
 uint64_t smgpu_gather_longest_row(const SmgpuGather* p) { return reinterpret_cast<const GatherRaw*>(p)->g.longest_row; }
 void smgpu_gather_topk_export_raw(SmgpuGather* p, uint64_t* d_records, uint32_t k, uint64_t stride, void* stream) {
     landing_void([&] {

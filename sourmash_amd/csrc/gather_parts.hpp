@@ -22,7 +22,7 @@ namespace smg {
 constexpr int BR_SUB = 256;
 constexpr int BR_SUB_BITS = 8;
 
-// gather.hip: T[b] = first position of the sorted query with Q >= b << shift, b = 0 .. buckets (qindex.hpp: qindex_geometry)
+// gather.hip: T[b] = first position of the sorted query with Q >= b << shift, b = 0 .. buckets (qindex_core.hpp: qindex_geometry)
 hipError_t qtable_launch(const uint64_t* Q, uint64_t nq, uint32_t shift, uint32_t buckets, uint32_t* table, hipStream_t stream);
 
 // overlap.hip: the builder's pass 1 + 2a through the lean streaming kernel's staging form

@@ -26,6 +26,10 @@ hipError_t select_flagged(const uint64_t* in, const uint8_t* flags, uint64_t n, 
 // op 0: overlap[d] = |Q ∩ D_d| ; op 1: overlap[d] -= |Q ∩ D_d| (saturating, rows at 0 skipped)
 hipError_t overlap_vector_launch(const uint64_t* Q, uint64_t nq, const uint64_t* hashes, const uint64_t* offsets,
                                  uint64_t ndb, unsigned long long* overlap, int op, hipStream_t stream);
+// test support: pos_out[i] = position of probes[i] in the sorted query Q (nq >= 1), or 0xffffffff, through the index that pass
+// builds (qindex.hpp).  form 0: table lookup, 1: bucket records, 2: the split record form with its callers' clamp-and-discard rule
+hipError_t debug_qindex_find(const uint64_t* Q, uint64_t nq, const uint64_t* probes, uint64_t n, int form, uint32_t* pos_out,
+                             hipStream_t stream);
 // CSR row gather: row i of the destination = row rows[i] of the source (dst_off = prefix sums of the row lengths)
 hipError_t copy_rows_launch(const uint64_t* src, const uint64_t* src_off, const uint64_t* rows, uint64_t n_rows,
                             const uint64_t* dst_off, uint64_t* dst, hipStream_t stream);

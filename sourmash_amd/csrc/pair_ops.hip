@@ -271,6 +271,57 @@ hipError_t overlap_vector_launch(const uint64_t* Q, uint64_t nq, const uint64_t*
     return e;
 }
 
+// ---- test support: the position of every probe in Q through the index, as the passes above and gather's see it -------------------
+__global__ __launch_bounds__(256) void qindex_record_kernel(const uint8_t* scratch, QRec* __restrict__ rec) {
+    const QIndexHeader* h = reinterpret_cast<const QIndexHeader*>(scratch);
+    qindex_fill_record(h->qi.Q, h->qi.T, h->buckets, rec, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// form 0: q_find's table form; 1: q_find with bucket records; 2: q_rec_load / q_rec_match with their callers' rule (the record of
+// min(x, qmax) is loaded, the match runs with x, lanes with x > qmax are discarded)
+__global__ __launch_bounds__(256) void qindex_probe_kernel(const QIndexHeader* __restrict__ hdr, const QRec* __restrict__ rec,
+                                                           const uint64_t* __restrict__ probes, uint64_t n, int form,
+                                                           uint32_t* __restrict__ pos_out) {
+    QIndex qi = hdr->qi;
+    if (form != 0) qi.rec = rec;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t x = probes[i];
+        uint32_t j;
+        if (form == 2) {
+            const QRecVal v = q_rec_load(qi, x <= qi.qmax ? x : qi.qmax);
+            j = q_rec_match(qi, x, v);
+            if (x > qi.qmax) j = NONE32;
+        } else {
+            j = q_find(qi, x);
+        }
+        pos_out[i] = j;
+    }
+}
+
+hipError_t debug_qindex_find(const uint64_t* Q, uint64_t nq, const uint64_t* probes, uint64_t n, int form, uint32_t* pos_out,
+                             hipStream_t stream) {
+    if (nq == 0 || nq >= NONE32 || form < 0 || form > 2) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    // scratch: header, padded query, table of at most 2 * nq + 2 entries (as overlap_vector_launch), then as many records
+    const size_t rec_at = (QIH_BYTES + (nq + 4) * 8 + (2 * nq + 4) * 4 + 31) / 32 * 32;
+    const size_t bytes = rec_at + (2 * nq + 2) * sizeof(QRec);
+    uint8_t* scratch = nullptr;
+    hipError_t e = arena_alloc((void**)&scratch, bytes, stream);
+    if (e != hipSuccess) return e;
+    QRec* rec = reinterpret_cast<QRec*>(scratch + rec_at);
+    const uint64_t copy_blocks = (nq + 4 + 255) / 256;
+    const unsigned table_blocks = (unsigned)((2 * nq + 2 + 255) / 256);
+    hipLaunchKernelGGL(qindex_setup_kernel, dim3((unsigned)(copy_blocks < 1024 ? copy_blocks : 1024)), dim3(256), 0, stream, Q,
+                       nq, scratch);
+    hipLaunchKernelGGL(qindex_table_kernel, dim3(table_blocks), dim3(256), 0, stream, scratch);
+    if (form != 0) hipLaunchKernelGGL(qindex_record_kernel, dim3(table_blocks), dim3(256), 0, stream, scratch, rec);
+    hipLaunchKernelGGL(qindex_probe_kernel, dim3(grid_for(n, 256, 2048)), dim3(256), 0, stream,
+                       reinterpret_cast<const QIndexHeader*>(scratch), rec, probes, n, form, pos_out);
+    e = hipGetLastError();
+    arena_free(scratch, stream);
+    return e;
+}
+
 // one workgroup per destination row: dst[dst_off[i] ..) = src[src_off[rows[i]] ..), 8-byte coalesced copies
 __global__ __launch_bounds__(256) void copy_rows_kernel(const uint64_t* __restrict__ src, const uint64_t* __restrict__ src_off,
                                                         const uint64_t* __restrict__ rows, uint64_t n_rows,
