@@ -1013,6 +1013,47 @@ double smgpu_nodegraph_containment(const SourmashNodegraph *ptr, const SourmashN
  * min(n, cap) into out; returns n. */
 uintptr_t smgpu_nodegraph_table_sizes(uintptr_t starting_size, uintptr_t n_tables, uint64_t *out, uintptr_t cap);
 
+/* ---- set algebra on resident collections: merge by group, intersect, subtract, downsample (csrc/setops.hip, csrc/setops_core.hpp) ----
+ * Flat sketches only, as `sig merge --flatten`, `sig intersect` and `sig subtract` work.  Every set-level entry returns a NEW set
+ * (freed with smgpu_sketchset_free) with the receiver's parameters, host offsets and manifest rows; the receiver is unchanged.
+ * geometry: lanes of a workgroup, the partner hashes the row-wise filter stages in LDS, and the row length above which the filter
+ * splits a row over workgroups.  key_form: the pair form of the merge for a set of `max_hash` (0: num) merged into n_groups rows --
+ * the bits of a hash and of a group number, and whether both share one 64-bit key.  Host only. */
+void smgpu_setops_geometry(uint32_t *workgroup, uint32_t *lds_partner, uint64_t *split);
+void smgpu_setops_key_form(uint64_t max_hash, uint64_t n_groups, uint32_t *hbits, uint32_t *gbits, uint32_t *packed);
+/* The CSR in device memory (d_offsets: n + 1 positions in d_hashes spanning `total` hashes; rows ascending) merged into n_groups
+ * rows: row g = the hashes that at least need-of-g rows of group g hold.  d_groups: one group number < n_groups per row (NULL:
+ * all rows in group 0); d_need: one count per group (NULL: 1, the union), need_all != 0: the group's row count (the
+ * intersection).  max_hash: of the sketches (0 for num sketches); num != 0: rows are cut to their num smallest hashes (union
+ * only).  d_out_hashes: room for `total`; d_out_offsets: n_groups + 1; d_result: 2 x uint64_t ([0] the result's hashes, [1]
+ * distinct (group, hash) pairs).  Returns the result's hashes.  Synchronises the stream.  UINT64_MAX with an error set: a refused
+ * argument, or no device. */
+uint64_t smgpu_setops_merge_workspace_bytes(uint64_t total, uint64_t n_groups);
+uint64_t smgpu_setops_merge_raw(const uint64_t *d_hashes, const uint64_t *d_offsets, uint64_t n, uint64_t total, const uint32_t *d_groups,
+                                uint64_t n_groups, const uint32_t *d_need, uint32_t need_all, uint64_t max_hash, uint64_t num,
+                                uint64_t *d_out_hashes, uint64_t *d_out_offsets, uint64_t *d_result, void *d_workspace,
+                                uint64_t workspace_bytes, void *stream);
+/* Row r of the result = the hashes of row r that are (keep_present != 0: intersect) or are not (0: subtract) in the other
+ * sketch.  d_other_offsets NULL: one sketch d_other_hashes[0, other_len), ascending, against every row; otherwise a second CSR of
+ * n rows, row r against row r (other_len is not read; the workspace takes other_len = 0).  grid: workgroups (0: the library's
+ * number).  d_out_offsets: n + 1, always written; d_out_hashes: `capacity` hashes -- when the result is longer nothing is written
+ * to it and the caller runs again with room.  d_result: 2 x uint64_t.  Returns the result's hashes.  Synchronises the stream. */
+uint64_t smgpu_setops_filter_workspace_bytes(uint64_t n, uint64_t total, uint64_t other_len);
+uint64_t smgpu_setops_filter_raw(const uint64_t *d_hashes, const uint64_t *d_offsets, uint64_t n, uint64_t total,
+                                 const uint64_t *d_other_hashes, const uint64_t *d_other_offsets, uint64_t other_len,
+                                 uint32_t keep_present, uint32_t grid, uint64_t *d_out_hashes, uint64_t capacity,
+                                 uint64_t *d_out_offsets, uint64_t *d_result, void *d_workspace, uint64_t workspace_bytes, void *stream);
+/* groups: one number < n_groups per row of the set (NULL: one group); need: one count per group (NULL: 1), need_all != 0: the
+ * group's row count; names: NULL or one C string per group.  A num set takes the union only (MISMATCH_NUM otherwise). */
+SmgpuSketchSet *smgpu_sketchset_merge_groups(const SmgpuSketchSet *set, const uint32_t *groups, uint64_t n_groups, const uint32_t *need,
+                                             uint32_t need_all, const char *const *names);
+/* other: a set of one row (against every row) or of as many rows as `set` (row by row); parameters must match in the
+ * reference's order (ksize, hash function, scaled, seed).  Names and file names follow the receiver's rows. */
+SmgpuSketchSet *smgpu_sketchset_filter(const SmgpuSketchSet *set, const SmgpuSketchSet *other, uint32_t keep_present);
+SmgpuSketchSet *smgpu_sketchset_filter_sketch(const SmgpuSketchSet *set, const SourmashKmerMinHash *mh, uint32_t keep_present);
+/* Every row cut to its hashes <= max_hash; a larger max_hash than the set's is CANNOT_UPSAMPLE_SCALED. */
+SmgpuSketchSet *smgpu_sketchset_downsample(const SmgpuSketchSet *set, uint64_t max_hash);
+
 #ifdef __cplusplus
 }
 #endif

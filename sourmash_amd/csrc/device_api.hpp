@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "find_core.hpp"
+#include "qindex_core.hpp"
 
 namespace smg {
 
@@ -268,6 +269,56 @@ size_t gather_rows_workspace_bytes(uint64_t m, uint64_t q_total, uint64_t n_pick
 // gather_rows_core.hpp (GR_BAD_*) -- then the outputs hold nothing; ms3 (may be null): milliseconds of the owner pass, the tally
 // pass and the pair sort.  hipErrorInvalidValue: an argument smgpu_gather_rows_raw refuses.
 hipError_t gather_rows_run(const GatherRowsArgs& args, uint64_t* n_owned, uint32_t* trouble, float* ms3, hipStream_t stream);
+
+// ---- setops.hip (set algebra on a CSR collection: merge by group, intersect, subtract; setops_core.hpp holds its rules) -----------
+// Merge: the CSR of n rows (d_offsets: n + 1 positions in d_hashes, `total` hashes between the first and the last) -> a CSR of
+// n_groups rows, row g = the hashes that at least need-of-g rows of group g hold, ascending.  d_groups: the group of every row,
+// < n_groups (null: every row in group 0); d_need: one count per group (null: 1), or with need_all != 0 the group's row count.
+// max_hash: of the set (0 for num sets; it chooses the key form); num != 0: every result row is cut to its num smallest.
+// d_out_hashes: room for `total`; d_out_offsets: n_groups + 1; d_result (2 x u64): [0] hashes of the result, [1] distinct
+// (group, hash) pairs.
+struct SetopsMergeArgs {
+    const uint64_t *d_hashes, *d_offsets;
+    uint64_t n, total;
+    const uint32_t* d_groups;
+    uint64_t n_groups;
+    const uint32_t* d_need;
+    uint32_t need_all;
+    uint64_t max_hash, num;
+    uint64_t *d_out_hashes, *d_out_offsets, *d_result;
+    void* d_workspace;
+    uint64_t workspace_bytes;
+};
+size_t setops_merge_workspace_bytes(uint64_t total, uint64_t n_groups);
+// Synchronises the stream.  hipErrorInvalidValue: an argument smgpu_setops_merge_raw refuses.
+hipError_t setops_merge_run(const SetopsMergeArgs& args, uint64_t* total_out, hipStream_t stream);
+// Filter: row r of the result = the hashes of row r that are (keep_present != 0) or are not members of the other sketch.
+// d_other_offsets null: ONE sketch, d_other_hashes[0, other_len) ascending, for every row (looked up through a query index built by
+// the call); otherwise the second set's CSR, n rows, row r for row r.  grid: workgroups (0: the launcher's own number).
+// d_out_offsets: n + 1; d_result (2 x u64): [0] hashes of the result, [1] the trouble word of the write.
+struct SetopsFilterArgs {
+    const uint64_t *d_hashes, *d_offsets;
+    uint64_t n, total;
+    const uint64_t *d_other_hashes, *d_other_offsets;
+    uint64_t other_len;
+    uint32_t keep_present, grid;
+    uint64_t *d_out_offsets, *d_result;
+    void* d_workspace;
+    uint64_t workspace_bytes;
+};
+// what the count leaves for the write (the workspace keeps the rest)
+struct SetopsFilterState {
+    QIndex qi;
+    uint64_t other_max = 0, total = 0;
+    bool counted = false;
+};
+size_t setops_filter_workspace_bytes(uint64_t n, uint64_t total, uint64_t other_len);
+// The two modes of the one kernel, with the scan of the counts between them.  The count writes d_out_offsets and reads the total
+// back (it synchronises the stream), so that the caller can make room; the write puts the kept hashes into d_out_hashes (room for
+// `capacity` >= the total) and synchronises.  *trouble: setops_core.hpp's SetopsTrouble -- then the output holds nothing of use.
+hipError_t setops_filter_count(const SetopsFilterArgs& args, SetopsFilterState& state, uint64_t* total_out, hipStream_t stream);
+hipError_t setops_filter_write(const SetopsFilterArgs& args, const SetopsFilterState& state, uint64_t* d_out_hashes, uint64_t capacity,
+                               uint32_t* trouble, hipStream_t stream);
 
 // ---- synth.hip --------------------------------------------------------------------
 hipError_t synth_dna_launch(uint8_t* d_out, uint64_t start, uint64_t n, uint64_t seed, uint64_t record_len,

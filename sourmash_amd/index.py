@@ -514,6 +514,97 @@ class SketchSet(RustObject):
         return GatherStats._from_handle(ptr, self, queries=None, with_abundance=with_abundance, query_scaled=scaled)
 
 
+    # ---- set algebra on the resident CSR (csrc/setops.hip): every method returns a NEW set, this one is unchanged ------------------
+    def merge(self, groups=None, *, min_rows=1, names=None):
+        """The rows merged by group -> a set of G rows: row g holds the hashes that at least min_rows rows of group g hold.
+        groups: one integer per row, any order, values 0 .. G - 1 with G = max + 1 (None: all rows in one group).  min_rows=1 is
+        the union (MinHash.merge, `sig merge --flatten`), min_rows="all" the intersection of a group's rows (`sig intersect`).  A
+        group without rows, or of fewer rows than an integer min_rows, gives an empty row.  A num set gives the num smallest of
+        the union, and takes min_rows=1 only.  names: one name per group."""
+        g_arr, n_groups, need, need_all, name_arr = _merge_plan(len(self), self.params[4], groups, min_rows, names)
+        return SketchSet._from_objptr(self._methodcall(lib.smgpu_sketchset_merge_groups, g_arr.ctypes.data_as(C.c_void_p) if g_arr is not None else None,
+                                                       n_groups, need.ctypes.data_as(C.c_void_p) if need is not None else None, need_all, name_arr))
+
+    def _filter(self, other, keep_present):
+        from .minhash import MinHash
+        if isinstance(other, MinHash):
+            flat = other.flatten()                                      # (held until the call returns: a flattened copy is a new object)
+            return SketchSet._from_objptr(self._methodcall(lib.smgpu_sketchset_filter_sketch, flat._get_objptr(), keep_present))
+        if not isinstance(other, SketchSet):
+            raise TypeError("the other side is a MinHash or a SketchSet")
+        _check_other_rows(len(self), len(other))
+        return SketchSet._from_objptr(self._methodcall(lib.smgpu_sketchset_filter, other._get_objptr(), keep_present))
+
+    def subtract(self, other):
+        """Every row without the hashes of `other` (MinHash.remove_many, `sig subtract`): a MinHash or a SketchSet of one row is
+        taken from every row, a SketchSet of len(self) rows row by row.  Parameters must match (ksize, moltype, scaled, seed; the
+        errors are count_common's): downsample first where the scaled differ."""
+        return self._filter(other, 0)
+
+    def intersect(self, other):
+        "every row's hashes that `other` holds too (MinHash.intersection, `sig intersect`); `other` as for subtract"
+        return self._filter(other, 1)
+
+    def downsample(self, scaled):
+        "every row cut to the hashes a sketch of `scaled` keeps (MinHash.downsample); a smaller scaled, or a num set, is a ValueError"
+        from .minhash import _get_max_hash_for_scaled
+        _check_downsample(self.params, scaled)
+        return SketchSet._from_objptr(self._methodcall(lib.smgpu_sketchset_downsample, _get_max_hash_for_scaled(int(scaled))))
+
+
+def _merge_plan(n_rows, num, groups, min_rows, names):
+    """The arguments of SketchSet.merge checked and turned into what smgpu_sketchset_merge_groups takes -> (groups u32 or None,
+    n_groups, need u32 per group or None, need_all, names array or None).  No device is needed."""
+    if groups is None:
+        g_arr, n_groups = None, 1
+    else:
+        g = np.asarray(groups)
+        if g.ndim != 1 or len(g) != n_rows:
+            raise ValueError("one group number per row of the set is needed")
+        if len(g) and not np.issubdtype(g.dtype, np.integer):
+            raise ValueError("group numbers are integers")
+        g = g.astype(np.int64) if len(g) else np.zeros(0, dtype=np.int64)
+        if len(g) and int(g.min()) < 0:
+            raise ValueError("group numbers are not negative")
+        n_groups = int(g.max()) + 1 if len(g) else 0
+        if n_groups > 0xfffffffe:
+            raise ValueError("group numbers fit 32 bits")
+        g_arr = np.ascontiguousarray(g, dtype=np.uint32)
+    if isinstance(min_rows, str):
+        if min_rows != "all":
+            raise ValueError('min_rows is a count, or "all"')
+        need, need_all = None, 1
+    else:
+        if int(min_rows) != min_rows or int(min_rows) < 1:
+            raise ValueError("min_rows is at least 1")
+        need_all = 0
+        need = None if int(min_rows) == 1 else np.full(max(n_groups, 1), min(int(min_rows), 0xffffffff), dtype=np.uint32)
+    if num and (need_all or need is not None):
+        raise ValueError("a num set merges to the union of its rows only (min_rows=1)")
+    name_arr = None
+    if names is not None:
+        enc = [v.encode("utf-8") if isinstance(v, str) else bytes(v) for v in names]
+        if len(enc) != n_groups:
+            raise ValueError("one name per group is needed")
+        name_arr = (C.c_char_p * max(n_groups, 1))(*enc)
+    return g_arr, n_groups, need, need_all, name_arr
+
+
+def _check_other_rows(n_rows, n_other):
+    "subtract / intersect: the other set has one row, or one per row of this set"
+    if n_other != 1 and n_other != n_rows:
+        raise ValueError(f"the other set has {n_other} rows: one row, or the {n_rows} of this set, are needed")
+
+
+def _check_downsample(params, scaled):
+    "the errors of MinHash.downsample(scaled=...) for a set of these params (ksize, moltype, seed, scaled, num)"
+    cur, num = params[3], params[4]
+    if num or not cur:
+        raise ValueError("cannot downsample a num MinHash using scaled")
+    if cur > scaled:
+        raise ValueError(f"new scaled {scaled} is lower than current sample scaled {cur}")
+
+
 class _ManyGather(RustObject):
     "the picks of a many-query gather on the host (smgpu_manygather_*): offsets per query into rows / isect, in rank order"
     __dealloc_func__ = lib.smgpu_manygather_free
