@@ -258,7 +258,7 @@ bool smgpu_counter_best(const SmgpuCounter* p, uint64_t* index, uint64_t* count)
         hip_check(hipStreamSynchronize(st), "sync");
         if (key == 0) return false;
         *count = key >> 32;
-        *index = (uint64_t)(0xffffffffull & ~key);
+        *index = gather_key_index(key);
         return true;
     });
 }

@@ -8,8 +8,8 @@
 //   * the hash space is cut into DX_P buckets by the top bits (hashes are MurmurHash3 values below max_hash: uniform); rows are
 //     sorted, so a row's hashes in a bucket are a contiguous slice, and one streaming pass writes where every slice starts
 //     (dx_bounds_kernel);
-//   * pass 1, one workgroup per bucket: every slice of the bucket is walked (16 rows flattened per wave step, as in
-//     gather.hip) and its hashes counted in an LDS hash table -- at most DX_MAXD distinct ones; a bucket that holds more
+//   * pass 1, one workgroup per bucket: every slice of the bucket is walked (16 rows flattened per wave step:
+//     slice_walk.hpp) and its hashes counted in an LDS hash table -- at most DX_MAXD distinct ones; a bucket that holds more
 //     raises a flag and the caller falls back to the sort.  The table becomes the bucket's piece of the dictionary: per
 //     distinct hash either its index among the bucket's frequent hashes or the offset of its row list among the bucket's
 //     rare elements;
@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "device_api.hpp"
+#include "slice_walk.hpp"
 
 namespace smg {
 
@@ -129,15 +130,8 @@ __global__ __launch_bounds__(256) void dx_bounds_kernel(const uint64_t* __restri
     }
 }
 
-// The slices of DX_EPW rows inside one bucket as ONE list that the 64 lanes of a wave walk together (the idiom of
-// gather.hip's range kernels): lane l < DX_EPW loads slice l, prefix sums give every flattened position its slice.
-struct DxGroup {
-    uint32_t total;                 // elements of the group
-    uint32_t incl, excl;            // lane l < DX_EPW: end / start of slice l in the flattened list
-    uint32_t lo_lo, lo_hi;          // lane l < DX_EPW: absolute index of the slice's first element
-    uint32_t bound[DX_EPW - 1];     // wave-uniform: end of slices 0 .. 14
-};
-// the loads of a group (issued early: the chain bounds -> hashes -> table is what a wave waits for) ...
+// The slices of DX_EPW rows inside one bucket are walked as ONE list by the 64 lanes of a wave (slice_walk.hpp: SliceGroup<DX_EPW>);
+// lane l < DX_EPW loads slice l, early: the chain bounds -> hashes -> table is what a wave waits for.
 struct DxRaw {
     uint64_t lo;                    // lane l < DX_EPW: absolute index of the first element of slice l
     uint32_t cnt;                   // ... and its length
@@ -155,30 +149,6 @@ __device__ __forceinline__ DxRaw dx_group_fetch(const uint64_t* __restrict__ off
         r.cnt = e - a;
     }
     return r;
-}
-// ... and the prefix sums over them
-__device__ __forceinline__ void dx_group_build(DxGroup& g, const DxRaw& r, int lane) {
-    uint32_t incl = r.cnt;
-#pragma unroll
-    for (int s = 1; s < DX_EPW; s <<= 1) {
-        const uint32_t v = __shfl_up(incl, s);
-        if (lane >= s) incl += v;
-    }
-    g.total = __shfl(incl, DX_EPW - 1);
-#pragma unroll
-    for (int k = 0; k < DX_EPW - 1; ++k) g.bound[k] = __shfl(incl, k);
-    g.incl = incl;
-    g.excl = incl - r.cnt;
-    g.lo_lo = (uint32_t)r.lo;
-    g.lo_hi = (uint32_t)(r.lo >> 32);
-}
-// flattened position t (< g.total) -> slice h and the element's absolute index
-__device__ __forceinline__ uint64_t dx_group_at(const DxGroup& g, uint32_t t, int& h) {
-    h = 0;
-#pragma unroll
-    for (int k = 0; k < DX_EPW - 1; ++k) h += t >= g.bound[k];
-    const uint64_t start = ((uint64_t)(uint32_t)__shfl((int)g.lo_hi, h) << 32) | (uint32_t)__shfl((int)g.lo_lo, h);
-    return start + (t - (uint32_t)__shfl((int)g.excl, h));
 }
 
 // pass 1: count the distinct hashes of bucket blockIdx.x; leave its piece of the dictionary and its statistics
@@ -225,8 +195,8 @@ __global__ __launch_bounds__(DX_THREADS) void dx_count_kernel(const uint64_t* __
         if (*over) break;                                           // the bucket does not fit: stop at once, the sort takes over
         const DxRaw cur = next;
         next = dx_group_fetch(offsets, bounds, n, b, row0 + DX_CHUNK, lane);      // (rows past the end: nothing is loaded)
-        DxGroup g;
-        dx_group_build(g, cur, lane);
+        SliceGroup<DX_EPW> g;
+        g.build(cur.lo, cur.cnt, lane);
         for (uint32_t t0 = 0; t0 < g.total; t0 += 128) {            // wave-uniform trip count (the shuffles read lanes 0 .. 15)
             if (*over) break;                                       // (one LDS word read by all lanes: uniform)
             uint64_t x[2];
@@ -236,7 +206,7 @@ __global__ __launch_bounds__(DX_THREADS) void dx_count_kernel(const uint64_t* __
                 const uint32_t t = t0 + 64u * (uint32_t)u + (uint32_t)lane;
                 ok[u] = t < g.total;
                 int h;
-                x[u] = hashes[dx_group_at(g, ok[u] ? t : g.total - 1, h)];
+                x[u] = hashes[g.at(ok[u] ? t : g.total - 1, h)];
             }
 #pragma unroll
             for (int u = 0; u < 2; ++u)
@@ -345,15 +315,15 @@ __global__ __launch_bounds__(DX_ETHREADS) void dx_emit_kernel(const uint64_t* __
         for (int k = tid; k < DX_CAP; k += DX_ETHREADS) s_key[k] = DX_EMPTY;
         for (uint32_t w = fw; w < W; w += 4) s_tile[frr][w] = 0;
         if (tid == 0) { s_ones_val = 0; s_ones_end = 0; s_ones_ent = 0; }
-        DxGroup g;
-        dx_group_build(g, raw, lane);
+        SliceGroup<DX_EPW> g;
+        g.build(raw.lo, raw.cnt, lane);
         uint64_t x0[2] = {0, 0};
         int h0[2] = {0, 0};
         if (g.total) {
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const uint32_t t = 64u * (uint32_t)u + (uint32_t)lane;
-                x0[u] = hashes[dx_group_at(g, t < g.total ? t : g.total - 1, h0[u])];
+                x0[u] = hashes[g.at(t < g.total ? t : g.total - 1, h0[u])];
             }
         }
         __syncthreads();
@@ -398,7 +368,7 @@ __global__ __launch_bounds__(DX_ETHREADS) void dx_emit_kernel(const uint64_t* __
         for (uint32_t t0 = 128; t0 < g.total; t0 += 64) {                 // longer groups: the rest, a step at a time
             const uint32_t t = t0 + (uint32_t)lane;
             int h;
-            const uint64_t at = dx_group_at(g, t < g.total ? t : g.total - 1, h);
+            const uint64_t at = g.at(t < g.total ? t : g.total - 1, h);
             if (t >= g.total) continue;
             emit(hashes[at], h);
         }

@@ -33,6 +33,7 @@
 #include <chrono>
 #include "qindex.hpp"
 #include "gather_parts.hpp"
+#include "slice_walk.hpp"
 
 namespace smg {
 
@@ -41,7 +42,7 @@ namespace {
 __device__ __forceinline__ void record_pending(unsigned long long* state, uint64_t* out_idx, uint64_t* out_isect) {
     if (state[GS_PENDING]) {
         const unsigned long long r = state[GS_ROUNDS], acc = state[GS_ACC];
-        out_idx[r] = 0xffffffffull & ~state[GS_KEY];
+        out_idx[r] = gather_key_index(state[GS_KEY]);
         out_isect[r] = acc;
         state[GS_QLEN] -= acc;
         state[GS_ACC] = 0;
@@ -51,15 +52,11 @@ __device__ __forceinline__ void record_pending(unsigned long long* state, uint64
     }
 }
 
-// search.py:15-37 + index/__init__.py:817-861: stop when nothing overlaps, the query is exhausted, the threshold
-// is unattainable (more hashes than the query has left) or the best overlap is below it
+// the stop rules (gather_stops) on the round's winner: the loop ends, or the round waits to be recorded
 __device__ __forceinline__ void stop_rules(unsigned long long* state, unsigned long long key) {
-    const unsigned long long count = key >> 32, qlen = state[GS_QLEN], thr = state[GS_THR];
-    if (key == 0 || qlen == 0 || qlen < thr || count < thr) state[GS_DONE] = 1;
+    if (gather_stops(key, state[GS_QLEN], state[GS_THR])) state[GS_DONE] = 1;
     else state[GS_PENDING] = 1;
 }
-
-
 
 // Packed arg-max with the reference tie-break (highest count, then lowest global index) over all counters, then --
 // in the workgroup that finishes last (ticket counter) -- the bookkeeping of the previous round, the final reduction
@@ -79,7 +76,7 @@ __global__ __launch_bounds__(256) void pick_kernel(const unsigned long long* __r
     for (uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; d < ndb; d += (uint64_t)gridDim.x * blockDim.x) {
         const unsigned long long c = counters[d];
         if (c) {
-            const unsigned long long key = (c << 32) | (0xffffffffull & ~(unsigned long long)(index_base + d));
+            const unsigned long long key = gather_key(c, index_base + d);
             k = key > k ? key : k;
         }
     }
@@ -193,7 +190,7 @@ __global__ __launch_bounds__(256) void topk_kernel(const unsigned long long* __r
     for (int i = 0; i < TOPK_LIST; ++i) best[i] = 0;
     for (uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; d < ndb; d += (uint64_t)gridDim.x * blockDim.x) {
         const unsigned long long c = counters[d];
-        if (c) topk_insert(best, (c << 32) | (0xffffffffull & ~(unsigned long long)(index_base + d)));
+        if (c) topk_insert(best, gather_key(c, index_base + d));
     }
     topk_block_merge(best, want, s_list);
     if (threadIdx.x < TOPK_LIST)
@@ -227,7 +224,7 @@ __global__ __launch_bounds__(256) void export_cands_kernel(const unsigned long l
     const unsigned long long key = state[GS_DONE] ? 0ull : sel[c];
     uint64_t lo = 0, len = 0;
     if (key) {
-        const uint64_t d = (0xffffffffull & ~key) - index_base;
+        const uint64_t d = gather_key_index(key) - index_base;
         lo = offsets[d];
         len = offsets[d + 1] - lo;
         if (len + GATHER_CAND_HEAD > stride) len = stride - GATHER_CAND_HEAD;   // cannot happen when stride covers the longest row
@@ -296,7 +293,7 @@ __global__ __launch_bounds__(64) void replay_pick_kernel(const unsigned long lon
     unsigned long long key = 0;
     if ((uint32_t)lane < n_cand) {
         const unsigned long long cnt = cand_count[lane];
-        if (cnt && cand_key[lane]) key = (cnt << 32) | (0xffffffffull & cand_key[lane]);
+        if (cnt && cand_key[lane]) key = gather_key(cnt, gather_key_index(cand_key[lane]));   // the same row, its count of now
     }
     unsigned long long best = key;
     for (int off = 32; off > 0; off >>= 1) {
@@ -356,7 +353,7 @@ __global__ __launch_bounds__(256) void apply_kernel(QIndex qi, uint8_t* alive, c
         len = rowbuf[0];
         row = rowbuf + 1;
     } else {
-        const uint64_t d = (0xffffffffull & ~state[GS_KEY]) - index_base;
+        const uint64_t d = gather_key_index(state[GS_KEY]) - index_base;
         row = hashes + offsets[d];
         row_pos = qpos + offsets[d];
         len = offsets[d + 1] - offsets[d];
@@ -392,41 +389,22 @@ __global__ __launch_bounds__(256) void apply_kernel(QIndex qi, uint8_t* alive, c
             else atomicAdd(&state[GS_QLEN], 0ull - (unsigned long long)__popcll(hits));   // protocol path: a later fused run starts from the truth
         }
         if (!hits) continue;
-        // lane l < APPLY_EPW: posting list [lo, lo + n) of its hit; inclusive prefix sums over those lanes
-        uint64_t lo = 0;
-        uint32_t n = 0;
-        if (j != NONE32) {
-            lo = list_lo;
-            n = (uint32_t)(list_hi - list_lo);
-        }
-        uint32_t incl = n;
-#pragma unroll
-        for (int d = 1; d < APPLY_EPW; d <<= 1) {
-            const uint32_t v = __shfl_up(incl, d);
-            if (lane >= d) incl += v;
-        }
-        const uint32_t total = __shfl(incl, APPLY_EPW - 1);
-        uint32_t bound[APPLY_EPW - 1];                          // wave-uniform: end of the lists of hits 0 .. 14
-#pragma unroll
-        for (int k = 0; k < APPLY_EPW - 1; ++k) bound[k] = __shfl(incl, k);
-        const uint32_t excl = incl - n;
-        const uint32_t lo_lo = (uint32_t)lo, lo_hi = (uint32_t)(lo >> 32);
-        // wave-uniform trip count (the shuffles read lanes 0 .. 15, which must not have left the loop); four
+        // lane l < APPLY_EPW: the posting list of its hit (empty without one); the lists are walked as one (slice_walk.hpp)
+        SliceGroup<APPLY_EPW> g;
+        g.build(j != NONE32 ? list_lo : 0, j != NONE32 ? (uint32_t)(list_hi - list_lo) : 0u, lane);
+        // wave-uniform trip count (SliceGroup::at: the lanes that hold the lists must not have left the loop); four
         // independent loads are in flight before their atomics are issued
         constexpr int UNROLL = 4;
-        for (uint32_t t0 = 0; t0 < total; t0 += 64 * UNROLL) {
+        for (uint32_t t0 = 0; t0 < g.total; t0 += 64 * UNROLL) {
             uint32_t target[UNROLL];
             bool live[UNROLL];
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u) {
                 const uint32_t t = t0 + (uint32_t)(64 * u + lane);
-                int h = 0;
-#pragma unroll
-                for (int k = 0; k < APPLY_EPW - 1; ++k) h += t >= bound[k];
-                const uint64_t start = ((uint64_t)(uint32_t)__shfl((int)lo_hi, h) << 32) | (uint32_t)__shfl((int)lo_lo, h);
-                const uint32_t first = (uint32_t)__shfl((int)excl, h);
-                live[u] = t < total;
-                target[u] = live[u] ? post_rows[start + (t - first)] : 0u;
+                int h;
+                const uint64_t at = g.at(t, h);
+                live[u] = t < g.total;
+                target[u] = live[u] ? post_rows[at] : 0u;
             }
 #pragma unroll
             for (int u = 0; u < UNROLL; ++u) {
@@ -620,7 +598,7 @@ __global__ __launch_bounds__(PL_THREADS) void gather_loop_kernel(LoopArgs a) {
         for (uint32_t i = tid; i < n_own; i += PL_THREADS) {
             const unsigned long long c = s_cnt[i];
             if (c) {
-                const unsigned long long key = (c << 32) | (0xffffffffull & ~(unsigned long long)(a.index_base + r0 + i));
+                const unsigned long long key = gather_key(c, a.index_base + r0 + i);
                 k = key > k ? key : k;
             }
         }
@@ -634,7 +612,7 @@ __global__ __launch_bounds__(PL_THREADS) void gather_loop_kernel(LoopArgs a) {
         if (tid == 0) {
             uint32_t start = 0, len = 0;
             if (k) {
-                const uint32_t i = (uint32_t)((0xffffffffull & ~k) - a.index_base - r0);
+                const uint32_t i = (uint32_t)(gather_key_index(k) - a.index_base - r0);
                 start = s_off[i];
                 len = s_off[i + 1] - start;
             }
@@ -786,7 +764,7 @@ __global__ __launch_bounds__(PL_THREADS) void gather_loop_kernel(LoopArgs a) {
         }
         // ---- stop rules on the round's winner (search.py:15-37; the same values in every workgroup) ----
         last_key = top;
-        if (top == 0 || qlen == 0 || qlen < thr || (top >> 32) < thr) break;
+        if (gather_stops(top, qlen, thr)) break;
         const uint32_t wstart = s_wstart, wlen = s_wlen;
         // a position of the winning row: from this rank's own index, or from the staged copy of another rank's row
         auto row_pos = [&](uint32_t i) -> uint32_t {
@@ -919,7 +897,7 @@ __global__ __launch_bounds__(PL_THREADS) void gather_loop_kernel(LoopArgs a) {
         }
         // ---- bookkeeping (pick_kernel's record_pending) ----
         if (wg == 0 && tid == 0) {
-            a.out_idx[rounds] = 0xffffffffull & ~top;
+            a.out_idx[rounds] = gather_key_index(top);
             a.out_isect[rounds] = isect;
         }
         qlen -= isect;

@@ -4,12 +4,13 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "qindex.hpp"
+#include "gather_key.hpp"           // gather_key, gather_key_index, gather_stops
 
 namespace smg {
 
 // slots of the 16 x u64 device state block
 enum GatherSlot {
-    GS_KEY = 0,      // packed winner of the round in flight: (count << 32) | (0xffffffff & ~global index)
+    GS_KEY = 0,      // packed winner of the round in flight: gather_key(count, global index)
     GS_DONE = 1,     // 1 once a stop rule fired
     GS_ROUNDS = 2,   // results recorded so far
     GS_QLEN = 3,     // hashes of the query still uncovered

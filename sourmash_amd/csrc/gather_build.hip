@@ -5,8 +5,9 @@
 // inverted ONCE: post_rows[post_off[j] .. post_off[j+1]) = the rows holding query hash j, counters[d] = |Q ∩ D_d|, and qpos[e] =
 // the query position of every database hash (or NONE32), which the rounds of gather.hip read instead of looking hashes up again.
 //   small databases        build_count_kernel / build_fill_kernel: a lookup per element, atomic cursors
-//   range builder          build_bounds_kernel, build_range_kernel (pass 1 by lookups in L2), build_partition_kernel (pass 2a),
-//                          build_scatter_kernel (pass 2b: a window's postings sorted by (list, row block) in LDS)
+//   range builder          build_bounds_kernel, build_range_count_kernel (pass 1 by lookups in L2), build_partition_kernel (pass 2a),
+//                          build_scatter_kernel (pass 2b: a window's postings sorted by (list, row block) in LDS); or, in place
+//                          of pass 2, build_range_fill_kernel (one store per posting)
 //   staged range builder   pass 1 + 2a by the lean streaming kernel of overlap.hip (build_stage_launch), then
 //                          build_count_runs_kernel, build_merge_counts_kernel, build_scatter_kernel, build_bounds_table_kernel
 // Every block comes from the arena: a warm build makes no driver call.  DESIGN.md 4.5; measurements in profiles/HISTORY.md 4.5.
@@ -21,6 +22,7 @@
 #include <chrono>
 #include "qindex.hpp"
 #include "gather_parts.hpp"
+#include "slice_walk.hpp"
 
 namespace smg {
 
@@ -85,8 +87,8 @@ __global__ __launch_bounds__(256) void build_fill_kernel(const uint32_t* __restr
 //   partial  [B][nq]       pass 1: postings of query hash j contributed by block b; then its exclusive prefix over b
 // so that in pass 2 the slot of an element is post_off[j] + partial[b][j] + (LDS cursor of j in this workgroup).
 constexpr int BR_RANGE = 32768;      // query positions per range: row slices long enough (~1 KB) to read DRAM efficiently
-constexpr int BR_EPW = 16;           // row slices a wave flattens per step (see apply_kernel)
-constexpr int BR_AHEAD = 4;   // steps of 64 lookups a wave keeps in flight in pass 1 (see build_range_kernel)
+constexpr int BR_EPW = 16;           // row slices a wave walks as one list (slice_walk.hpp)
+constexpr int BR_AHEAD = 4;   // steps of 64 lookups a wave keeps in flight in pass 1 (see build_range_count_kernel)
 constexpr int BR_THREADS = 512;      // 64 KB of LDS per workgroup (u16 slots, two per word): 2 workgroups = 16 waves per CU
 // Two-level fill (the default): a 4-byte store per posting straight into its list leaves 32,768 lists x 8 lines open per
 // range -- far more than one L2 -- and partially filled lines were evicted and fetched back (8.1 GB written and 13.6 GB
@@ -129,150 +131,98 @@ __global__ __launch_bounds__(256) void build_bounds_kernel(const uint64_t* __res
     }
 }
 
-// MODE 0: pass 1 (lookups, query positions, histogram, counters)   MODE 1: direct fill (one store per posting into its list)
-// (Rounds 1-4 also had a MODE 2 -- pass 2a by plain 4-byte stores into 128 open streams -- and a MODE 3 -- the overlap pass by
-//  lookups in L2; build_partition_kernel and the streaming kernels of overlap.hip replaced them and they are gone.)
-template <int MODE>
-__global__ __launch_bounds__(BR_THREADS) void build_range_kernel(QIndex qi, const uint64_t* __restrict__ hashes,
-                                                          const uint64_t* __restrict__ offsets, uint64_t ndb,
-                                                          const uint32_t* __restrict__ bounds, uint32_t R, uint32_t B,
-                                                          uint64_t rows_per_block, uint32_t* __restrict__ partial,
-                                                          const uint64_t* __restrict__ post_off,
-                                                          uint32_t* __restrict__ post_rows, unsigned long long* counters,
-                                                          uint32_t* __restrict__ qpos, uint32_t* __restrict__ subcnt) {
-    static_assert(MODE == 0 || MODE == 1, "");
-    constexpr bool FILL = MODE == 1;
-    constexpr bool COUNT = MODE == 0;
-    // pass 1: histogram; direct fill: cursors.  A block holds < 65536 rows and a row adds at most 1 to a slot, so 16 bits do.
-    __shared__ uint32_t s_slot[BR_RANGE / 2];
-    // Launch order: ranges in groups of 8, range (8g + x) entirely on workgroup ids = x mod 8, i.e. on one XCD (workgroups
-    // are dealt to the 8 XCDs round-robin), blocks in ascending order.  The 4-byte stores of pass 2 that fill one posting
-    // list then meet in a single L2, whose working set is one open cache line per list of the range.
+// Workgroup (range r, row block b) of the range kernels, from blockIdx.x.  Launch order: ranges in groups of 8, range (8g + x)
+// entirely on workgroup ids = x mod 8, i.e. on one XCD (workgroups are dealt to the 8 XCDs round-robin), blocks in ascending
+// order.  The 4-byte stores of pass 2 that fill one posting list then meet in a single L2, whose working set is one open cache
+// line per list of the range.
+struct RangeWork { uint32_t r, b; uint64_t j0, d_lo, d_hi; };       // j0: the range's first query position; [d_lo, d_hi): the block's rows
+__device__ __forceinline__ bool range_work(RangeWork& rw, uint32_t R, uint32_t B, uint64_t rows_per_block, uint64_t ndb) {
     const uint32_t local = blockIdx.x % (8u * B);
-    const uint32_t r = (blockIdx.x / (8u * B)) * 8u + (local & 7u), b = local >> 3;
-    if (r >= R) return;
-    const uint64_t j0 = (uint64_t)r * BR_RANGE;
-    const uint32_t nj = (uint32_t)(qi.nq - j0 < (uint64_t)BR_RANGE ? qi.nq - j0 : (uint64_t)BR_RANGE);
+    rw.r = (blockIdx.x / (8u * B)) * 8u + (local & 7u);
+    rw.b = local >> 3;
+    if (rw.r >= R) return false;
+    rw.j0 = (uint64_t)rw.r * BR_RANGE;
+    rw.d_lo = (uint64_t)rw.b * rows_per_block;
+    rw.d_hi = rw.d_lo + rows_per_block < ndb ? rw.d_lo + rows_per_block : ndb;
+    return true;
+}
+// the slices of rows dbase .. dbase + BR_EPW - 1 inside range r as one list; from_start: from the row's first element instead
+__device__ __forceinline__ void range_group(SliceGroup<BR_EPW>& g, const uint64_t* __restrict__ offsets, uint64_t ndb,
+                                            const uint32_t* __restrict__ bounds, uint32_t r, bool from_start, uint64_t dbase, uint64_t d_hi, int lane) {
+    uint64_t lo = 0;
+    uint32_t n = 0;
+    const uint64_t d = dbase + lane;
+    if (lane < BR_EPW && d < d_hi) {
+        const uint32_t a = from_start ? 0u : bounds[(uint64_t)r * ndb + d], e = bounds[(uint64_t)(r + 1) * ndb + d];
+        lo = offsets[d] + a;
+        n = e - a;
+    }
+    g.build(lo, n, lane);
+}
+// What pass 1 and the direct fill begin with: the work decode and the range's LDS slots at zero -- pass 1: the histogram, direct
+// fill: the cursors.  A block holds < 65536 rows and a row adds at most 1 to a slot, so 16 bits do (two slots per word).
+__device__ __forceinline__ bool range_begin(RangeWork& rw, uint32_t (&s_slot)[BR_RANGE / 2], uint32_t R, uint32_t B, uint64_t rows_per_block, uint64_t ndb) {
+    if (!range_work(rw, R, B, rows_per_block, ndb)) return false;
     for (int k = threadIdx.x; k < BR_RANGE / 2; k += BR_THREADS) s_slot[k] = 0;
     __syncthreads();
-    const uint64_t d_lo = (uint64_t)b * rows_per_block;
-    const uint64_t d_hi = d_lo + rows_per_block < ndb ? d_lo + rows_per_block : ndb;
+    return true;
+}
+
+// Pass 1 by lookups in L2: query positions, histogram, counters.  (Rounds 1-4 had further forms of this kernel; build_partition_kernel
+// and the streaming kernels of overlap.hip replaced them.)
+__global__ __launch_bounds__(BR_THREADS) void build_range_count_kernel(QIndex qi, const uint64_t* __restrict__ hashes,
+                                                          const uint64_t* __restrict__ offsets, uint64_t ndb, const uint32_t* __restrict__ bounds,
+                                                          uint32_t R, uint32_t B, uint64_t rows_per_block, uint32_t* __restrict__ partial,
+                                                          unsigned long long* counters, uint32_t* __restrict__ qpos, uint32_t* __restrict__ subcnt) {
+    __shared__ uint32_t s_slot[BR_RANGE / 2];
+    RangeWork rw;
+    if (!range_begin(rw, s_slot, R, B, rows_per_block, ndb)) return;
+    const uint32_t nj = (uint32_t)(qi.nq - rw.j0 < (uint64_t)BR_RANGE ? qi.nq - rw.j0 : (uint64_t)BR_RANGE);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t* part_b = partial + (uint64_t)b * qi.nq;
-    for (uint64_t dbase = d_lo + (uint64_t)wave * BR_EPW; dbase < d_hi; dbase += (BR_THREADS / 64) * BR_EPW) {
-        // lane l < BR_EPW: the slice of row dbase + l inside this range
-        uint64_t lo = 0;
-        uint32_t n = 0;
-        const uint64_t d = dbase + lane;
-        if (lane < BR_EPW && d < d_hi) {
-            // pass 1 starts its first range at the row's first element: what lies below Q[0] is looked up (and missed) like
-            // everything else, so that every element's query position is written and nobody has to pre-fill 2 GB of them
-            const uint32_t a = (MODE == 0 && r == 0) ? 0u : bounds[(uint64_t)r * ndb + d], e = bounds[(uint64_t)(r + 1) * ndb + d];
-            lo = offsets[d] + a;
-            n = e - a;
-        }
-        uint32_t incl = n;
-#pragma unroll
-        for (int s = 1; s < BR_EPW; s <<= 1) {
-            const uint32_t v = __shfl_up(incl, s);
-            if (lane >= s) incl += v;
-        }
-        const uint32_t total = __shfl(incl, BR_EPW - 1);
-        if (total == 0) continue;
-        uint32_t bound[BR_EPW - 1];                                 // wave-uniform: end of slices 0 .. 14
-#pragma unroll
-        for (int k = 0; k < BR_EPW - 1; ++k) bound[k] = __shfl(incl, k);
-        const uint32_t excl = incl - n;
-        const uint32_t lo_lo = (uint32_t)lo, lo_hi = (uint32_t)(lo >> 32);
+    for (uint64_t dbase = rw.d_lo + (uint64_t)wave * BR_EPW; dbase < rw.d_hi; dbase += (BR_THREADS / 64) * BR_EPW) {
+        // the first range starts at the row's first element: what lies below Q[0] is looked up (and missed) like everything else,
+        // so that every element's query position is written and nobody has to pre-fill 2 GB of them
+        SliceGroup<BR_EPW> g;
+        range_group(g, offsets, ndb, bounds, rw.r, rw.r == 0, dbase, rw.d_hi, lane);
+        if (g.total == 0) continue;
         uint32_t row_hits = 0;                                      // lane l < BR_EPW: hits of slice l
-        if (COUNT && qi.rec) {
-            // Lookups, BR_AHEAD steps of 64 elements at a time: a step is a chain of two loads (the hash from HBM, its
-            // record from L2, about 3 us together) and a wave that waits for each step in turn keeps 64 loads in flight --
-            // 16 waves per CU then bound the pass at ~100 G lookups/s whatever the bandwidth (6.0 ms at C5, measured).
-            // All hash loads of the steps are issued first, then all record loads, then the compares and outputs.
-            for (uint32_t t0 = 0; t0 < total; t0 += 64 * BR_AHEAD) {
-                uint64_t x[BR_AHEAD], at[BR_AHEAD];
-                bool ok[BR_AHEAD];
+        // Lookups, BR_AHEAD steps of 64 elements at a time: a step is a chain of two loads (the hash from HBM, its
+        // record from L2, about 3 us together) and a wave that waits for each step in turn keeps 64 loads in flight --
+        // 16 waves per CU then bound the pass at ~100 G lookups/s whatever the bandwidth (6.0 ms at C5, measured).
+        // All hash loads of the steps are issued first, then all record loads, then the compares and outputs.
+        for (uint32_t t0 = 0; t0 < g.total; t0 += 64 * BR_AHEAD) {  // wave-uniform trip count (SliceGroup::at)
+            uint64_t x[BR_AHEAD], at[BR_AHEAD];
+            bool ok[BR_AHEAD];
 #pragma unroll
-                for (int u = 0; u < BR_AHEAD; ++u) {
-                    const uint32_t t = t0 + 64u * (uint32_t)u + (uint32_t)lane;
-                    ok[u] = t < total;
-                    const uint32_t tt = ok[u] ? t : total - 1;      // lanes past the end re-read the last element
-                    int h = 0;
-#pragma unroll
-                    for (int k = 0; k < BR_EPW - 1; ++k) h += tt >= bound[k];
-                    const uint64_t start = ((uint64_t)(uint32_t)__shfl((int)lo_hi, h) << 32) | (uint32_t)__shfl((int)lo_lo, h);
-                    at[u] = start + (tt - (uint32_t)__shfl((int)excl, h));
-                    x[u] = hashes[at[u]];
-                }
-                __builtin_amdgcn_sched_barrier(0);                  // every hash load is out before the first one is waited for
-                QRecVal rv[BR_AHEAD];
-#pragma unroll
-                for (int u = 0; u < BR_AHEAD; ++u) rv[u] = q_rec_load(qi, x[u] <= qi.qmax ? x[u] : qi.qmax);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int u = 0; u < BR_AHEAD; ++u) {
-                    uint32_t j = q_rec_match(qi, x[u], rv[u]);
-                    if (!ok[u] || x[u] > qi.qmax) j = NONE32;
-                    if (MODE == 0 && ok[u]) qpos[at[u]] = j;
-                    const bool hit = j != NONE32;
-                    if (MODE == 0 && hit) {
-                        const uint32_t k = j - (uint32_t)j0;        // < nj: the slice lies inside the range
-                        atomicAdd(&s_slot[k >> 1], 1u << (16u * (k & 1u)));
-                    }
-                    const uint32_t tb = t0 + 64u * (uint32_t)u;
-                    const unsigned long long hits = __ballot(hit);
-                    const uint32_t a = excl > tb ? (excl - tb < 64u ? excl - tb : 64u) : 0u;
-                    const uint32_t e = incl > tb ? (incl - tb < 64u ? incl - tb : 64u) : 0u;
-                    const unsigned long long upto_e = e >= 64u ? ~0ull : ((1ull << e) - 1ull);
-                    const unsigned long long upto_a = a >= 64u ? ~0ull : ((1ull << a) - 1ull);
-                    row_hits += (uint32_t)__popcll(hits & upto_e & ~upto_a);
-                }
+            for (int u = 0; u < BR_AHEAD; ++u) {
+                const uint32_t t = t0 + 64u * (uint32_t)u + (uint32_t)lane;
+                ok[u] = t < g.total;
+                int h;
+                at[u] = g.at(ok[u] ? t : g.total - 1, h);           // lanes past the end re-read the last element
+                x[u] = hashes[at[u]];
             }
-        } else
-        for (uint32_t t0 = 0; t0 < total; t0 += 64) {               // wave-uniform trip count: the shuffles read lanes 0 .. 15
-            const uint32_t t = t0 + (uint32_t)lane;
-            int h = 0;
+            __builtin_amdgcn_sched_barrier(0);                      // every hash load is out before the first one is waited for
+            QRecVal rv[BR_AHEAD];
 #pragma unroll
-            for (int k = 0; k < BR_EPW - 1; ++k) h += t >= bound[k];
-            const uint64_t start = ((uint64_t)(uint32_t)__shfl((int)lo_hi, h) << 32) | (uint32_t)__shfl((int)lo_lo, h);
-            const uint32_t first = (uint32_t)__shfl((int)excl, h);
-            uint32_t j = NONE32;
-            if (t < total) {
-                if (FILL) {
-                    j = qpos[start + (t - first)];                  // pass 1 left it there
-                } else {
-                    j = q_find(qi, hashes[start + (t - first)]);
-                    if (MODE == 0) qpos[start + (t - first)] = j;
+            for (int u = 0; u < BR_AHEAD; ++u) rv[u] = q_rec_load(qi, x[u] <= qi.qmax ? x[u] : qi.qmax);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < BR_AHEAD; ++u) {
+                uint32_t j = q_rec_match(qi, x[u], rv[u]);
+                if (!ok[u] || x[u] > qi.qmax) j = NONE32;
+                if (ok[u]) qpos[at[u]] = j;
+                const bool hit = j != NONE32;
+                if (hit) {
+                    const uint32_t k = j - (uint32_t)rw.j0;          // < nj: the slice lies inside the range
+                    atomicAdd(&s_slot[k >> 1], 1u << (16u * (k & 1u)));
                 }
-            }
-            const bool hit = j != NONE32;
-            if (hit) {
-                const uint32_t k = j - (uint32_t)j0;                // < nj: the slice lies inside the range
-                const uint32_t sh = 16u * (k & 1u);
-                if (FILL) {
-                    const uint32_t mine = (atomicAdd(&s_slot[k >> 1], 1u << sh) >> sh) & 0xffffu;
-                    const uint64_t at = post_off ? post_off[j] + part_b[j] : (uint64_t)part_b[j];   // null: partial already holds absolute slots
-                    post_rows[at + mine] = (uint32_t)(dbase + (uint64_t)h);
-                } else if (MODE == 0) {
-                    atomicAdd(&s_slot[k >> 1], 1u << sh);
-                }
-            }
-            if (COUNT) {
-                // slice l occupies the flattened positions [excl, incl): its lanes in this step are a contiguous run
-                const unsigned long long hits = __ballot(hit);
-                const uint32_t a = excl > t0 ? (excl - t0 < 64u ? excl - t0 : 64u) : 0u;
-                const uint32_t e = incl > t0 ? (incl - t0 < 64u ? incl - t0 : 64u) : 0u;
-                const unsigned long long upto_e = e >= 64u ? ~0ull : ((1ull << e) - 1ull);
-                const unsigned long long upto_a = a >= 64u ? ~0ull : ((1ull << a) - 1ull);
-                row_hits += (uint32_t)__popcll(hits & upto_e & ~upto_a);
+                row_hits += g.hits_of_step(__ballot(hit), t0 + 64u * (uint32_t)u);
             }
         }
-        if (COUNT && lane < BR_EPW && row_hits) atomicAdd(&counters[d], (unsigned long long)row_hits);
+        if (lane < BR_EPW && row_hits) atomicAdd(&counters[dbase + lane], (unsigned long long)row_hits);
     }
-    if (FILL) return;
     __syncthreads();
-    uint32_t* out = partial + (uint64_t)b * qi.nq + j0;
+    uint32_t* out = partial + (uint64_t)rw.b * qi.nq + rw.j0;
     for (uint32_t k = threadIdx.x; k < nj; k += BR_THREADS) out[k] = (s_slot[k >> 1] >> (16u * (k & 1u))) & 0xffffu;
     if (subcnt) {
         // postings this workgroup holds per sub-range: PARTS threads per sub-range, each sums its share of the words
@@ -285,11 +235,41 @@ __global__ __launch_bounds__(BR_THREADS) void build_range_kernel(QIndex qi, cons
             sum += (v & 0xffffu) + (v >> 16);
         }
         for (int off = PARTS / 2; off > 0; off >>= 1) sum += __shfl_down(sum, off, PARTS);
-        if (part == 0) subcnt[((uint64_t)r * BR_NSUB + sub) * B + b] = sum;
+        if (part == 0) subcnt[((uint64_t)rw.r * BR_NSUB + sub) * B + rw.b] = sum;
     }
 }
 
-// pass 2a with staging: the walk of build_range_kernel over the positions pass 1 left, but the workgroup moves through its rows in
+// Direct fill: one store per posting into its list, at partial[b][j] (+ post_off[j] unless partial already holds absolute slots:
+// post_off null) + the LDS cursor of j in this workgroup.  The query positions are the ones pass 1 left.
+__global__ __launch_bounds__(BR_THREADS) void build_range_fill_kernel(uint64_t nq, const uint64_t* __restrict__ offsets, uint64_t ndb,
+                                                          const uint32_t* __restrict__ bounds, uint32_t R, uint32_t B, uint64_t rows_per_block,
+                                                          const uint32_t* __restrict__ partial, const uint64_t* __restrict__ post_off,
+                                                          uint32_t* __restrict__ post_rows, const uint32_t* __restrict__ qpos) {
+    __shared__ uint32_t s_slot[BR_RANGE / 2];
+    RangeWork rw;
+    if (!range_begin(rw, s_slot, R, B, rows_per_block, ndb)) return;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t* part_b = partial + (uint64_t)rw.b * nq;
+    for (uint64_t dbase = rw.d_lo + (uint64_t)wave * BR_EPW; dbase < rw.d_hi; dbase += (BR_THREADS / 64) * BR_EPW) {
+        SliceGroup<BR_EPW> g;
+        range_group(g, offsets, ndb, bounds, rw.r, false, dbase, rw.d_hi, lane);
+        for (uint32_t t0 = 0; t0 < g.total; t0 += 64) {             // wave-uniform trip count (SliceGroup::at)
+            const uint32_t t = t0 + (uint32_t)lane;
+            int h;
+            const uint64_t at = g.at(t, h);
+            const uint32_t j = t < g.total ? qpos[at] : NONE32;
+            if (j != NONE32) {
+                const uint32_t k = j - (uint32_t)rw.j0;              // < BR_RANGE: the slice lies inside the range
+                const uint32_t sh = 16u * (k & 1u);
+                const uint32_t mine = (atomicAdd(&s_slot[k >> 1], 1u << sh) >> sh) & 0xffffu;
+                const uint64_t slot = post_off ? post_off[j] + part_b[j] : (uint64_t)part_b[j];
+                post_rows[slot + mine] = (uint32_t)(dbase + (uint64_t)h);
+            }
+        }
+    }
+}
+
+// pass 2a with staging: the walk of build_range_fill_kernel over the positions pass 1 left, but the workgroup moves through its rows in
 // chunks of 8 waves x 16 rows with all waves in step; an entry's final slot in its stream is reserved at once (an LDS
 // counter per stream), the entry itself waits in LDS -- stream k's entries of the chunk at s_stage[k][slot - chunk start]
 // -- and after the chunk every stream's part goes out with consecutive lanes (~80 entries = 330 bytes at C5).  An entry
@@ -307,67 +287,41 @@ __global__ __launch_bounds__(BR_THREADS) void build_partition_kernel(uint64_t nq
     constexpr int WAVES = BR_THREADS / 64;
     __shared__ uint32_t s_stage[BR_NSUB][PA_CAPS];
     __shared__ uint32_t s_gbase[BR_NSUB], s_gcur[BR_NSUB], s_cbase[BR_NSUB];
-    const uint32_t local = blockIdx.x % (8u * B);
-    const uint32_t r = (blockIdx.x / (8u * B)) * 8u + (local & 7u), b = local >> 3;
-    if (r >= R) return;
-    const uint64_t j0 = (uint64_t)r * BR_RANGE;
+    RangeWork rw;
+    if (!range_work(rw, R, B, rows_per_block, ndb)) return;
     (void)nq;
     for (int k = threadIdx.x; k < BR_NSUB; k += BR_THREADS) {
-        s_gbase[k] = inter_off[((uint64_t)r * BR_NSUB + k) * B + b];
+        s_gbase[k] = inter_off[((uint64_t)rw.r * BR_NSUB + k) * B + rw.b];
         s_gcur[k] = 0;
     }
-    const uint64_t d_lo = (uint64_t)b * rows_per_block;
-    const uint64_t d_hi = d_lo + rows_per_block < ndb ? d_lo + rows_per_block : ndb;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint64_t n_chunks = d_hi > d_lo ? (d_hi - d_lo + (uint64_t)(WAVES * BR_EPW) - 1) / (WAVES * BR_EPW) : 0;
+    const uint64_t n_chunks = rw.d_hi > rw.d_lo ? (rw.d_hi - rw.d_lo + (uint64_t)(WAVES * BR_EPW) - 1) / (WAVES * BR_EPW) : 0;
     for (uint64_t chunk = 0; chunk < n_chunks; ++chunk) {
         __syncthreads();                                            // the previous chunk is flushed (and, first time, s_gbase is set)
         for (int k = threadIdx.x; k < BR_NSUB; k += BR_THREADS) s_cbase[k] = s_gcur[k];
         __syncthreads();
-        const uint64_t dbase = d_lo + (chunk * WAVES + (uint64_t)wave) * BR_EPW;
-        if (dbase < d_hi) {
-            uint64_t lo = 0;
-            uint32_t n = 0;
-            const uint64_t d = dbase + lane;
-            if (lane < BR_EPW && d < d_hi) {
-                const uint32_t a = bounds[(uint64_t)r * ndb + d], e = bounds[(uint64_t)(r + 1) * ndb + d];
-                lo = offsets[d] + a;
-                n = e - a;
-            }
-            uint32_t incl = n;
-#pragma unroll
-            for (int sft = 1; sft < BR_EPW; sft <<= 1) {
-                const uint32_t v = __shfl_up(incl, sft);
-                if (lane >= sft) incl += v;
-            }
-            const uint32_t total = __shfl(incl, BR_EPW - 1);
-            uint32_t bound[BR_EPW - 1];
-#pragma unroll
-            for (int k = 0; k < BR_EPW - 1; ++k) bound[k] = __shfl(incl, k);
-            const uint32_t excl = incl - n;
-            const uint32_t lo_lo = (uint32_t)lo, lo_hi = (uint32_t)(lo >> 32);
-            for (uint32_t t0 = 0; t0 < total; t0 += 64 * PA_AHEAD) {   // PA_AHEAD steps of loads in flight (see pass 1)
+        const uint64_t dbase = rw.d_lo + (chunk * WAVES + (uint64_t)wave) * BR_EPW;
+        if (dbase < rw.d_hi) {
+            SliceGroup<BR_EPW> g;
+            range_group(g, offsets, ndb, bounds, rw.r, false, dbase, rw.d_hi, lane);
+            for (uint32_t t0 = 0; t0 < g.total; t0 += 64 * PA_AHEAD) {   // PA_AHEAD steps of loads in flight (see pass 1)
                 uint32_t jv[PA_AHEAD];
                 int hv[PA_AHEAD];
 #pragma unroll
                 for (int u = 0; u < PA_AHEAD; ++u) {
                     const uint32_t t = t0 + 64u * (uint32_t)u + (uint32_t)lane;
-                    const bool ok = t < total;
-                    const uint32_t tt = ok ? t : total - 1;
-                    int h = 0;
-#pragma unroll
-                    for (int k = 0; k < BR_EPW - 1; ++k) h += tt >= bound[k];
-                    const uint64_t start = ((uint64_t)(uint32_t)__shfl((int)lo_hi, h) << 32) | (uint32_t)__shfl((int)lo_lo, h);
-                    const uint32_t first = (uint32_t)__shfl((int)excl, h);
+                    const bool ok = t < g.total;
+                    int h;
+                    const uint64_t at = g.at(ok ? t : g.total - 1, h);
                     hv[u] = ok ? h : -1;
-                    jv[u] = __builtin_nontemporal_load(&qpos[start + (tt - first)]);   // read once: streaming load
+                    jv[u] = __builtin_nontemporal_load(&qpos[at]);   // read once: streaming load
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int u = 0; u < PA_AHEAD; ++u) {
                     const uint32_t j = hv[u] >= 0 ? jv[u] : NONE32;
                     if (j != NONE32) {
-                        const uint32_t k = j - (uint32_t)j0;
+                        const uint32_t k = j - (uint32_t)rw.j0;
                         const uint32_t sub = k >> BR_SUB_BITS;
                         const uint32_t entry = ((uint32_t)(dbase + (uint64_t)hv[u]) << BR_SUB_BITS) | (k & (BR_SUB - 1));
                         const uint32_t at = atomicAdd(&s_gcur[sub], 1u);                   // final slot in this workgroup's stream
@@ -402,6 +356,45 @@ constexpr int BR_ORD_NB = 8;
 // A window's postings arrive as `n_sub` runs, run i holding those of row block i / m (m = 1: one run per block, laid out by
 // pass 2a; m > 1: one run per workgroup of the lean pass 1, m consecutive workgroups to a block), (start, length) in
 // inter_off / subcnt [window][n_sub].
+// Workgroup (window w, group g) of pass 2b and of the run count, from blockIdx.x, and what the group owns.
+// j0, nl: the window's first list (query position) and their number; [b_lo, b_hi): the group's row blocks; i_lo, n_runs: its runs in
+// the window's directory, <= 64 (enforced by the host)
+struct WindowWork { uint32_t w, nl, b_lo, b_hi, i_lo, n_runs; uint64_t j0; };
+__device__ __forceinline__ bool window_work(WindowWork& ww, uint64_t nq, uint32_t n_windows, uint32_t B, uint32_t n_sub, uint32_t m) {
+    const uint32_t q = blockIdx.x >> 3, x = blockIdx.x & 7u;
+    const uint32_t g = q % BR_GROUPS;
+    ww.w = (q / BR_GROUPS) * 8u + x;
+    if (ww.w >= n_windows) return false;
+    ww.j0 = (uint64_t)ww.w * BR_SUB;
+    if (ww.j0 >= nq) return false;
+    ww.nl = (uint32_t)(nq - ww.j0 < (uint64_t)BR_SUB ? nq - ww.j0 : (uint64_t)BR_SUB);
+    const uint32_t per = (B + BR_GROUPS - 1) / BR_GROUPS;
+    ww.b_lo = g * per;
+    ww.b_hi = ww.b_lo + per < B ? ww.b_lo + per : B;
+    if (ww.b_lo >= B) return false;
+    ww.i_lo = ww.b_lo * m;
+    const uint32_t i_hi = ww.b_hi * m < n_sub ? ww.b_hi * m : n_sub;
+    ww.n_runs = i_hi > ww.i_lo ? i_hi - ww.i_lo : 0u;
+    return true;
+}
+// The group's runs as one list of entries: s_pre[i] = entries before run i, s_pre[n_runs] = all of them, s_src[i] = where run i
+// starts in `inter`.  Wave 0 asks for all lengths at once and takes their prefix; a barrier of the caller's publishes the arrays.
+__device__ __forceinline__ void run_directory(const WindowWork& ww, uint32_t n_sub, const uint32_t* __restrict__ dir_start,
+                                              const uint32_t* __restrict__ dir_len, uint32_t (&s_pre)[BR_GROUPS * 8 + 1],
+                                              uint32_t (&s_src)[BR_GROUPS * 8]) {
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        const bool ok = (uint32_t)tid < ww.n_runs;
+        const uint32_t len = ok ? dir_len[(uint64_t)ww.w * n_sub + ww.i_lo + tid] : 0u;
+        const uint32_t incl = wave_incl_sum<64>(len, tid);
+        if (ok) {
+            s_pre[tid] = incl - len;
+            s_src[tid] = dir_start[(uint64_t)ww.w * n_sub + ww.i_lo + tid];
+        }
+        if (tid == 63) s_pre[ww.n_runs] = incl;
+    }
+}
+
 template <bool ORDERED>
 __global__ __launch_bounds__(512) void build_scatter_kernel(uint64_t nq, uint32_t n_windows, uint32_t B,
                                                             const uint32_t* __restrict__ partial,
@@ -415,38 +408,16 @@ __global__ __launch_bounds__(512) void build_scatter_kernel(uint64_t nq, uint32_
     __shared__ uint32_t s_cnt[NK], s_start[NK + 1], s_fill[NK], s_cur[BR_SUB];
     __shared__ uint32_t s_pre[BR_GROUPS * 8 + 1], s_src[BR_GROUPS * 8];     // flat entry index -> region (at most 64 row blocks per group)
     __shared__ uint32_t s_wsum[8];
-    const uint32_t q = blockIdx.x >> 3, x = blockIdx.x & 7u;
-    const uint32_t w = (q / BR_GROUPS) * 8u + x, g = q % BR_GROUPS;
-    if (w >= n_windows) return;
-    const uint64_t j0 = (uint64_t)w * BR_SUB;
-    if (j0 >= nq) return;
-    const uint32_t nl = (uint32_t)(nq - j0 < (uint64_t)BR_SUB ? nq - j0 : (uint64_t)BR_SUB);
-    const uint32_t per = (B + BR_GROUPS - 1) / BR_GROUPS;
-    const uint32_t b_lo = g * per, b_hi = b_lo + per < B ? b_lo + per : B;
-    if (b_lo >= B) return;
-    const uint32_t i_lo = b_lo * m, i_hi = b_hi * m < n_sub ? b_hi * m : n_sub;
-    const uint32_t nb = i_hi > i_lo ? i_hi - i_lo : 0u;               // runs of this group: <= 64 (enforced by the host)
-    const uint64_t wbase = post_off[j0];
+    WindowWork ww;
+    if (!window_work(ww, nq, n_windows, B, n_sub, m)) return;
+    const uint64_t j0 = ww.j0, wbase = post_off[j0];
+    const uint32_t nl = ww.nl;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (uint32_t k = tid; k < (uint32_t)BR_SUB; k += blockDim.x)
-        s_cur[k] = k < nl ? (uint32_t)(post_off[j0 + k] - wbase) + partial[(uint64_t)b_lo * nq + j0 + k] : 0u;
-    if (tid < 64) {                                                  // the runs' lengths, all loads at once, and their prefix
-        const bool ok = (uint32_t)tid < nb;
-        const uint32_t len = ok ? subcnt[(uint64_t)w * n_sub + i_lo + tid] : 0u;
-        uint32_t incl = len;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(incl, d);
-            if (lane >= d) incl += o;
-        }
-        if (ok) {
-            s_pre[tid] = incl - len;
-            s_src[tid] = inter_off[(uint64_t)w * n_sub + i_lo + tid];
-        }
-        if (tid == 63) s_pre[nb] = incl;
-    }
+        s_cur[k] = k < nl ? (uint32_t)(post_off[j0 + k] - wbase) + partial[(uint64_t)ww.b_lo * nq + j0 + k] : 0u;
+    run_directory(ww, n_sub, inter_off, subcnt, s_pre, s_src);
     __syncthreads();
-    const uint32_t total = s_pre[nb];
+    const uint32_t total = s_pre[ww.n_runs];
     for (uint32_t f0 = 0; f0 < total; f0 += BR_SORT_CAP) {
         const uint32_t f1 = f0 + BR_SORT_CAP < total ? f0 + BR_SORT_CAP : total;
         for (uint32_t k = tid; k < (uint32_t)NK; k += blockDim.x) s_cnt[k] = 0;
@@ -484,12 +455,7 @@ __global__ __launch_bounds__(512) void build_scatter_kernel(uint64_t nq, uint32_
             static_assert(!ORDERED || NK == 4 * 512, "");
             const uint32_t c0 = s_cnt[4 * tid], c1 = s_cnt[4 * tid + 1], c2 = s_cnt[4 * tid + 2], c3 = s_cnt[4 * tid + 3];
             const uint32_t mine = c0 + c1 + c2 + c3;
-            uint32_t incl = mine;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t o = __shfl_up(incl, d);
-                if (lane >= d) incl += o;
-            }
+            const uint32_t incl = wave_incl_sum<64>(mine, lane);
             if (lane == 63) s_wsum[wave] = incl;
             __syncthreads();
             uint32_t before = 0;
@@ -504,12 +470,7 @@ __global__ __launch_bounds__(512) void build_scatter_kernel(uint64_t nq, uint32_
             uint32_t carry = 0;
             for (int base = 0; base < BR_SUB; base += 64) {
                 const uint32_t v = s_cnt[base + lane];
-                uint32_t incl = v;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const uint32_t o = __shfl_up(incl, d);
-                    if (lane >= d) incl += o;
-                }
+                const uint32_t incl = wave_incl_sum<64>(v, lane);
                 s_start[base + lane] = carry + incl - v;
                 s_fill[base + lane] = carry + incl - v;
                 carry += __shfl(incl, 63);
@@ -544,37 +505,16 @@ __global__ __launch_bounds__(512) void build_count_runs_kernel(uint64_t nq, uint
                                                                const uint32_t* __restrict__ dir_start, const uint32_t* __restrict__ dir_len,
                                                                const uint32_t* __restrict__ inter, uint32_t* __restrict__ partial) {
     __shared__ uint32_t s_cnt[BR_SUB * BR_ORD_NB];
-    const uint32_t q = blockIdx.x >> 3, x = blockIdx.x & 7u;
-    const uint32_t w = (q / BR_GROUPS) * 8u + x, g = q % BR_GROUPS;
-    if (w >= n_windows) return;
-    const uint64_t j0 = (uint64_t)w * BR_SUB;
-    if (j0 >= nq) return;
-    const uint32_t nl = (uint32_t)(nq - j0 < (uint64_t)BR_SUB ? nq - j0 : (uint64_t)BR_SUB);
-    const uint32_t per = (B + BR_GROUPS - 1) / BR_GROUPS;              // <= BR_ORD_NB (the host checks)
-    const uint32_t b_lo = g * per, b_hi = b_lo + per < B ? b_lo + per : B;
-    if (b_lo >= B) return;
-    const uint32_t i_lo = b_lo * m, i_hi = b_hi * m < n_sub ? b_hi * m : n_sub;
-    const uint32_t nreg = i_hi > i_lo ? i_hi - i_lo : 0u;              // <= 64
-    const int tid = threadIdx.x, lane = tid & 63;
+    WindowWork ww;                                                     // (row blocks per group <= BR_ORD_NB: the host checks)
+    if (!window_work(ww, nq, n_windows, B, n_sub, m)) return;
+    const uint64_t j0 = ww.j0;
+    const uint32_t nl = ww.nl, b_lo = ww.b_lo, b_hi = ww.b_hi, i_lo = ww.i_lo;
+    const int tid = threadIdx.x;
     __shared__ uint32_t s_pre[BR_GROUPS * 8 + 1], s_src[BR_GROUPS * 8];
     for (uint32_t k = tid; k < (uint32_t)(BR_SUB * BR_ORD_NB); k += blockDim.x) s_cnt[k] = 0;
-    if (tid < 64) {
-        const bool ok = (uint32_t)tid < nreg;
-        const uint32_t len = ok ? dir_len[(uint64_t)w * n_sub + i_lo + tid] : 0u;
-        uint32_t incl = len;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(incl, d);
-            if (lane >= d) incl += o;
-        }
-        if (ok) {
-            s_pre[tid] = incl - len;
-            s_src[tid] = dir_start[(uint64_t)w * n_sub + i_lo + tid];
-        }
-        if (tid == 63) s_pre[nreg] = incl;
-    }
+    run_directory(ww, n_sub, dir_start, dir_len, s_pre, s_src);
     __syncthreads();
-    const uint32_t total = s_pre[nreg];
+    const uint32_t total = s_pre[ww.n_runs];
     constexpr int PER = 8;                                              // entries a thread has in flight
     for (uint32_t f0 = 0; f0 < total; f0 += 512u * PER) {
         uint32_t ent[PER], blk[PER];
@@ -696,6 +636,43 @@ hipError_t gather_build(GatherDev& g, hipStream_t stream) {
     return e;
 }
 
+// How every builder sizes the index: pass 1 leaves post_cnt[j] = postings of query hash j (post_cnt[nq] = 0); their exclusive
+// scan is post_off, whose last entry -- the number of postings -- starts its way to the host ...
+// (the range builders first merge their per-block counts partial[B][nq] into post_cnt)
+struct PostScan { unsigned long long* cnt; void* tmp; size_t bytes; };
+static hipError_t scan_postings(GatherDev& g, PostScan& ps, uint32_t* partial, uint64_t B, hipStream_t stream) {
+    if (partial) {
+        hipLaunchKernelGGL(build_merge_counts_kernel, dim3((unsigned)((g.nq + 256) / 256)), dim3(256), 0, stream, partial, (uint32_t)B, g.nq, ps.cnt);
+        SMG_TRY(hipGetLastError());
+    }
+    SMG_TRY(rocprim::exclusive_scan(ps.tmp, ps.bytes, (uint64_t*)ps.cnt, g.post_off, (uint64_t)0, (size_t)(g.nq + 1),
+                                    rocprim::plus<uint64_t>(), stream));
+    return hipMemcpyAsync(&g.pinned[8], g.post_off + g.nq, 8, hipMemcpyDeviceToHost, stream);
+}
+// ... and once a synchronisation has brought it back, the rows are allocated
+static hipError_t size_postings(GatherDev& g) {
+    g.npairs = g.pinned[8];
+    return own_alloc(g, &g.post_rows, (g.npairs + 4) * 4);
+}
+// where every row block's run begins and ends inside every list, for the resident loop: block_pre [nq][B + 1]
+static hipError_t block_pre_table(GatherDev& g, const uint32_t* partial, uint64_t B, uint64_t rows_per_block, hipStream_t stream) {
+    SMG_TRY(own_alloc(g, &g.block_pre, (g.nq * (B + 1) + 4) * 4));
+    hipLaunchKernelGGL(build_bounds_table_kernel, dim3((unsigned)((g.nq + 63) / 64)), dim3(256), 0, stream, partial, g.nq, (uint32_t)B,
+                       (const uint64_t*)g.post_off, g.block_pre);
+    SMG_TRY(hipGetLastError());
+    g.block_B = (uint32_t)B;
+    g.block_rows = (uint32_t)rows_per_block;
+    return hipSuccess;
+}
+// pass 2b over every window; ordered: row-block runs inside every list (what the persistent loop needs)
+struct RunDir { const uint32_t *len, *start, *inter; uint64_t n_sub, m; };   // [window][n_sub] runs of `inter`, m consecutive ones to a row block
+static hipError_t scatter_launch(GatherDev& g, bool ordered, uint32_t n_windows, uint64_t B, const uint32_t* partial, const RunDir& runs, hipStream_t stream) {
+    auto* kernel = ordered ? build_scatter_kernel<true> : build_scatter_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n_windows + 7) / 8 * 8 * BR_GROUPS)), dim3(512), 0, stream, g.nq, n_windows, (uint32_t)B,
+                       partial, (const uint64_t*)g.post_off, runs.len, runs.start, runs.inter, g.post_rows, (uint32_t)runs.n_sub, (uint32_t)runs.m);
+    return hipGetLastError();
+}
+
 static hipError_t gather_build_body(GatherDev& g, hipStream_t stream) {
     if (g.nq >= NONE32) return hipErrorInvalidValue;             // query positions are u32
     if (g.ndb >= NONE32) return hipErrorInvalidValue;            // row ids are u32
@@ -755,7 +732,7 @@ static hipError_t gather_build_body(GatherDev& g, hipStream_t stream) {
     SMG_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, (uint64_t*)post_cnt, g.post_off, (uint64_t)0, (size_t)nq1,
                                     rocprim::plus<uint64_t>(), stream));
     SMG_TRY(scan_tmp_b.get(scan_bytes + 256, stream));
-    void* scan_tmp = scan_tmp_b.p;
+    PostScan scan{post_cnt, scan_tmp_b.p, scan_bytes};
     SMG_TRY(own_alloc(g, &g.qpos, (total + 4) * 4));                // kept: apply reads it instead of looking hashes up again
     // Small problems: one atomic per element is cheapest.  Large ones: range-partitioned, histogram and cursors in LDS.
     const char* force = getenv("SMG_GATHER_BUILD");
@@ -775,13 +752,10 @@ static hipError_t gather_build_body(GatherDev& g, hipStream_t stream) {
         hipLaunchKernelGGL(build_count_kernel, dim3(blocks_for_rows(g.ndb)), dim3(256), 0, stream, qi, g.hashes, g.offsets,
                            g.ndb, qpos, post_cnt, g.counters);
         SMG_TRY(hipGetLastError());
-        SMG_TRY(rocprim::exclusive_scan(scan_tmp, scan_bytes, (uint64_t*)post_cnt, g.post_off, (uint64_t)0, (size_t)nq1,
-                                        rocprim::plus<uint64_t>(), stream));
-        SMG_TRY(hipMemcpyAsync(&g.pinned[8], g.post_off + g.nq, 8, hipMemcpyDeviceToHost, stream));
+        SMG_TRY(scan_postings(g, scan, nullptr, 0, stream));
         SMG_TRY(hipMemcpyAsync(post_cnt, g.post_off, nq1 * 8, hipMemcpyDeviceToDevice, stream));   // cursors
         SMG_TRY(timed_sync(g, stream));                           // synchronisation 2 of 2
-        g.npairs = g.pinned[8];
-        SMG_TRY(own_alloc(g, &g.post_rows, (g.npairs + 4) * 4));
+        SMG_TRY(size_postings(g));
         hipLaunchKernelGGL(build_fill_kernel, dim3(blocks_for_rows(g.ndb)), dim3(256), 0, stream, qpos, g.offsets, g.ndb,
                            post_cnt, g.post_rows);
         SMG_TRY(hipGetLastError());
@@ -798,7 +772,7 @@ static hipError_t gather_build_body(GatherDev& g, hipStream_t stream) {
         // flows through LDS in ranges and every workgroup walks its own rows once -- no lookups in L2.  It wants a few hundred rows
         // per CU, a query without the hash 2^64 - 1, ranges that fit its LDS (one more synchronisation: the widest range's size
         // comes back first), and it works per WORKGROUP: a row block of the builder becomes `m_sub` consecutive workgroups of `rpw`
-        // rows.  Anything it cannot take goes to pass 1 by lookups in L2 (build_range_kernel<0>); a forced form that cannot run is
+        // rows.  Anything it cannot take goes to pass 1 by lookups in L2 (build_range_count_kernel); a forced form that cannot run is
         // an error.  (Round 4 kept a third form between the two -- the lean kernel counting only, SMG_GATHER_PASS1=lean -- as the
         // fallback for queries whose ranges do not fit the staging form's table slice; the lookups take those now.)
         const char* pass1_s = getenv("SMG_GATHER_PASS1");
@@ -869,11 +843,7 @@ static hipError_t gather_build_body(GatherDev& g, hipStream_t stream) {
                                (uint32_t)m_sub, (const uint32_t*)inter_off_b.as<uint32_t>(), (const uint32_t*)subcnt_b.as<uint32_t>(),
                                (const uint32_t*)inter_b.as<uint32_t>(), partial);
             SMG_TRY(hipGetLastError());
-            hipLaunchKernelGGL(build_merge_counts_kernel, dim3((unsigned)((nq1 + 255) / 256)), dim3(256), 0, stream, partial, (uint32_t)B, g.nq, post_cnt);
-            SMG_TRY(hipGetLastError());
-            SMG_TRY(rocprim::exclusive_scan(scan_tmp, scan_bytes, (uint64_t*)post_cnt, g.post_off, (uint64_t)0, (size_t)nq1,
-                                            rocprim::plus<uint64_t>(), stream));
-            SMG_TRY(hipMemcpyAsync(&g.pinned[8], g.post_off + g.nq, 8, hipMemcpyDeviceToHost, stream));
+            SMG_TRY(scan_postings(g, scan, partial, B, stream));
             g.pinned[10] = 0;
             SMG_TRY(hipMemcpyAsync(&g.pinned[10], misc_b.p, 8, hipMemcpyDeviceToHost, stream));
             SMG_TRY(timed_sync(g, stream));                               // synchronisation 3 of 3
@@ -883,20 +853,10 @@ static hipError_t gather_build_body(GatherDev& g, hipStream_t stream) {
                 stage1 = false;
                 SMG_TRY(hipMemsetAsync(g.counters, 0, (g.ndb + 1) * 8, stream));
             } else {
-                g.npairs = g.pinned[8];
-                SMG_TRY(own_alloc(g, &g.post_rows, (g.npairs + 4) * 4));
-                hipLaunchKernelGGL(build_scatter_kernel<true>, dim3(win_grid), dim3(512), 0, stream, g.nq, n_windows, (uint32_t)B,
-                                   (const uint32_t*)partial, (const uint64_t*)g.post_off, (const uint32_t*)subcnt_b.as<uint32_t>(),
-                                   (const uint32_t*)inter_off_b.as<uint32_t>(), (const uint32_t*)inter_b.as<uint32_t>(), g.post_rows, (uint32_t)n_sub,
-                                   (uint32_t)m_sub);
-                SMG_TRY(hipGetLastError());
-                SMG_TRY(own_alloc(g, &g.block_pre, (g.nq * (B + 1) + 4) * 4));
-                hipLaunchKernelGGL(build_bounds_table_kernel, dim3((unsigned)((g.nq + 63) / 64)), dim3(256), 0, stream, (const uint32_t*)partial,
-                                   g.nq, (uint32_t)B, (const uint64_t*)g.post_off, g.block_pre);
-                SMG_TRY(hipGetLastError());
-                g.block_B = (uint32_t)B;
-                g.block_rows = (uint32_t)rows_per_block;
-                return hipSuccess;
+                SMG_TRY(size_postings(g));
+                const RunDir runs{/*len*/ subcnt_b.as<uint32_t>(), /*start*/ inter_off_b.as<uint32_t>(), inter_b.as<uint32_t>(), n_sub, m_sub};
+                SMG_TRY(scatter_launch(g, true, n_windows, B, partial, runs, stream));
+                return block_pre_table(g, partial, B, rows_per_block, stream);
             }
         }
         SMG_TRY(bounds_b.get(((uint64_t)R + 1) * g.ndb * 4, stream));
@@ -914,16 +874,10 @@ static hipError_t gather_build_body(GatherDev& g, hipStream_t stream) {
             SMG_TRY(hipMemsetAsync(subcnt, 0, (uint64_t)n_windows * B * 4, stream));   // ranges past R launch nothing
         }
         const unsigned range_grid = (unsigned)(((R + 7) / 8) * 8 * B);
-        hipLaunchKernelGGL(build_range_kernel<0>, dim3(range_grid), dim3(BR_THREADS), 0, stream, qi, g.hashes, g.offsets,
-                           g.ndb, bounds, R, (uint32_t)B, rows_per_block, partial, (const uint64_t*)nullptr, (uint32_t*)nullptr,
-                           g.counters, g.qpos, subcnt);
+        hipLaunchKernelGGL(build_range_count_kernel, dim3(range_grid), dim3(BR_THREADS), 0, stream, qi, g.hashes, g.offsets,
+                           g.ndb, (const uint32_t*)bounds, R, (uint32_t)B, rows_per_block, partial, g.counters, g.qpos, subcnt);
         SMG_TRY(hipGetLastError());
-        hipLaunchKernelGGL(build_merge_counts_kernel, dim3((unsigned)((nq1 + 255) / 256)), dim3(256), 0, stream, partial,
-                           (uint32_t)B, g.nq, post_cnt);
-        SMG_TRY(hipGetLastError());
-        SMG_TRY(rocprim::exclusive_scan(scan_tmp, scan_bytes, (uint64_t*)post_cnt, g.post_off, (uint64_t)0, (size_t)nq1,
-                                        rocprim::plus<uint64_t>(), stream));
-        SMG_TRY(hipMemcpyAsync(&g.pinned[8], g.post_off + g.nq, 8, hipMemcpyDeviceToHost, stream));
+        SMG_TRY(scan_postings(g, scan, partial, B, stream));
         if (staged) {
             // region of (window, row block) in the intermediate buffer: exclusive scan of the exact counts, window-major
             size_t lay_bytes = 0;
@@ -932,8 +886,7 @@ static hipError_t gather_build_body(GatherDev& g, hipStream_t stream) {
             SMG_TRY(rocprim::exclusive_scan(lay_tmp_b.p, lay_bytes, subcnt, inter_off, 0u, (size_t)n_windows * B, rocprim::plus<uint32_t>(), stream));
         }
         SMG_TRY(timed_sync(g, stream));                           // the last synchronisation (2 of 2, or 3 of 3 with the lean pass 1)
-        g.npairs = g.pinned[8];
-        SMG_TRY(own_alloc(g, &g.post_rows, (g.npairs + 4) * 4));
+        SMG_TRY(size_postings(g));
         const uint64_t inter_words = g.npairs + 4;
         if (staged && (inter_words >= 0xffffffffull || B > 512)) staged = false;
         if (staged) {
@@ -945,24 +898,8 @@ static hipError_t gather_build_body(GatherDev& g, hipStream_t stream) {
             SMG_TRY(hipGetLastError());
             const uint32_t per = (uint32_t)((B + BR_GROUPS - 1) / BR_GROUPS);
             const bool ordered = per <= (uint32_t)BR_ORD_NB;            // row-block runs inside every list (persistent loop)
-            if (ordered)
-                hipLaunchKernelGGL(build_scatter_kernel<true>, dim3((unsigned)((n_windows + 7) / 8 * 8 * BR_GROUPS)), dim3(512), 0, stream, g.nq,
-                                   n_windows, (uint32_t)B, (const uint32_t*)partial, (const uint64_t*)g.post_off, (const uint32_t*)subcnt,
-                                   (const uint32_t*)inter_off, (const uint32_t*)inter, g.post_rows, (uint32_t)B, 1u);
-            else
-                hipLaunchKernelGGL(build_scatter_kernel<false>, dim3((unsigned)((n_windows + 7) / 8 * 8 * BR_GROUPS)), dim3(512), 0, stream, g.nq,
-                                   n_windows, (uint32_t)B, (const uint32_t*)partial, (const uint64_t*)g.post_off, (const uint32_t*)subcnt,
-                                   (const uint32_t*)inter_off, (const uint32_t*)inter, g.post_rows, (uint32_t)B, 1u);
-            SMG_TRY(hipGetLastError());
-            if (ordered && g.npairs < 0xffffffffull) {
-                // where every row block's run begins and ends inside every list, for the resident loop: [nq][B + 1]
-                SMG_TRY(own_alloc(g, &g.block_pre, (g.nq * (B + 1) + 4) * 4));
-                hipLaunchKernelGGL(build_bounds_table_kernel, dim3((unsigned)((g.nq + 63) / 64)), dim3(256), 0, stream, (const uint32_t*)partial,
-                                   g.nq, (uint32_t)B, (const uint64_t*)g.post_off, g.block_pre);
-                SMG_TRY(hipGetLastError());
-                g.block_B = (uint32_t)B;
-                g.block_rows = (uint32_t)rows_per_block;
-            }
+            SMG_TRY(scatter_launch(g, ordered, n_windows, B, partial, RunDir{/*len*/ subcnt, /*start*/ inter_off, inter, B, 1}, stream));
+            if (ordered && g.npairs < 0xffffffffull) SMG_TRY(block_pre_table(g, partial, B, rows_per_block, stream));
         } else {
             const bool absolute = g.npairs < 0xffffffffull;
             if (absolute) {
@@ -970,10 +907,9 @@ static hipError_t gather_build_body(GatherDev& g, hipStream_t stream) {
                                    (uint32_t)B, g.nq, (const uint64_t*)g.post_off);
                 SMG_TRY(hipGetLastError());
             }
-            hipLaunchKernelGGL(build_range_kernel<1>, dim3(range_grid), dim3(BR_THREADS), 0, stream, qi, g.hashes, g.offsets,
-                               g.ndb, bounds, R, (uint32_t)B, rows_per_block, partial,
-                               absolute ? (const uint64_t*)nullptr : (const uint64_t*)g.post_off, g.post_rows, g.counters, g.qpos,
-                               (uint32_t*)nullptr);
+            hipLaunchKernelGGL(build_range_fill_kernel, dim3(range_grid), dim3(BR_THREADS), 0, stream, g.nq, g.offsets, g.ndb,
+                               (const uint32_t*)bounds, R, (uint32_t)B, rows_per_block, (const uint32_t*)partial,
+                               absolute ? (const uint64_t*)nullptr : (const uint64_t*)g.post_off, g.post_rows, (const uint32_t*)g.qpos);
             SMG_TRY(hipGetLastError());
         }
     }

@@ -22,7 +22,7 @@ namespace smg {
 constexpr int BR_SUB = 256;
 constexpr int BR_SUB_BITS = 8;
 
-// gather.hip: T[b] = first position of the sorted query with Q >= b << shift, b = 0 .. buckets (qindex_core.hpp: qindex_geometry)
+// gather_build.hip: T[b] = first position of the sorted query with Q >= b << shift, b = 0 .. buckets (qindex_core.hpp: qindex_geometry)
 hipError_t qtable_launch(const uint64_t* Q, uint64_t nq, uint32_t shift, uint32_t buckets, uint32_t* table, hipStream_t stream);
 
 // overlap.hip: the builder's pass 1 + 2a through the lean streaming kernel's staging form
@@ -51,8 +51,6 @@ __device__ __forceinline__ unsigned long long wave_max(unsigned long long k) {
 
 static inline QIndex qindex_of(const GatherDev& g) { return QIndex{g.q_padded, g.nq, g.q_table, g.q_shift, g.q_max, g.q_rec}; }
 
-
-
 // Owned buffers and build scratch come from the arena (arena.hpp): blocks the library keeps between builds, so that a
 // rebuild of the same shape makes no driver call.  (Round 2 used hipMallocAsync with a raised release threshold; on the
 // benchmark host that still cost 175 ms per build against 6.9 ms of kernels -- VERDICT r02.)
@@ -71,6 +69,5 @@ static inline hipError_t timed_sync(GatherDev& g, hipStream_t stream) {
     g.build_syncs++;
     return e;
 }
-
 
 }  // namespace smg

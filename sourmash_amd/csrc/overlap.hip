@@ -19,6 +19,7 @@
 #include "wavemask.hpp"
 #include "qindex.hpp"
 #include "gather_parts.hpp"
+#include "slice_walk.hpp"
 
 namespace smg {
 
@@ -308,12 +309,7 @@ void overlap_lean_kernel(const uint64_t* __restrict__ Q, const uint32_t* __restr
             const uint32_t nw = (done_cnt + (uint32_t)BR_SUB - 1) >> BR_SUB_BITS;        // windows of the range (<= LEAN_NW)
             uint32_t have = (uint32_t)lane < nw ? s_wcur[lane] : 0u;
             if (have > (uint32_t)LEAN_CAPW) { atomicOr(&sa.misc[1], 1u); have = LEAN_CAPW; }
-            uint32_t incl = have;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t o = __shfl_up(incl, d);
-                if (lane >= d) incl += o;
-            }
+            const uint32_t incl = wave_incl_sum<64>(have, lane);
             const uint32_t total = __shfl(incl, 63);
             uint32_t base = 0;
             if (lane == 0 && total) base = atomicAdd(&sa.misc[0], total);

@@ -183,15 +183,14 @@ __global__ __launch_bounds__(256) void overlap_vector_kernel(const QIndexHeader*
     }
 }
 
-// packed arg-max with the reference tie-break (highest count, then lowest index):
-// key = (count << 32) | ~index  (counts < 2^32), reduced with max.
+// packed arg-max with the reference tie-break (highest count, then lowest index): gather_key (gather_key.hpp, through gather_api.hpp), reduced with max.
 __global__ __launch_bounds__(256) void argmax_kernel(const unsigned long long* __restrict__ overlap, uint64_t ndb,
                                                      uint64_t index_base, unsigned long long* __restrict__ best) {
     unsigned long long k = 0;
     for (uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; d < ndb; d += (uint64_t)gridDim.x * blockDim.x) {
         const unsigned long long c = overlap[d];
         if (c) {
-            const unsigned long long key = (c << 32) | (0xffffffffull & ~(unsigned long long)(index_base + d));
+            const unsigned long long key = gather_key(c, index_base + d);
             k = key > k ? key : k;
         }
     }

@@ -559,6 +559,13 @@ def _index_builder_cases():
         [np.concatenate([crowded + np.arange(2000, dtype=np.uint64), np.uint64(2**50) + np.arange(5, dtype=np.uint64) * np.uint64(2**45)]),
          np.concatenate([crowded + np.arange(0, 2000, 2, dtype=np.uint64), np.array([2**55], dtype=np.uint64)])] * 3,
     ]
+    # one row short of a wave's group of 16 slices, exactly one group, one row into the next (csrc/slice_walk.hpp); ragged rows
+    # over a small pool, so that the rows share hashes, with an empty row and a row of one hash among them
+    for n_rows in (15, 16, 17):
+        rows = [rng.choice(pool[:400], size=int(rng.integers(1, 200)), replace=False) for _ in range(n_rows)]
+        rows[2] = np.array([], dtype=np.uint64)
+        rows[n_rows - 1] = pool[:1].copy()
+        corner_sets.append(rows)
     for sk3 in corner_sets:
         sk3 = [np.unique(r) for r in sk3]
         wc3, wj3 = oracle.compare_all_pairs(*oracle.make_csr(sk3), nthreads=2)
