@@ -423,11 +423,75 @@ SMG_HD void store_chunk(uint32_t* dst, const uint32_t* w) {      // dst is 16-by
 // byte, and *s_dirty set where a staged byte is not ACGT (the caller has zeroed it in front of the barrier).  The unstaged forms of
 // sketch_dna_kernel and hll_dna_kernel keep the unstaged loop inline, for their registers' sake: sketch_kernel.hpp, hll_kernel.hpp.
 // n_chunks (<= IN_CHUNKS, which sizes the arrays): the chunks of this launch's tile where its rounds are a run-time value.
-template <int IN_CHUNKS, bool STAGED, int BLOCK>
+//
+// BATCH (staged form, a caller's choice per instantiation): a tile of all IN_CHUNKS chunks that lies wholly inside the buffer
+// (stage_batch_ok) is staged by stage_lane_batched -- a lane's loads all issued first, then the per-byte work and the stores in
+// load order -- so that a tile pays one round trip to memory, not one per trip of the loop below.  Every other tile -- the last
+// one, the first one behind an alignment prefix, and every tile of a launch that walks fewer rounds than IN_CHUNKS was sized
+// for (n_chunks < IN_CHUNKS: whole trips of the batch would serve no chunk) -- takes the loop, which keeps the one
+// implementation of the zero fill and the prefix blanking.  The choice is the same for every lane of the workgroup.  On the
+// host the function stages all chunks by the loop, whatever BATCH.
+SMG_HD bool stage_batch_ok(uint64_t base, uint64_t len, uint32_t skip, int n_chunks, int in_chunks) {
+    return n_chunks == in_chunks && base + 16ull * (uint64_t)n_chunks <= len && !(base == 0 && skip != 0);
+}
+
+// The chunks lane + j * BLOCK (< IN_CHUNKS) of a tile for which stage_batch_ok holds, staged: what the loop of stage_tile does
+// for them, with every load in front of the first use.  In the last trip the lanes without a chunk (all but the few that take
+// the stray chunks of the halo) take the tile's last chunk once more.  THE DUPLICATE STORES ARE RELIED ON TO BE IDEMPOTENT:
+// such a lane loads, stages and stores exactly what that chunk's own lane does -- the same bytes to the same words of s_in and
+// s_comp, the same 1 to *s_dirty -- so whichever store lands last, the words hold the same value.
+template <int IN_CHUNKS, int BLOCK>
+SMG_HD void stage_lane_batched(const uint8_t* seq, uint64_t base, int lane, uint32_t* s_in, uint32_t* s_comp, unsigned int* s_dirty,
+                               int n_chunks = IN_CHUNKS) {
+    // n_chunks: IN_CHUNKS, which the device caller passes as the run-time value it compared with it -- with the constant the
+    // compiler holds the last load back behind a wait for the first two
+    constexpr int TRIPS = (IN_CHUNKS + BLOCK - 1) / BLOCK;
+    uint32_t w[TRIPS][4];
+    // So the batch is straight-line code without a lane mask.  With a branch per load the compiler joins a load's block with
+    // the block of its use and waits for memory once per trip again.
+#pragma unroll
+    for (int j = 0; j < TRIPS; ++j) {
+        const int c = lane + j * BLOCK < n_chunks ? lane + j * BLOCK : n_chunks - 1;
+        const uint64_t off = base + (uint64_t)c * 16;
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint4 v = *reinterpret_cast<const uint4*>(seq + off);
+        w[j][0] = v.x; w[j][1] = v.y; w[j][2] = v.z; w[j][3] = v.w;
+#else
+        w[j][0] = w[j][1] = w[j][2] = w[j][3] = 0;
+        for (int b = 0; b < 16; ++b) w[j][b >> 2] |= (uint32_t)seq[off + b] << (8 * (b & 3));
+#endif
+    }
+#pragma unroll
+    for (int j = 0; j < TRIPS; ++j) {
+        const int c = lane + j * BLOCK < n_chunks ? lane + j * BLOCK : n_chunks - 1;
+        uint32_t cw[4];
+        if (stage_chunk(w[j], cw)) *s_dirty = 1;
+        store_chunk(&s_comp[c * 4], cw);
+        store_chunk(&s_in[c * 4], w[j]);
+    }
+}
+
+template <int IN_CHUNKS, bool STAGED, int BLOCK, bool BATCH = false>
 SMG_HD void stage_tile(const uint8_t* seq, uint64_t base, uint64_t len, uint32_t skip, uint32_t* s_in, uint32_t* s_comp,
                        unsigned int* s_dirty, int n_chunks = IN_CHUNKS) {
+    static_assert(!BATCH || STAGED, "the batch is a form of the staged tile");
 #if defined(__HIP_DEVICE_COMPILE__)
-    const int first = threadIdx.x, step = BLOCK;
+    int first = threadIdx.x;
+    const int step = BLOCK;
+    if constexpr (BATCH) {
+        // The lane index and the chunk count pass through an empty asm: what is derived from them -- the lane's addresses in
+        // memory and in LDS, the batch's bounds -- is then computed here, per tile, where the window's registers are dead.
+        // Otherwise they are invariants of the caller's tile loop, and the compiler keeps two dozen of them in registers across
+        // the hash loop (k = 31: 120 -> 141 vector registers, a wave per SIMD).  The lever is the compiler's to honour and no
+        // test sees it fail: after a compiler change compare the registers with tools/kernel_resources.py (118 at k = 31,
+        // profiles/stage_batch_kernel_resources.txt).
+        asm volatile("" : "+v"(first));
+        asm volatile("" : "+s"(n_chunks));
+        if (stage_batch_ok(base, len, skip, n_chunks, IN_CHUNKS)) {
+            stage_lane_batched<IN_CHUNKS, BLOCK>(seq, base, first, s_in, s_comp, s_dirty, n_chunks);
+            return;
+        }
+    }
 #else
     const int first = 0, step = 1;
 #endif

@@ -90,6 +90,20 @@ constexpr bool sk_handout(int) { return false; }
 #else
 constexpr bool sk_handout(int) { return true; }
 #endif
+// The staged appending form of several rounds stages a tile that lies wholly inside the buffer in one batch (kmer_core.hpp,
+// stage_tile<.., BATCH>): a lane issues the loads of all its chunks -- five at k = 31, 1,026 chunks for 256 lanes, the two
+// stray ones of the halo among them -- in front of the first use, where the rolled loop pays a round trip to memory per trip.
+// The loads live in the turnover between two tiles, where the window's registers are dead.  A launch that walks tiles of one
+// round (small `scaled`, num sketches) stays on the loop: whole trips of the batch would serve no chunk there.  An instantiation
+// that would run fewer waves per SIMD, gain scratch or spill with the batch stays on the loop; none does
+// (profiles/stage_batch_kernel_resources.txt) -- but that holds by an empty asm in stage_tile that keeps the staging addresses
+// out of the hash loop's registers, which no test guards: re-run tools/kernel_resources.py after a compiler change.
+// SMG_SK_STAGE_LOOP: a variant build with the loop everywhere, for A/B runs.
+#ifdef SMG_SK_STAGE_LOOP
+constexpr bool sk_stage_batched(int) { return false; }
+#else
+constexpr bool sk_stage_batched(int k) { return sk_staged(k) && !sk_one_round(k); }
+#endif
 // Workgroups per CU a launch may ask for (tile_launch.hpp, sk_grid); 0: as many workgroups as are resident at once
 // (sk_resident_grid), which is what a launch with tickets takes -- at k = 31 a step of the benchmark took 27.04 ms with the 1,024
 // resident workgroups, 27.01 with 2,048 and 27.03 with 8,192, a tie, and the smallest grid has the fewest start-ups and partial
@@ -146,8 +160,9 @@ __global__ __launch_bounds__(SK_BLOCK) void sketch_dna_kernel(
         }
         __syncthreads();   // previous tile's readers are done with s_in; s_cnt reset visible
         if constexpr (STAGED) {
-            if constexpr (R_MAX > 1) stage_tile<IN_CHUNKS, true, SK_BLOCK>(seq, base, len, skip, s_in, s_comp, &s_dirty, T::chunks((int)n_rounds));
-            else stage_tile<IN_CHUNKS, true, SK_BLOCK>(seq, base, len, skip, s_in, s_comp, &s_dirty);
+            constexpr bool BATCH = sk_stage_batched(K);
+            if constexpr (R_MAX > 1) stage_tile<IN_CHUNKS, true, SK_BLOCK, BATCH>(seq, base, len, skip, s_in, s_comp, &s_dirty, T::chunks((int)n_rounds));
+            else stage_tile<IN_CHUNKS, true, SK_BLOCK, BATCH>(seq, base, len, skip, s_in, s_comp, &s_dirty);
         } else {
             // stage_tile<IN_CHUNKS, false> (kmer_core.hpp), kept inline: through the function, in either shape of its loader, the
             // dense k = 1 goes from 64 to 66 VGPRs, the dense k = 25 from 128 to 130, the appending k = 18 from 96 to 98 -- a wave
