@@ -1014,7 +1014,8 @@ double smgpu_nodegraph_containment(const SourmashNodegraph *ptr, const SourmashN
 uintptr_t smgpu_nodegraph_table_sizes(uintptr_t starting_size, uintptr_t n_tables, uint64_t *out, uintptr_t cap);
 
 /* ---- set algebra on resident collections: merge by group, intersect, subtract, downsample (csrc/setops.hip, csrc/setops_core.hpp) ----
- * Flat sketches only, as `sig merge --flatten`, `sig intersect` and `sig subtract` work.  Every set-level entry returns a NEW set
+ * Flat sets as `sig merge --flatten`, `sig intersect` and `sig subtract` work; what a set that carries abundances adds is said
+ * under "abundance sets" below.  Every set-level entry returns a NEW set
  * (freed with smgpu_sketchset_free) with the receiver's parameters, host offsets and manifest rows; the receiver is unchanged.
  * geometry: lanes of a workgroup, the partner hashes the row-wise filter stages in LDS, and the row length above which the filter
  * splits a row over workgroups.  key_form: the pair form of the merge for a set of `max_hash` (0: num) merged into n_groups rows --
@@ -1053,6 +1054,75 @@ SmgpuSketchSet *smgpu_sketchset_filter(const SmgpuSketchSet *set, const SmgpuSke
 SmgpuSketchSet *smgpu_sketchset_filter_sketch(const SmgpuSketchSet *set, const SourmashKmerMinHash *mh, uint32_t keep_present);
 /* Every row cut to its hashes <= max_hash; a larger max_hash than the set's is CANNOT_UPSAMPLE_SCALED. */
 SmgpuSketchSet *smgpu_sketchset_downsample(const SmgpuSketchSet *set, uint64_t max_hash);
+
+/* ---- abundance sets: a resident collection with a u64 abundance column aligned with its hashes (csrc/capi_abund_set.cpp,
+ * csrc/abund_set.hip, and the value-moving forms of csrc/setops.hip).  Every stored abundance is at least 1.  Every entry that
+ * reads hashes and offsets only (compare, overlaps, search, gather, the many-query entries, Nodegraph, find, md5sums) sees an
+ * abundance set as its flattened self.  subset, downsample and smgpu_sketchset_filter* carry the receiver's abundances with the
+ * kept hashes (the other side's stay ignored); smgpu_sketchset_merge_groups sums them per kept hash (wrapping u64);
+ * smgpu_sketchset_get gives abundance sketches; smgpu_sketchset_to_json and smgpu_sigwriter_add refuse the set.
+ * new_abund: every sketch must track abundance (NEEDS_ABUNDANCE_TRACKING) and share parameters (the reference's mismatch errors).
+ * from_csr_abund: smgpu_sketchset_from_csr with d_abunds aligned with d_hashes; a 0 in it is refused with the first such position. */
+SmgpuSketchSet *smgpu_sketchset_new_abund(const SourmashKmerMinHash *const *mhs, uintptr_t n);
+SmgpuSketchSet *smgpu_sketchset_from_csr_abund(const uint64_t *d_hashes, const uint64_t *d_abunds, const uint64_t *d_offsets, uint64_t n,
+                                               uint32_t ksize, uint32_t hash_function, uint64_t seed, uint64_t max_hash, uint64_t num,
+                                               const char *const *names, const char *const *filenames);
+/* smgpu_sketchset_sketch_records / _sketch_file / _sketch_residue_records / _sketch_residue_file with track_abundance != 0: the
+ * result is an abundance set, a kept hash's abundance the number of times the record holds it (both strands counted as one
+ * k-mer, as add_sequence counts); manifest rows say with_abundance = 1.  track_abundance = 0: the flat entries themselves. */
+SmgpuSketchSet *smgpu_sketchset_sketch_records_abund(const uint8_t *d_seq, uint64_t len, const uint64_t *d_starts, uint64_t n_records,
+                                                     uint32_t ksize, uint64_t seed, uint64_t scaled, uint32_t track_abundance);
+SmgpuSketchSet *smgpu_sketchset_sketch_file_abund(const char *path, uint32_t ksize, uint64_t seed, uint64_t scaled, uint32_t track_abundance);
+SmgpuSketchSet *smgpu_sketchset_sketch_residue_records_abund(const uint8_t *d_seq, uint64_t len, const uint64_t *d_starts, const uint64_t *d_ends,
+                                                             uint64_t n_records, uint32_t ksize, uint32_t hash_function, int32_t translate,
+                                                             uint64_t seed, uint64_t scaled, uint32_t track_abundance);
+SmgpuSketchSet *smgpu_sketchset_sketch_residue_file_abund(const char *path, uint32_t ksize, uint32_t hash_function, int32_t translate,
+                                                          uint64_t seed, uint64_t scaled, uint32_t track_abundance);
+/* 1 for an abundance set; the largest stored abundance (a bound after a filter; UINT64_MAX after a summing merge). */
+uint32_t smgpu_sketchset_track_abundance(const SmgpuSketchSet *set);
+uint64_t smgpu_sketchset_abund_max(const SmgpuSketchSet *set);
+/* The column where it lies, borrowed: valid while the set lives; NULL for a flat set. */
+void smgpu_sketchset_device_abunds(const SmgpuSketchSet *set, const uint64_t **d_abunds);
+/* out[r] = the sum of row r's abundances, wrapping u64 (MinHash.sum_abundances), computed on the device. */
+void smgpu_sketchset_abund_sums(const SmgpuSketchSet *set, uint64_t *out);
+/* A flat copy (device-to-device); manifest rows say with_abundance = 0. */
+SmgpuSketchSet *smgpu_sketchset_flatten(const SmgpuSketchSet *set);
+/* sig inflate: `set` is flat, `other` carries abundance (one row against every row, or as many rows as `set`, row by row; or one
+ * sketch).  A hash is kept when the other side holds it and takes the other side's abundance.  Parameters as for
+ * smgpu_sketchset_filter. */
+SmgpuSketchSet *smgpu_sketchset_inflate(const SmgpuSketchSet *set, const SmgpuSketchSet *other);
+SmgpuSketchSet *smgpu_sketchset_inflate_sketch(const SmgpuSketchSet *set, const SourmashKmerMinHash *mh);
+/* sig filter: the hashes whose abundance a satisfies min_abundance <= a <= max_abundance (UINT64_MAX: no upper bound), with
+ * their abundances.  A flat set is NEEDS_ABUNDANCE_TRACKING. */
+SmgpuSketchSet *smgpu_sketchset_filter_abund(const SmgpuSketchSet *set, uint64_t min_abundance, uint64_t max_abundance);
+/* smgpu_sketchset_merge_groups with count_rows != 0: `set` is flat and the result carries, as abundance, the number of rows of
+ * the group that hold the hash.  count_rows = 0: smgpu_sketchset_merge_groups itself. */
+SmgpuSketchSet *smgpu_sketchset_merge_groups_values(const SmgpuSketchSet *set, const uint32_t *groups, uint64_t n_groups, const uint32_t *need,
+                                                    uint32_t need_all, const char *const *names, uint32_t count_rows);
+/* sims_out: n x n doubles, the angular similarity of every pair of rows (smgpu_compare_abund_raw_n on the set's own buffers,
+ * narrow when every abundance is below 2^32, then smgpu_host_angular_f64).  A flat set is NEEDS_ABUNDANCE_TRACKING. */
+void smgpu_sketchset_compare_angular(const SmgpuSketchSet *set, double *sims_out);
+/* smgpu_sketchset_gather_rows_many; use_resident != 0: `queries` is an abundance set and its own column is the pass's
+ * abundances (abunds must be NULL): no host array, no upload. */
+SmgpuGatherRows *smgpu_sketchset_gather_rows_many_resident(const SmgpuSketchSet *db, const SmgpuSketchSet *queries, const uint64_t *abunds,
+                                                           uint64_t threshold_hashes, uint32_t use_resident);
+/* The value-moving forms on caller-owned buffers.  filter: smgpu_setops_filter_raw (its workspace function serves) with `values`:
+ * 0 flat; 1 carry -- d_abunds is aligned with d_hashes and a kept hash keeps its own; 2 take -- d_other_abunds is aligned with
+ * d_other_hashes, keep_present is 1, a kept hash takes the other's at the found position; 3 range -- no other sketch, a hash is
+ * kept when range_lo <= its abundance <= range_hi.  d_out_abunds: `capacity` values beside d_out_hashes.
+ * merge: smgpu_setops_merge_raw with `values`: 0 flat; 1 sum -- d_out_abunds gets the wrapping u64 sum of the abundances of the
+ * group's rows that hold the hash; 2 count -- their number (d_abunds is not read).  With values the workspace is
+ * smgpu_setops_merge_values_workspace_bytes'. */
+uint64_t smgpu_setops_filter_values_raw(const uint64_t *d_hashes, const uint64_t *d_abunds, const uint64_t *d_offsets, uint64_t n, uint64_t total,
+                                        const uint64_t *d_other_hashes, const uint64_t *d_other_abunds, const uint64_t *d_other_offsets,
+                                        uint64_t other_len, uint32_t keep_present, uint32_t values, uint64_t range_lo, uint64_t range_hi,
+                                        uint32_t grid, uint64_t *d_out_hashes, uint64_t *d_out_abunds, uint64_t capacity,
+                                        uint64_t *d_out_offsets, uint64_t *d_result, void *d_workspace, uint64_t workspace_bytes, void *stream);
+uint64_t smgpu_setops_merge_values_workspace_bytes(uint64_t total, uint64_t n_groups);
+uint64_t smgpu_setops_merge_values_raw(const uint64_t *d_hashes, const uint64_t *d_abunds, const uint64_t *d_offsets, uint64_t n, uint64_t total,
+                                       const uint32_t *d_groups, uint64_t n_groups, const uint32_t *d_need, uint32_t need_all,
+                                       uint64_t max_hash, uint64_t num, uint32_t values, uint64_t *d_out_hashes, uint64_t *d_out_abunds,
+                                       uint64_t *d_out_offsets, uint64_t *d_result, void *d_workspace, uint64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

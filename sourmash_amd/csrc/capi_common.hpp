@@ -6,6 +6,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -126,7 +127,32 @@ struct SketchSet {
     uint32_t ksize = 0, hash_function = HF_DNA;
     uint64_t seed = 42, max_hash = 0, num = 0, skipped = 0;
     // (the device blocks are arena blocks and go back to the arena with the DevBufs: no hipFree, which would synchronise the device)
+    // An abundance set: u64 abundances aligned with `hashes`, every one >= 1 (MinHash.set_abundances drops zeros); no block: a flat
+    // set.  Every reader of hashes / offsets sees an abundance set as its flattened self.  abund_max: the largest stored abundance
+    // (it chooses the narrow form of the angular kernels).
+    DevBuf abunds;
+    uint64_t abund_max = 0;
+    bool has_abunds() const { return abunds.p != nullptr; }
 };
+
+// ---- abundance sets (capi_abund_set.cpp) and what the set-algebra unit (capi_setops.cpp) shares with them
+// an empty set of n rows with the parameters of s
+std::unique_ptr<SketchSet> sketchset_like(const SketchSet& s, uint64_t n);
+// The manifest rows of a result whose host offsets stand: those of `from` (row for row, when it has them) or fresh ones, with the
+// new sizes; with_abundance says whether the result carries the column.
+void sketchset_finish_rows(SketchSet& out, const SketchSet* from);
+// the device offsets of a result (n + 1 values) to its host side, and its total
+void sketchset_fetch_offsets(SketchSet& out, hipStream_t st);
+// sig subtract / sig intersect / sig inflate refuse sketches of other parameters: the reference's order (check_compatible)
+void check_filter_compatible(const SketchSet& s, uint32_t ksize, uint32_t hash_function, uint64_t max_hash, uint64_t seed);
+// The filter of a resident set in any value mode (setops_core.hpp: SetopsValueMode) -> a new set; with a mode that moves values the
+// result carries the column.  d_other_offsets null: one sketch d_other_hashes[0, other_len) (TAKE: d_other_abunds beside it);
+// otherwise a second CSR row by row.  abund_max: of the other side, for TAKE.
+SketchSet* sketchset_filter_values(const SketchSet& s, const uint64_t* d_other_hashes, const uint64_t* d_other_offsets, uint64_t other_len,
+                                   uint32_t keep_present, uint32_t values, const uint64_t* d_other_abunds, uint64_t range_lo, uint64_t range_hi,
+                                   hipStream_t st, uint64_t abund_max = 0);
+// the writers' refusal of an abundance set
+void refuse_abundance_writer(const SketchSet& s, const char* entry);
 
 // ---- helpers of the many-queries unit (capi_many.cpp) and the gather unit (capi_gather.cpp) that the gather-many unit uses too
 // throws the reference's mismatch error for two sets that cannot meet (many_core.hpp: many_compat_code)

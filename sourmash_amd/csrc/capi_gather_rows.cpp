@@ -39,8 +39,9 @@ double ms_since(std::chrono::steady_clock::time_point t) {
 
 // The pass on resident buffers: out->offsets / rows / isect hold the picks (host); h_abunds (may be null) is aligned with the m
 // queries' q_total hashes on the device.  Fills the rest of *out and checks the pass against the gather: unique == isect.
+// d_resident_abunds (may be null): the same column already on the device -- an abundance set's own; nothing is uploaded then.
 void rows_pass(const SketchSet& db, const uint64_t* d_qhashes, const uint64_t* d_qoffsets, uint64_t m, uint64_t q_total, const uint64_t* h_abunds,
-               GatherRows* out, const char* who, hipStream_t st) {
+               GatherRows* out, const char* who, hipStream_t st, const uint64_t* d_resident_abunds = nullptr) {
     const uint64_t n = db.n, n_picks = out->rows.size(), cutoff = out->max_hash;
     if (!gr_sizes_fit(m, q_total, n, n_picks)) throw err_internal(std::string(who) + ": 2^32 queries, query hashes, rows or picks are not taken");
     out->orig_common.assign(n_picks, 0);
@@ -63,11 +64,11 @@ void rows_pass(const SketchSet& db, const uint64_t* d_qhashes, const uint64_t* d
     AsyncBuf ws((size_t)ws_bytes, st);
     hip_check(hipMemcpyAsync(d_pick_off.p, out->offsets.data(), (m + 1) * 8, hipMemcpyHostToDevice, st), "H2D");
     if (n_picks) hip_check(hipMemcpyAsync(d_pick_rows.p, out->rows.data(), n_picks * 4, hipMemcpyHostToDevice, st), "H2D");
-    if (h_abunds && q_total) {
+    if (h_abunds && q_total && !d_resident_abunds) {
         d_abunds.reset(q_total * 8, st);
         hip_check(hipMemcpyAsync(d_abunds.p, h_abunds, q_total * 8, hipMemcpyHostToDevice, st), "H2D");
     }
-    const GatherRowsArgs a{d_qhashes, d_abunds.as<uint64_t>(), d_qoffsets, m, q_total, db.hashes.as<uint64_t>(), db.offsets.as<uint64_t>(), n,
+    const GatherRowsArgs a{d_qhashes, d_resident_abunds && q_total ? d_resident_abunds : d_abunds.as<uint64_t>(), d_qoffsets, m, q_total, db.hashes.as<uint64_t>(), db.offsets.as<uint64_t>(), n,
                            d_pick_off.as<uint64_t>(), d_pick_rows.as<uint32_t>(), n_picks, cutoff, 0, d_owner.as<uint32_t>(), d_orig.as<uint32_t>(),
                            d_unique.as<uint32_t>(), d_weighted.as<uint64_t>(), d_aoff.as<uint64_t>(), d_avals.as<uint64_t>(), d_qsizes.as<uint64_t>(),
                            d_tw.as<uint64_t>(), ws.p, ws_bytes};
@@ -148,10 +149,17 @@ uint64_t smgpu_gather_rows_raw(const uint64_t* d_qhashes, const uint64_t* d_qabu
 
 SmgpuGatherRows* smgpu_sketchset_gather_rows_many(const SmgpuSketchSet* db_p, const SmgpuSketchSet* queries_p, const uint64_t* abunds,
                                                   uint64_t threshold_hashes) {
+    return smgpu_sketchset_gather_rows_many_resident(db_p, queries_p, abunds, threshold_hashes, 0);
+}
+
+SmgpuGatherRows* smgpu_sketchset_gather_rows_many_resident(const SmgpuSketchSet* db_p, const SmgpuSketchSet* queries_p, const uint64_t* abunds,
+                                                           uint64_t threshold_hashes, uint32_t use_resident) {
     return landing<SmgpuGatherRows*>([&]() -> SmgpuGatherRows* {
         const SketchSet* db = reinterpret_cast<const SketchSet*>(db_p);
         const SketchSet* qs = reinterpret_cast<const SketchSet*>(queries_p);
         if (!db || !qs) throw err_internal("smgpu_sketchset_gather_rows_many: null pointer");
+        if (use_resident && abunds) throw err_internal("smgpu_sketchset_gather_rows_many_resident: the set's own abundances, or an array, not both");
+        if (use_resident && !qs->has_abunds()) throw err_internal("smgpu_sketchset_gather_rows_many_resident: the queries are a flat set");
         check_sets_compatible(*db, *qs);
         const auto t_begin = std::chrono::steady_clock::now();
         // ---- the picks: the many-queries gather itself (its error, if any, stands in the thread's slot)
@@ -170,7 +178,9 @@ SmgpuGatherRows* smgpu_sketchset_gather_rows_many(const SmgpuSketchSet* db_p, co
         // ---- the pass, on the buffers the gather worked on
         DeviceCtx& ctx = DeviceCtx::get();
         std::lock_guard<std::recursive_mutex> g(ctx.mutex());
-        rows_pass(*db, qs->hashes.as<uint64_t>(), qs->offsets.as<uint64_t>(), m, qs->total, abunds, out.get(), "smgpu_sketchset_gather_rows_many", ctx.stream());
+        // (use_resident: the queries' own abundance column is the pass's d_qabunds -- no host array, no upload)
+        rows_pass(*db, qs->hashes.as<uint64_t>(), qs->offsets.as<uint64_t>(), m, qs->total, abunds, out.get(), "smgpu_sketchset_gather_rows_many", ctx.stream(),
+                  use_resident ? qs->abunds.as<uint64_t>() : nullptr);
         out->stats[4] = ms_since(t_begin);
         return reinterpret_cast<SmgpuGatherRows*>(out.release());
     });

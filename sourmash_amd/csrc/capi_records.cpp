@@ -213,13 +213,14 @@ void records_csr(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, c
     });
 }
 
-// a set that takes over the blocks of the records' CSR; ksize in units of the molecule
+// a set that takes over the blocks of the records' CSR; ksize in units of the molecule.  want_abunds: an abundance set, which
+// takes over the third block too -- every kept hash's multiplicity in its record (at least 1)
 SketchSet* sketchset_from_records(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, const uint64_t* d_ends, uint64_t n_records, uint32_t ksize,
-                                  bool residue, uint32_t hf, bool translate, uint64_t seed, uint64_t scaled, hipStream_t st) {
+                                  bool residue, uint32_t hf, bool translate, uint64_t seed, uint64_t scaled, hipStream_t st, bool want_abunds = false) {
     if (scaled == 0) throw err_internal("per-record sketches are scaled sketches: scaled must not be 0");
     const uint64_t max_hash = max_hash_for_scaled(scaled);
     RecordsCsr csr;
-    records_csr(d_seq, len, d_starts, d_ends, n_records, ksize, residue, hf, translate, seed, max_hash, false, csr, st);
+    records_csr(d_seq, len, d_starts, d_ends, n_records, ksize, residue, hf, translate, seed, max_hash, want_abunds, csr, st);
     std::unique_ptr<SketchSet> s(new SketchSet());
     s->n = n_records; s->total = csr.total;
     s->ksize = ksize; s->hash_function = hf; s->seed = seed; s->max_hash = max_hash; s->num = 0;
@@ -228,10 +229,21 @@ SketchSet* sketchset_from_records(const uint8_t* d_seq, uint64_t len, const uint
     hip_check(hipStreamSynchronize(st), "sync");
     std::swap(s->hashes.p, csr.hashes.p); std::swap(s->hashes.cap, csr.hashes.cap); std::swap(s->hashes.st, csr.hashes.st);
     std::swap(s->offsets.p, csr.offsets.p); std::swap(s->offsets.cap, csr.offsets.cap); std::swap(s->offsets.st, csr.offsets.st);
+    if (want_abunds) {
+        std::swap(s->abunds.p, csr.abunds.p); std::swap(s->abunds.cap, csr.abunds.cap); std::swap(s->abunds.st, csr.abunds.st);
+        if (!s->abunds.p) s->abunds.reserve(16, st);                 // (no record kept a hash: still an abundance set)
+        AsyncBuf d_max(64, st);
+        uint64_t found[2] = {0, ~0ull};
+        hip_check(abund_check_launch(s->abunds.as<uint64_t>(), s->total, d_max.as<uint64_t>(), st), "abund_check");
+        hip_check(hipMemcpyAsync(found, d_max.p, 16, hipMemcpyDeviceToHost, st), "D2H");
+        hip_check(hipStreamSynchronize(st), "sync");
+        if (found[1] != ~0ull) throw err_internal("per-record sketches: a kept hash with multiplicity 0");
+        s->abund_max = found[0];
+    }
     s->rows.resize(n_records);
     for (uint64_t r = 0; r < n_records; ++r) {
         ManifestRow& m = s->rows[r];
-        m.ksize = ksize; m.moltype = molecule_name(hf); m.scaled = scaled;
+        m.ksize = ksize; m.moltype = molecule_name(hf); m.scaled = scaled; m.with_abundance = want_abunds;
         m.n_hashes = s->host_offsets[r + 1] - s->host_offsets[r];
     }
     return s.release();
@@ -344,7 +356,8 @@ void file_record_ends(const ParsedRecords& pr, AsyncBuf& ends, hipStream_t st) {
 }
 
 // sketchset_from_records over the records of a file, the rows named after them; the DNA pass takes no ends
-SketchSet* sketchset_from_file(const char* path, uint32_t ksize, bool residue, uint32_t hf, bool translate, uint64_t seed, uint64_t scaled) {
+SketchSet* sketchset_from_file(const char* path, uint32_t ksize, bool residue, uint32_t hf, bool translate, uint64_t seed, uint64_t scaled,
+                               bool want_abunds = false) {
     if (!path) throw err_internal("null path");
     DeviceCtx& ctx = DeviceCtx::get();
     std::lock_guard<std::recursive_mutex> g(ctx.mutex());
@@ -354,7 +367,7 @@ SketchSet* sketchset_from_file(const char* path, uint32_t ksize, bool residue, u
     AsyncBuf ends;
     if (residue) file_record_ends(pr, ends, st);
     std::unique_ptr<SketchSet> s(sketchset_from_records(pr.comp.as<uint8_t>(), pr.len, pr.starts.as<uint64_t>(), residue ? ends.as<uint64_t>() : nullptr,
-                                                        pr.n_records, ksize, residue, hf, translate, seed, scaled, st));
+                                                        pr.n_records, ksize, residue, hf, translate, seed, scaled, st, want_abunds));
     for (uint64_t r = 0; r < pr.n_records; ++r) { s->rows[r].name = pr.names[r]; s->rows[r].filename = path; }
     return s.release();
 }
@@ -526,6 +539,41 @@ SmgpuSketchSet* smgpu_sketchset_sketch_records(const uint8_t* d_seq, uint64_t le
 SmgpuSketchSet* smgpu_sketchset_sketch_file(const char* path, uint32_t ksize, uint64_t seed, uint64_t scaled) {
     return landing<SmgpuSketchSet*>([&]() -> SmgpuSketchSet* {
         return reinterpret_cast<SmgpuSketchSet*>(sketchset_from_file(path, ksize, false, HF_DNA, false, seed, scaled));
+    });
+}
+
+// the same four with the records' multiplicities kept: abundance sets (track_abundance = 0: the flat entries themselves)
+SmgpuSketchSet* smgpu_sketchset_sketch_records_abund(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, uint64_t n_records, uint32_t ksize,
+                                                     uint64_t seed, uint64_t scaled, uint32_t track_abundance) {
+    return landing<SmgpuSketchSet*>([&]() -> SmgpuSketchSet* {
+        DeviceCtx& ctx = DeviceCtx::get();
+        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+        return reinterpret_cast<SmgpuSketchSet*>(sketchset_from_records(d_seq, len, d_starts, nullptr, n_records, ksize, false, HF_DNA, false, seed, scaled, ctx.stream(),
+                                                                        track_abundance != 0));
+    });
+}
+
+SmgpuSketchSet* smgpu_sketchset_sketch_file_abund(const char* path, uint32_t ksize, uint64_t seed, uint64_t scaled, uint32_t track_abundance) {
+    return landing<SmgpuSketchSet*>([&]() -> SmgpuSketchSet* {
+        return reinterpret_cast<SmgpuSketchSet*>(sketchset_from_file(path, ksize, false, HF_DNA, false, seed, scaled, track_abundance != 0));
+    });
+}
+
+SmgpuSketchSet* smgpu_sketchset_sketch_residue_records_abund(const uint8_t* d_seq, uint64_t len, const uint64_t* d_starts, const uint64_t* d_ends,
+                                                             uint64_t n_records, uint32_t ksize, uint32_t hash_function, int32_t translate, uint64_t seed,
+                                                             uint64_t scaled, uint32_t track_abundance) {
+    return landing<SmgpuSketchSet*>([&]() -> SmgpuSketchSet* {
+        DeviceCtx& ctx = DeviceCtx::get();
+        std::lock_guard<std::recursive_mutex> g(ctx.mutex());
+        return reinterpret_cast<SmgpuSketchSet*>(sketchset_from_records(d_seq, len, d_starts, d_ends, n_records, ksize, true, hash_function, translate != 0, seed, scaled,
+                                                                        ctx.stream(), track_abundance != 0));
+    });
+}
+
+SmgpuSketchSet* smgpu_sketchset_sketch_residue_file_abund(const char* path, uint32_t ksize, uint32_t hash_function, int32_t translate, uint64_t seed,
+                                                          uint64_t scaled, uint32_t track_abundance) {
+    return landing<SmgpuSketchSet*>([&]() -> SmgpuSketchSet* {
+        return reinterpret_cast<SmgpuSketchSet*>(sketchset_from_file(path, ksize, true, hash_function, translate != 0, seed, scaled, track_abundance != 0));
     });
 }
 

@@ -18,6 +18,18 @@ void need_params(const SketchSet& s) {
     if (s.ksize == 0) throw err_internal("the set's sketches do not share one set of parameters");
 }
 
+// The filter of a resident set against one sketch on the device (d_other[0, other_len)) or a second set row by row.  An abundance
+// receiver carries its column: the kept hashes keep their own abundances (the other side's stay ignored).
+SketchSet* filter_set(const SketchSet& s, const uint64_t* d_other_hashes, const uint64_t* d_other_offsets, uint64_t other_len, uint32_t keep_present,
+                      hipStream_t st) {
+    return sketchset_filter_values(s, d_other_hashes, d_other_offsets, other_len, keep_present,
+                                   s.has_abunds() ? SETOPS_VALUES_CARRY : SETOPS_VALUES_NONE, nullptr, 0, ~0ull, st);
+}
+
+}  // namespace
+
+namespace smg {
+
 // the reference's order (check_compatible, minhash.rs:886-912) with max_hash always compared: sig subtract / sig intersect refuse
 // sketches of different scaled (is_compatible), and the caller downsamples first
 void check_filter_compatible(const SketchSet& s, uint32_t ksize, uint32_t hash_function, uint64_t max_hash, uint64_t seed) {
@@ -27,26 +39,15 @@ void check_filter_compatible(const SketchSet& s, uint32_t ksize, uint32_t hash_f
     if (s.seed != seed) throw err_mismatch_seed();
 }
 
-// the offsets of a set on the host (a set built from sketch handles keeps none)
-std::vector<uint64_t> host_offsets_of(const SketchSet& s, hipStream_t st) {
-    if (s.host_offsets.size() == s.n + 1) return s.host_offsets;
-    std::vector<uint64_t> off(s.n + 1, 0);
-    hip_check(hipMemcpyAsync(off.data(), s.offsets.p, (s.n + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
-    hip_check(hipStreamSynchronize(st), "sync");
-    return off;
-}
-
-// an empty set of n rows with the parameters of s
-std::unique_ptr<SketchSet> like(const SketchSet& s, uint64_t n) {
+std::unique_ptr<SketchSet> sketchset_like(const SketchSet& s, uint64_t n) {
     std::unique_ptr<SketchSet> out(new SketchSet());
     out->n = n;
     out->ksize = s.ksize; out->hash_function = s.hash_function; out->seed = s.seed; out->max_hash = s.max_hash; out->num = s.num;
     return out;
 }
 
-// The manifest rows of a result whose host offsets stand: those of `from` (row for row, when it has them) or fresh ones, with the
-// new sizes; a row's md5 is that of other hashes and is dropped.
-void finish_rows(SketchSet& out, const SketchSet* from) {
+// (a row's md5 is that of other hashes and is dropped)
+void sketchset_finish_rows(SketchSet& out, const SketchSet* from) {
     out.rows.assign(out.n, ManifestRow());
     for (uint64_t r = 0; r < out.n; ++r) {
         ManifestRow& m = out.rows[r];
@@ -55,42 +56,48 @@ void finish_rows(SketchSet& out, const SketchSet* from) {
         m.internal_location.clear();
         m.ksize = out.ksize; m.moltype = molecule_name(out.hash_function); m.num = out.num;
         m.scaled = out.max_hash ? scaled_for_max_hash(out.max_hash) : 0;
-        m.with_abundance = false;
+        m.with_abundance = out.has_abunds();
         m.n_hashes = out.host_offsets[r + 1] - out.host_offsets[r];
     }
 }
 
-// the device offsets of a result (n + 1 values in d_offsets) to its host side
-void fetch_offsets(SketchSet& out, hipStream_t st) {
+void sketchset_fetch_offsets(SketchSet& out, hipStream_t st) {
     out.host_offsets.assign(out.n + 1, 0);
     hip_check(hipMemcpyAsync(out.host_offsets.data(), out.offsets.p, (out.n + 1) * 8, hipMemcpyDeviceToHost, st), "D2H");
     hip_check(hipStreamSynchronize(st), "sync");
     out.total = out.host_offsets[out.n];
 }
 
-// the filter of a resident set against one sketch on the device (d_other[0, other_len)) or a second set row by row
-SketchSet* filter_set(const SketchSet& s, const uint64_t* d_other_hashes, const uint64_t* d_other_offsets, uint64_t other_len, uint32_t keep_present,
-                      hipStream_t st) {
-    std::unique_ptr<SketchSet> out = like(s, s.n);
+// One filter for every value mode (setops_core.hpp: SetopsValueMode): count, room, write; the result carries an abundance column
+// whenever the mode moves values.  abund_max of the result: the source's (a bound is all the angular kernels need).
+SketchSet* sketchset_filter_values(const SketchSet& s, const uint64_t* d_other_hashes, const uint64_t* d_other_offsets, uint64_t other_len,
+                                   uint32_t keep_present, uint32_t values, const uint64_t* d_other_abunds, uint64_t range_lo, uint64_t range_hi,
+                                   hipStream_t st, uint64_t abund_max) {
+    std::unique_ptr<SketchSet> out = sketchset_like(s, s.n);
     out->offsets.reserve((s.n + 1) * 8, st);
     const uint64_t ws_bytes = setops_filter_workspace_bytes(s.n, s.total, d_other_offsets ? 0 : other_len);
     AsyncBuf ws((size_t)ws_bytes, st), d_result(64, st);
-    const SetopsFilterArgs a{s.hashes.as<uint64_t>(), s.offsets.as<uint64_t>(), s.n, s.total, d_other_hashes, d_other_offsets, other_len,
-                             keep_present, 0, out->offsets.as<uint64_t>(), d_result.as<uint64_t>(), ws.p, ws_bytes};
+    SetopsFilterArgs a{s.hashes.as<uint64_t>(), s.offsets.as<uint64_t>(), s.n, s.total, d_other_hashes, d_other_offsets, other_len,
+                       keep_present, 0, out->offsets.as<uint64_t>(), d_result.as<uint64_t>(), ws.p, ws_bytes};
+    a.values = values; a.d_abunds = s.abunds.as<uint64_t>(); a.d_other_abunds = d_other_abunds; a.range_lo = range_lo; a.range_hi = range_hi;
     SetopsFilterState state;
     uint64_t total = 0;
     hip_check(setops_filter_count(a, state, &total, st), "setops_filter (count)");
     out->hashes.reserve(total * 8 + 16, st);
+    if (values != SETOPS_VALUES_NONE) {
+        out->abunds.reserve(total * 8 + 16, st);
+        out->abund_max = values == SETOPS_VALUES_TAKE ? abund_max : s.abund_max;
+    }
     uint32_t trouble = 0;
-    hip_check(setops_filter_write(a, state, out->hashes.as<uint64_t>(), total, &trouble, st), "setops_filter (write)");
+    hip_check(setops_filter_write(a, state, out->hashes.as<uint64_t>(), total, &trouble, st, out->abunds.as<uint64_t>()), "setops_filter (write)");
     if (trouble) throw err_internal("the filter wrote another number of hashes than it had counted");
-    fetch_offsets(*out, st);
+    sketchset_fetch_offsets(*out, st);
     if (out->total != total) throw err_internal("the filter's offsets do not end at its total");
-    finish_rows(*out, &s);
+    sketchset_finish_rows(*out, &s);
     return out.release();
 }
 
-}  // namespace
+}  // namespace smg
 
 extern "C" {
 
@@ -109,12 +116,25 @@ void smgpu_setops_key_form(uint64_t max_hash, uint64_t n_groups, uint32_t* hbits
 
 uint64_t smgpu_setops_merge_workspace_bytes(uint64_t total, uint64_t n_groups) { return setops_merge_workspace_bytes(total, n_groups); }
 
+uint64_t smgpu_setops_merge_values_workspace_bytes(uint64_t total, uint64_t n_groups) { return setops_merge_values_workspace_bytes(total, n_groups); }
+
 uint64_t smgpu_setops_merge_raw(const uint64_t* d_hashes, const uint64_t* d_offsets, uint64_t n, uint64_t total, const uint32_t* d_groups, uint64_t n_groups,
                                 const uint32_t* d_need, uint32_t need_all, uint64_t max_hash, uint64_t num, uint64_t* d_out_hashes,
                                 uint64_t* d_out_offsets, uint64_t* d_result, void* d_workspace, uint64_t workspace_bytes, void* stream) {
+    return smgpu_setops_merge_values_raw(d_hashes, nullptr, d_offsets, n, total, d_groups, n_groups, d_need, need_all, max_hash, num, SETOPS_MERGE_FLAT,
+                                         d_out_hashes, nullptr, d_out_offsets, d_result, d_workspace, workspace_bytes, stream);
+}
+
+uint64_t smgpu_setops_merge_values_raw(const uint64_t* d_hashes, const uint64_t* d_abunds, const uint64_t* d_offsets, uint64_t n, uint64_t total,
+                                       const uint32_t* d_groups, uint64_t n_groups, const uint32_t* d_need, uint32_t need_all, uint64_t max_hash,
+                                       uint64_t num, uint32_t values, uint64_t* d_out_hashes, uint64_t* d_out_abunds, uint64_t* d_out_offsets,
+                                       uint64_t* d_result, void* d_workspace, uint64_t workspace_bytes, void* stream) {
     uint64_t ret = ~0ull;
     landing_void([&] {
-        const char* me = "smgpu_setops_merge_raw";
+        const char* me = values ? "smgpu_setops_merge_values_raw" : "smgpu_setops_merge_raw";
+        if (values > SETOPS_MERGE_COUNT) throw err_internal(std::string(me) + ": values is 0 (flat), 1 (sum) or 2 (count)");
+        if (values == SETOPS_MERGE_SUM && total) check_raw(d_abunds, me, "d_abunds");
+        if (values && total) check_raw(d_out_abunds, me, "d_out_abunds");
         check_raw(d_result, me, "d_result");
         check_raw(d_workspace, me, "d_workspace");
         check_raw(d_out_offsets, me, "d_out_offsets");
@@ -124,8 +144,8 @@ uint64_t smgpu_setops_merge_raw(const uint64_t* d_hashes, const uint64_t* d_offs
             throw err_internal(std::string(me) + ": 2^32 hashes, rows or groups are not taken");
         if (n && n_groups == 0) throw err_internal(std::string(me) + ": rows without a group");
         if (num && (need_all || d_need)) throw err_internal(std::string(me) + ": a num cut goes with the union only");
-        if (workspace_bytes < setops_merge_workspace_bytes(total, n_groups))
-            throw err_internal(std::string(me) + ": the workspace is smaller than smgpu_setops_merge_workspace_bytes says");
+        if (workspace_bytes < (values ? setops_merge_values_workspace_bytes(total, n_groups) : setops_merge_workspace_bytes(total, n_groups)))
+            throw err_internal(std::string(me) + ": the workspace is smaller than smgpu_setops_merge_" + (values ? "values_" : "") + "workspace_bytes says");
         (void)DeviceCtx::get();                                      // no device: say so, not "invalid device"
         hipStream_t st = (hipStream_t)stream;
         if (n) {
@@ -140,8 +160,9 @@ uint64_t smgpu_setops_merge_raw(const uint64_t* d_hashes, const uint64_t* d_offs
             for (uint32_t g : groups)
                 if (g >= n_groups) throw err_internal(std::string(me) + ": a group number outside 0 .. n_groups - 1");
         }
-        const SetopsMergeArgs a{d_hashes, d_offsets, n, total, d_groups, n_groups, d_need, need_all, max_hash, num, d_out_hashes, d_out_offsets, d_result,
-                                d_workspace, workspace_bytes};
+        SetopsMergeArgs a{d_hashes, d_offsets, n, total, d_groups, n_groups, d_need, need_all, max_hash, num, d_out_hashes, d_out_offsets, d_result,
+                          d_workspace, workspace_bytes};
+        a.values = values; a.d_abunds = d_abunds; a.d_out_abunds = d_out_abunds;
         uint64_t out_total = 0;
         hip_check(setops_merge_run(a, &out_total, st), "setops_merge");
         ret = out_total;
@@ -155,9 +176,29 @@ uint64_t smgpu_setops_filter_raw(const uint64_t* d_hashes, const uint64_t* d_off
                                  const uint64_t* d_other_offsets, uint64_t other_len, uint32_t keep_present, uint32_t grid, uint64_t* d_out_hashes,
                                  uint64_t capacity, uint64_t* d_out_offsets, uint64_t* d_result, void* d_workspace, uint64_t workspace_bytes,
                                  void* stream) {
+    return smgpu_setops_filter_values_raw(d_hashes, nullptr, d_offsets, n, total, d_other_hashes, nullptr, d_other_offsets, other_len, keep_present,
+                                          SETOPS_VALUES_NONE, 0, ~0ull, grid, d_out_hashes, nullptr, capacity, d_out_offsets, d_result, d_workspace,
+                                          workspace_bytes, stream);
+}
+
+uint64_t smgpu_setops_filter_values_raw(const uint64_t* d_hashes, const uint64_t* d_abunds, const uint64_t* d_offsets, uint64_t n, uint64_t total,
+                                        const uint64_t* d_other_hashes, const uint64_t* d_other_abunds, const uint64_t* d_other_offsets,
+                                        uint64_t other_len, uint32_t keep_present, uint32_t values, uint64_t range_lo, uint64_t range_hi, uint32_t grid,
+                                        uint64_t* d_out_hashes, uint64_t* d_out_abunds, uint64_t capacity, uint64_t* d_out_offsets, uint64_t* d_result,
+                                        void* d_workspace, uint64_t workspace_bytes, void* stream) {
     uint64_t ret = ~0ull;
     landing_void([&] {
-        const char* me = "smgpu_setops_filter_raw";
+        const char* me = values ? "smgpu_setops_filter_values_raw" : "smgpu_setops_filter_raw";
+        if (values > SETOPS_VALUES_RANGE) throw err_internal(std::string(me) + ": values is 0 (flat), 1 (carry), 2 (take) or 3 (range)");
+        if ((values == SETOPS_VALUES_CARRY || values == SETOPS_VALUES_RANGE) && total) check_raw(d_abunds, me, "d_abunds");
+        if (values && capacity) check_raw(d_out_abunds, me, "d_out_abunds");
+        if (values == SETOPS_VALUES_TAKE) {
+            if (!keep_present) throw err_internal(std::string(me) + ": take keeps the hashes the other sketch holds (keep_present = 1)");
+            if (d_other_offsets || other_len) check_raw(d_other_abunds, me, "d_other_abunds");
+        }
+        if (values == SETOPS_VALUES_RANGE) {                         // no other sketch: an empty one stands in, and nothing is looked up
+            if (d_other_offsets || other_len) throw err_internal(std::string(me) + ": the range filter takes no other sketch");
+        }
         check_raw(d_result, me, "d_result");
         check_raw(d_workspace, me, "d_workspace");
         check_raw(d_out_offsets, me, "d_out_offsets");
@@ -179,15 +220,16 @@ uint64_t smgpu_setops_filter_raw(const uint64_t* d_hashes, const uint64_t* d_off
             hip_check(hipStreamSynchronize(st), "sync");
             if (ends[1] < ends[0] || ends[1] - ends[0] != total) throw err_internal(std::string(me) + ": the offsets do not span `total` hashes");
         }
-        const SetopsFilterArgs a{d_hashes, d_offsets, n, total, d_other_hashes, d_other_offsets, other_len, keep_present, grid, d_out_offsets, d_result,
-                                 d_workspace, workspace_bytes};
+        SetopsFilterArgs a{d_hashes, d_offsets, n, total, d_other_hashes, d_other_offsets, other_len, keep_present, grid, d_out_offsets, d_result,
+                           d_workspace, workspace_bytes};
+        a.values = values; a.d_abunds = d_abunds; a.d_other_abunds = d_other_abunds; a.range_lo = range_lo; a.range_hi = range_hi;
         SetopsFilterState state;
         uint64_t out_total = 0;
         hip_check(setops_filter_count(a, state, &out_total, st), "setops_filter (count)");
         ret = out_total;
         if (out_total > capacity) return;                            // the caller runs again with room
         uint32_t trouble = 0;
-        hip_check(setops_filter_write(a, state, d_out_hashes, capacity, &trouble, st), "setops_filter (write)");
+        hip_check(setops_filter_write(a, state, d_out_hashes, capacity, &trouble, st, d_out_abunds), "setops_filter (write)");
         if (trouble) {
             ret = ~0ull;
             throw err_internal(std::string(me) + ": the write kept another number of hashes than the count");
@@ -198,9 +240,17 @@ uint64_t smgpu_setops_filter_raw(const uint64_t* d_hashes, const uint64_t* d_off
 
 SmgpuSketchSet* smgpu_sketchset_merge_groups(const SmgpuSketchSet* p, const uint32_t* groups, uint64_t n_groups, const uint32_t* need, uint32_t need_all,
                                              const char* const* names) {
+    return smgpu_sketchset_merge_groups_values(p, groups, n_groups, need, need_all, names, 0);
+}
+
+SmgpuSketchSet* smgpu_sketchset_merge_groups_values(const SmgpuSketchSet* p, const uint32_t* groups, uint64_t n_groups, const uint32_t* need,
+                                                    uint32_t need_all, const char* const* names, uint32_t count_rows) {
     return landing<SmgpuSketchSet*>([&]() -> SmgpuSketchSet* {
         const SketchSet* s = reinterpret_cast<const SketchSet*>(p);
         if (!s) throw err_internal("smgpu_sketchset_merge_groups: null pointer");
+        if (count_rows && s->has_abunds())
+            throw err_internal("count_rows counts the rows of a flat set: this set carries abundance, and its merge sums them (flatten() first)");
+        const uint32_t values = count_rows ? SETOPS_MERGE_COUNT : s->has_abunds() ? SETOPS_MERGE_SUM : SETOPS_MERGE_FLAT;
         if (s->n) need_params(*s);
         if (s->n && n_groups == 0) throw err_internal("smgpu_sketchset_merge_groups: rows without a group");
         if (n_groups > 0xfffffffeull || s->total > SETOPS_MERGE_MAX_HASHES) throw err_internal("smgpu_sketchset_merge_groups: 2^32 hashes or groups are not taken");
@@ -211,22 +261,30 @@ SmgpuSketchSet* smgpu_sketchset_merge_groups(const SmgpuSketchSet* p, const uint
         DeviceCtx& ctx = DeviceCtx::get();
         std::lock_guard<std::recursive_mutex> g(ctx.mutex());
         hipStream_t st = ctx.stream();
-        std::unique_ptr<SketchSet> out = like(*s, n_groups);
+        std::unique_ptr<SketchSet> out = sketchset_like(*s, n_groups);
         out->offsets.reserve((n_groups + 1) * 8, st);
-        const uint64_t ws_bytes = setops_merge_workspace_bytes(s->total, n_groups);
+        const uint64_t ws_bytes = values ? setops_merge_values_workspace_bytes(s->total, n_groups) : setops_merge_workspace_bytes(s->total, n_groups);
         AsyncBuf ws((size_t)ws_bytes, st), d_result(64, st), d_groups((s->n + 1) * 4, st), d_need((n_groups + 1) * 4, st), d_tmp((s->total + 2) * 8, st);
+        AsyncBuf d_tmp_abunds(values ? (s->total + 2) * 8 : 8, st);
         if (groups && s->n) hip_check(hipMemcpyAsync(d_groups.p, groups, s->n * 4, hipMemcpyHostToDevice, st), "H2D");
         if (need && n_groups) hip_check(hipMemcpyAsync(d_need.p, need, n_groups * 4, hipMemcpyHostToDevice, st), "H2D");
-        const SetopsMergeArgs a{s->hashes.as<uint64_t>(), s->offsets.as<uint64_t>(), s->n, s->total, groups ? d_groups.as<uint32_t>() : nullptr, n_groups,
-                                need ? d_need.as<uint32_t>() : nullptr, need_all, s->max_hash, s->num, d_tmp.as<uint64_t>(), out->offsets.as<uint64_t>(),
-                                d_result.as<uint64_t>(), ws.p, ws_bytes};
+        SetopsMergeArgs a{s->hashes.as<uint64_t>(), s->offsets.as<uint64_t>(), s->n, s->total, groups ? d_groups.as<uint32_t>() : nullptr, n_groups,
+                          need ? d_need.as<uint32_t>() : nullptr, need_all, s->max_hash, s->num, d_tmp.as<uint64_t>(), out->offsets.as<uint64_t>(),
+                          d_result.as<uint64_t>(), ws.p, ws_bytes};
+        a.values = values; a.d_abunds = s->abunds.as<uint64_t>(); a.d_out_abunds = values ? d_tmp_abunds.as<uint64_t>() : nullptr;
         uint64_t total = 0;
         hip_check(setops_merge_run(a, &total, st), "setops_merge");
         out->hashes.reserve(total * 8 + 16, st);
         if (total) hip_check(hipMemcpyAsync(out->hashes.p, d_tmp.p, total * 8, hipMemcpyDeviceToDevice, st), "D2D");
-        fetch_offsets(*out, st);
+        if (values) {
+            out->abunds.reserve(total * 8 + 16, st);
+            if (total) hip_check(hipMemcpyAsync(out->abunds.p, d_tmp_abunds.p, total * 8, hipMemcpyDeviceToDevice, st), "D2D");
+            // (a sum is not bounded by its addends' bound: the wide angular form; a count is at most the set's rows)
+            out->abund_max = count_rows ? s->n : ~0ull;
+        }
+        sketchset_fetch_offsets(*out, st);
         if (out->total != total) throw err_internal("the merge's offsets do not end at its total");
-        finish_rows(*out, nullptr);
+        sketchset_finish_rows(*out, nullptr);
         for (uint64_t gi = 0; names && gi < n_groups; ++gi)
             if (names[gi]) out->rows[gi].name = names[gi];
         return reinterpret_cast<SmgpuSketchSet*>(out.release());
@@ -280,7 +338,7 @@ SmgpuSketchSet* smgpu_sketchset_downsample(const SmgpuSketchSet* p, uint64_t max
         DeviceCtx& ctx = DeviceCtx::get();
         std::lock_guard<std::recursive_mutex> g(ctx.mutex());
         hipStream_t st = ctx.stream();
-        std::unique_ptr<SketchSet> out = like(*s, s->n);
+        std::unique_ptr<SketchSet> out = sketchset_like(*s, s->n);
         out->max_hash = max_hash;
         // every row ends where its hashes pass max_hash (rows ascend): sizes at the cutoff, their prefix sums, one prefix gather
         std::vector<uint64_t> sizes(s->n + 1, 0);
@@ -298,8 +356,14 @@ SmgpuSketchSet* smgpu_sketchset_downsample(const SmgpuSketchSet* p, uint64_t max
         hip_check(hipMemcpyAsync(out->offsets.p, out->host_offsets.data(), (s->n + 1) * 8, hipMemcpyHostToDevice, st), "H2D");
         hip_check(csr_prefix_gather_launch(s->hashes.as<uint64_t>(), s->offsets.as<uint64_t>(), out->offsets.as<uint64_t>(), (uint32_t)s->n,
                                            out->hashes.as<uint64_t>(), st), "csr_prefix_gather");
+        if (s->has_abunds()) {                                       // the same prefix of every row, in the other column
+            out->abunds.reserve(out->total * 8 + 16, st);
+            out->abund_max = s->abund_max;
+            hip_check(csr_prefix_gather_launch(s->abunds.as<uint64_t>(), s->offsets.as<uint64_t>(), out->offsets.as<uint64_t>(), (uint32_t)s->n,
+                                               out->abunds.as<uint64_t>(), st), "csr_prefix_gather");
+        }
         hip_check(hipStreamSynchronize(st), "sync");
-        finish_rows(*out, s);
+        sketchset_finish_rows(*out, s);
         return reinterpret_cast<SmgpuSketchSet*>(out.release());
     });
 }

@@ -210,6 +210,12 @@ SmgpuSketchSet* smgpu_sketchset_subset(const SmgpuSketchSet* p, const uint64_t* 
         if (n) hip_check(hipMemcpyAsync(d_rows.p, rows, n * 8, hipMemcpyHostToDevice, st), "H2D");
         hip_check(copy_rows_launch(s->hashes.as<uint64_t>(), s->offsets.as<uint64_t>(), d_rows.as<uint64_t>(), n,
                                    out->offsets.as<uint64_t>(), out->hashes.as<uint64_t>(), st), "copy_rows");
+        if (s->has_abunds()) {                                      // the same row gather, in the other column
+            out->abunds.reserve((out->total + 1) * 8, st);
+            out->abund_max = s->abund_max;
+            hip_check(copy_rows_launch(s->abunds.as<uint64_t>(), s->offsets.as<uint64_t>(), d_rows.as<uint64_t>(), n,
+                                       out->offsets.as<uint64_t>(), out->abunds.as<uint64_t>(), st), "copy_rows");
+        }
         hip_check(hipStreamSynchronize(st), "sync");
         return reinterpret_cast<SmgpuSketchSet*>(out.release());
     });
@@ -249,13 +255,16 @@ SourmashKmerMinHash* smgpu_sketchset_get(const SmgpuSketchSet* p, uint64_t index
         if (s->host_offsets.size() != s->n + 1) throw err_internal("smgpu_sketchset_get needs a set made by smgpu_sketchset_load");
         const uint64_t lo = s->host_offsets[index], len = s->host_offsets[index + 1] - lo;
         std::unique_ptr<KmerMinHash> mh(new KmerMinHash(0, s->ksize * (s->hash_function == HF_DNA ? 1 : 3), s->hash_function,
-                                                        s->seed, false, (uint32_t)s->num));
+                                                        s->seed, s->has_abunds(), (uint32_t)s->num));
         mh->max_hash = s->max_hash;
         mh->mins.resize(len);
+        if (s->has_abunds()) mh->abunds.resize(len);                // (an abundance set gives abundance sketches)
         mh->touch();
         DeviceCtx& ctx = DeviceCtx::get();
         std::lock_guard<std::recursive_mutex> g(ctx.mutex());
         if (len) hip_check(hipMemcpyAsync(mh->mins.data(), s->hashes.as<uint64_t>() + lo, len * 8, hipMemcpyDeviceToHost, ctx.stream()), "D2H");
+        if (len && s->has_abunds())
+            hip_check(hipMemcpyAsync(mh->abunds.data(), s->abunds.as<uint64_t>() + lo, len * 8, hipMemcpyDeviceToHost, ctx.stream()), "D2H");
         hip_check(hipStreamSynchronize(ctx.stream()), "sync");
         return reinterpret_cast<SourmashKmerMinHash*>(mh.release());
     });
@@ -441,6 +450,7 @@ const uint8_t* smgpu_sketchset_to_json(const SmgpuSketchSet* p, const uint64_t* 
     return landing<const uint8_t*>([&]() -> const uint8_t* {
         const SketchSet* s = reinterpret_cast<const SketchSet*>(p);
         if (!size) throw err_internal("null pointer");
+        refuse_abundance_writer(*s, "smgpu_sketchset_to_json");
         if (s->n && s->ksize == 0) throw err_internal("the set's sketches do not share one set of parameters, or track abundance: it cannot be written");
         DeviceCtx& ctx = DeviceCtx::get();
         std::lock_guard<std::recursive_mutex> g(ctx.mutex());
@@ -508,6 +518,7 @@ void smgpu_sigwriter_add(SmgpuSigWriter* w, const SmgpuSketchSet* p, const char*
         SigWriterHandle* h = reinterpret_cast<SigWriterHandle*>(w);
         const SketchSet* s = reinterpret_cast<const SketchSet*>(p);
         if (!h || !h->w || !s) throw err_internal("null pointer");
+        refuse_abundance_writer(*s, "smgpu_sigwriter_add");
         DeviceCtx& ctx = DeviceCtx::get();
         std::lock_guard<std::recursive_mutex> g(ctx.mutex());
         hipStream_t st = ctx.stream();

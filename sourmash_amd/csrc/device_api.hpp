@@ -116,7 +116,7 @@ hipError_t sort_report_launch(const unsigned long long* d_n, const uint64_t* d_n
 // (key, value) pairs sorted by the low `bits` bits of the key (stable), and runs of equal (a, b) pairs with their lengths
 size_t sort_pairs_temp_bytes(uint64_t n);
 hipError_t sort_pairs(const uint64_t* d_keys_in, uint64_t* d_keys_out, const uint64_t* d_vals_in, uint64_t* d_vals_out, uint64_t n,
-                      int bits, void* d_temp, size_t temp_bytes, hipStream_t stream);
+                      int bits, void* d_temp, size_t temp_bytes, hipStream_t stream, int begin_bit = 0);     // (orders by bits [begin_bit, begin_bit + bits))
 size_t rle_pairs_temp_bytes(uint64_t n);
 hipError_t rle_pairs(const uint64_t* d_a, const uint64_t* d_b, uint64_t n, uint64_t* d_out_a, uint64_t* d_out_b, uint64_t* d_counts,
                      uint64_t* d_n_out, void* d_temp, size_t temp_bytes, hipStream_t stream);
@@ -288,8 +288,15 @@ struct SetopsMergeArgs {
     uint64_t *d_out_hashes, *d_out_offsets, *d_result;
     void* d_workspace;
     uint64_t workspace_bytes;
+    // values (setops_core.hpp: SetopsMergeValues).  SUM: d_abunds is aligned with d_hashes and d_out_abunds (room for `total`)
+    // gets, beside every kept hash, the wrapping u64 sum of the abundances of the group's rows that hold it; COUNT: d_out_abunds
+    // gets the number of those rows and d_abunds is not read.  The workspace is setops_merge_values_workspace_bytes' then.
+    uint32_t values = 0;
+    const uint64_t* d_abunds = nullptr;
+    uint64_t* d_out_abunds = nullptr;
 };
 size_t setops_merge_workspace_bytes(uint64_t total, uint64_t n_groups);
+size_t setops_merge_values_workspace_bytes(uint64_t total, uint64_t n_groups);
 // Synchronises the stream.  hipErrorInvalidValue: an argument smgpu_setops_merge_raw refuses.
 hipError_t setops_merge_run(const SetopsMergeArgs& args, uint64_t* total_out, hipStream_t stream);
 // Filter: row r of the result = the hashes of row r that are (keep_present != 0) or are not members of the other sketch.
@@ -305,6 +312,11 @@ struct SetopsFilterArgs {
     uint64_t *d_out_offsets, *d_result;
     void* d_workspace;
     uint64_t workspace_bytes;
+    // values (setops_core.hpp: SetopsValueMode).  CARRY / RANGE: d_abunds is aligned with d_hashes; TAKE: d_other_abunds is aligned
+    // with d_other_hashes and keep_present is 1; RANGE: no other sketch, a hash is kept when range_lo <= its abundance <= range_hi.
+    uint32_t values = 0;
+    const uint64_t *d_abunds = nullptr, *d_other_abunds = nullptr;
+    uint64_t range_lo = 0, range_hi = ~0ull;
 };
 // what the count leaves for the write (the workspace keeps the rest)
 struct SetopsFilterState {
@@ -316,9 +328,16 @@ size_t setops_filter_workspace_bytes(uint64_t n, uint64_t total, uint64_t other_
 // The two modes of the one kernel, with the scan of the counts between them.  The count writes d_out_offsets and reads the total
 // back (it synchronises the stream), so that the caller can make room; the write puts the kept hashes into d_out_hashes (room for
 // `capacity` >= the total) and synchronises.  *trouble: setops_core.hpp's SetopsTrouble -- then the output holds nothing of use.
+// With values, d_out_abunds (the same capacity) gets every kept hash's value at the same position.
 hipError_t setops_filter_count(const SetopsFilterArgs& args, SetopsFilterState& state, uint64_t* total_out, hipStream_t stream);
 hipError_t setops_filter_write(const SetopsFilterArgs& args, const SetopsFilterState& state, uint64_t* d_out_hashes, uint64_t capacity,
-                               uint32_t* trouble, hipStream_t stream);
+                               uint32_t* trouble, hipStream_t stream, uint64_t* d_out_abunds = nullptr);
+
+// ---- abund_set.hip (the abundance column of a resident collection) ------------------------------------------------------------
+// d_result (2 x u64): [0] the largest of d_abunds[0, total), [1] the first position of a 0 (2^64 - 1: none).  Does not synchronise.
+hipError_t abund_check_launch(const uint64_t* d_abunds, uint64_t total, uint64_t* d_result, hipStream_t stream);
+// d_sums[r] = the wrapping u64 sum of d_abunds[d_offsets[r], d_offsets[r + 1])
+hipError_t abund_row_sums_launch(const uint64_t* d_abunds, const uint64_t* d_offsets, uint64_t n, uint64_t* d_sums, hipStream_t stream);
 
 // ---- synth.hip --------------------------------------------------------------------
 hipError_t synth_dna_launch(uint8_t* d_out, uint64_t start, uint64_t n, uint64_t seed, uint64_t record_len,

@@ -70,12 +70,13 @@ size_t sort_pairs_temp_bytes(uint64_t n) {
 }
 
 hipError_t sort_pairs(const uint64_t* d_keys_in, uint64_t* d_keys_out, const uint64_t* d_vals_in, uint64_t* d_vals_out, uint64_t n,
-                      int bits, void* d_temp, size_t temp_bytes, hipStream_t stream) {
+                      int bits, void* d_temp, size_t temp_bytes, hipStream_t stream, int begin_bit) {
     if (n == 0) return hipSuccess;
-    if (temp_bytes < sort_pairs_temp_bytes(n)) return hipErrorInvalidValue;
+    if (temp_bytes < sort_pairs_temp_bytes(n) || begin_bit < 0 || begin_bit > 63) return hipErrorInvalidValue;
     if (bits < 1) bits = 1;
-    if (bits > 64) bits = 64;
-    return rocprim::radix_sort_pairs(d_temp, temp_bytes, d_keys_in, d_keys_out, d_vals_in, d_vals_out, (size_t)n, 0u, (unsigned)bits, stream);
+    if (bits > 64 - begin_bit) bits = 64 - begin_bit;
+    return rocprim::radix_sort_pairs(d_temp, temp_bytes, d_keys_in, d_keys_out, d_vals_in, d_vals_out, (size_t)n, (unsigned)begin_bit,
+                                     (unsigned)(begin_bit + bits), stream);
 }
 
 size_t rle_pairs_temp_bytes(uint64_t n) {

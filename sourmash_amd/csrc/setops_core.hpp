@@ -1,7 +1,9 @@
 // setops_core.hpp -- the rules of the set algebra on a CSR collection (setops.hip: merge by group, intersect, subtract) that can be
 // stated without a GPU: the key form of the merge, its keep rule and num cut, the row offsets of its result, the membership rule of
-// the row filter over a loaded value, and the position arithmetic of the ordered compaction.  Compiled for the device by setops.hip
-// and for the host by capi_setops.cpp and tests/native/setops_core_emul.cpp.
+// the row filter over a loaded value, and the position arithmetic of the ordered compaction; and for sets that carry abundances the
+// value modes of the filter with their range test, the payload the summing merge sorts with, and the run sum taken from one scan.
+// Compiled for the device by setops.hip and for the host by capi_setops.cpp, capi_abund_set.cpp, tests/native/setops_core_emul.cpp
+// and tests/native/abund_set_core_emul.cpp.
 #pragma once
 #include <stdint.h>
 
@@ -118,6 +120,50 @@ SMG_HD bool setops_search(const uint64_t* row, uint64_t n, uint64_t x) {
     }
     return lo < n && row[lo] == x;
 }
+
+// the same search with the answer a value mover needs: the position of x in the row, SETOPS_NOT_FOUND when the row does not hold it.
+// One statement for both address spaces: the row-wise filter calls it on a partner staged in LDS and on one left in global memory.
+constexpr uint64_t SETOPS_NOT_FOUND = ~0ull;
+SMG_HD uint64_t setops_find(const uint64_t* row, uint64_t n, uint64_t x) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (row[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo < n && row[lo] == x ? lo : SETOPS_NOT_FOUND;
+}
+// the membership rule with a position for an answer: no lookup in an empty sketch, none for x > other_max
+template <class Find>
+SMG_HD uint64_t setops_member_at(uint64_t x, uint64_t other_n, uint64_t other_max, const Find& find) {
+    if (other_n == 0 || x > other_max) return SETOPS_NOT_FOUND;
+    return find(x);
+}
+
+// ---- values that move with the hashes (abundance sets) --------------------------------------------------------------------------
+// What the filter does with values.  NONE: a flat set, no value is read or written.  CARRY: a kept hash keeps the receiver's own
+// abundance (subtract, intersect on an abundance set).  TAKE: a hash is kept when the other sketch holds it and takes the OTHER's
+// abundance at the found position (inflate).  RANGE: no other sketch; a hash is kept when its own abundance lies in [lo, hi], and
+// keeps it (sig filter).  Every stored abundance is >= 1 (MinHash.set_abundances drops zeros).
+enum SetopsValueMode : uint32_t { SETOPS_VALUES_NONE = 0, SETOPS_VALUES_CARRY = 1, SETOPS_VALUES_TAKE = 2, SETOPS_VALUES_RANGE = 3 };
+// the range test, inclusive at both ends; "no upper bound" is hi = 2^64 - 1; lo > hi keeps nothing
+SMG_HD bool setops_in_range(uint64_t a, uint64_t lo, uint64_t hi) { return lo <= a && a <= hi; }
+// the value a kept hash is written with: its own (`own`) or the other's at the found position (`taken`)
+SMG_HD uint64_t setops_filter_value(uint32_t mode, uint64_t own, uint64_t taken) { return mode == SETOPS_VALUES_TAKE ? taken : own; }
+
+// What the merge writes beside a kept hash.  SUM: the sum of the abundances of the group's rows that hold it, wrapping u64
+// (KmerMinHash::merge).  COUNT: the number of those rows (the run's length).
+enum SetopsMergeValues : uint32_t { SETOPS_MERGE_FLAT = 0, SETOPS_MERGE_SUM = 1, SETOPS_MERGE_COUNT = 2 };
+// The sort's payload of a summing merge: the pair's group above j, the hash's position in the input (both fit 32 bits under
+// SETOPS_MERGE_MAX_HASHES and the group limit).  The abundance of a sorted pair is abunds[base + j].
+SMG_HD uint64_t setops_payload(uint64_t group, uint64_t j) { return (group << 32) | j; }
+SMG_HD uint64_t setops_payload_group(uint64_t p) { return p >> 32; }
+SMG_HD uint64_t setops_payload_pos(uint64_t p) { return p & 0xffffffffull; }
+// A run's sum from ONE inclusive scan (wrapping u64, so exact modulo 2^64 and the same on every run) of the sorted pairs'
+// abundances: the run covers the sorted pairs [start, start + count), start from the exclusive scan of the runs' counts.
+SMG_HD uint64_t setops_run_sum(const uint64_t* scan, uint64_t start, uint64_t count) {
+    return scan[start + count - 1] - (start ? scan[start - 1] : 0ull);
+}
+SMG_HD uint64_t setops_merge_value(uint32_t mode, uint64_t count, uint64_t sum) { return mode == SETOPS_MERGE_COUNT ? count : sum; }
 
 // ---- pieces of the filter -------------------------------------------------------------------------------------------------------
 // work items of a row of len hashes: one for an empty or short row, ceil(len / SETOPS_SPLIT) otherwise

@@ -149,15 +149,26 @@ class SketchSet(RustObject):
     Built from MinHash objects (`SketchSet(minhashes)`) or straight from files (`SketchSet.load(paths, ...)`:
     .sig / .sig.gz / .zip / directories / path lists, parsed by the native loader without creating a Python
     object per sketch).  A loaded set answers compare / search / gather by row number; `manifest[row]` says
-    which signature that is, `signature(row)` materialises it."""
+    which signature that is, `signature(row)` materialises it.
+
+    A set may carry abundances (`SketchSet(minhashes, track_abundance=True)`, `from_csr(..., abunds=)`): a uint64 column aligned
+    with the hashes, every value at least 1.  See `track_abundance`, `abund_sums`, `flatten`, `inflate`, `filter_abund`, `merge`,
+    `compare_angular`; `to_json`, `save` and SketchSetWriter write flat sets only."""
     __dealloc_func__ = lib.smgpu_sketchset_free
     _keep = ()
     _manifest = None
 
-    def __init__(self, minhashes):
+    def __init__(self, minhashes, track_abundance=False):
+        """track_abundance=True: an abundance set -- every sketch must track abundance and share parameters; the set then carries a
+        u64 abundance column beside its hashes (smgpu_sketchset_new_abund).  Every method that reads hashes only (compare, overlaps,
+        search, gather, the *_many methods) sees such a set as its flattened self; subset, downsample, subtract and intersect
+        carry the abundances, merge sums them, inflate / filter_abund / compare_angular / abund_sums use them.  The default keeps
+        a flat set, of abundance sketches too."""
         self._keep = list(minhashes)
         ptrs, _alive = objptr_array(self._keep)
-        self._objptr = rustcall(lib.smgpu_sketchset_new, ptrs, len(self._keep))
+        self._objptr = rustcall(lib.smgpu_sketchset_new_abund if track_abundance else lib.smgpu_sketchset_new, ptrs, len(self._keep))
+        if track_abundance:
+            self._keep = ()                                             # (the set has host offsets and manifest rows of its own)
 
     @classmethod
     def load(cls, paths, *, ksize=0, moltype=None, scaled=0, threads=0):
@@ -166,15 +177,17 @@ class SketchSet(RustObject):
                                          moltype.encode() if moltype else None, int(scaled or 0), int(threads)))
 
     @classmethod
-    def from_csr(cls, hashes, offsets, *, ksize, scaled=0, num=0, seed=42, moltype="DNA", names=None, filenames=None):
+    def from_csr(cls, hashes, offsets, *, ksize, scaled=0, num=0, seed=42, moltype="DNA", names=None, filenames=None, abunds=None):
         """n flat sketches from device tensors (smgpu_sketchset_from_csr): row r = hashes[offsets[r]:offsets[r + 1]], ascending.
         hashes: int64 / uint64 device tensor (the bits are the hashes); offsets: int64 device tensor of n + 1 positions.  The rows
-        are copied.  names / filenames: one string per row for the manifest."""
+        are copied.  names / filenames: one string per row for the manifest.  abunds: an int64 / uint64 device tensor aligned with
+        hashes makes an abundance set (smgpu_sketchset_from_csr_abund); an abundance of 0 is refused."""
         from .device import _ptr, _torch
         from .minhash import _get_max_hash_for_scaled
         torch = _torch()
         assert hashes.is_cuda and hashes.is_contiguous() and hashes.element_size() == 8
         assert offsets.dtype == torch.int64 and offsets.is_cuda and offsets.is_contiguous() and offsets.numel() >= 1
+        _check_csr_abunds(abunds, hashes)
         n = offsets.numel() - 1
 
         def strings(values):
@@ -186,12 +199,18 @@ class SketchSet(RustObject):
             return (C.c_char_p * max(n, 1))(*values)
         hf = {"DNA": 1, "PROTEIN": 2, "DAYHOFF": 3, "HP": 4}[moltype.upper()]
         torch.cuda.current_stream().synchronize()                   # the library works on its own stream
+        max_hash = _get_max_hash_for_scaled(int(scaled)) if scaled else 0
+        if abunds is not None:
+            return cls._from_objptr(rustcall(lib.smgpu_sketchset_from_csr_abund, _ptr(hashes), _ptr(abunds), _ptr(offsets), n, int(ksize), hf, int(seed),
+                                             max_hash, int(num), strings(names), strings(filenames)))
         return cls._from_objptr(rustcall(lib.smgpu_sketchset_from_csr, _ptr(hashes), _ptr(offsets), n, int(ksize), hf, int(seed),
-                                         _get_max_hash_for_scaled(int(scaled)) if scaled else 0, int(num), strings(names), strings(filenames)))
+                                         max_hash, int(num), strings(names), strings(filenames)))
 
     @classmethod
-    def sketch_records(cls, seq, starts, *, ksize, scaled, seed=42, moltype="DNA", is_protein=False, ends=None):
-        """One flat scaled sketch per record of a device buffer, in one pass (smgpu_sketchset_sketch_records).
+    def sketch_records(cls, seq, starts, *, ksize, scaled, seed=42, moltype="DNA", is_protein=False, ends=None, track_abundance=False):
+        """One flat scaled sketch per record of a device buffer, in one pass (smgpu_sketchset_sketch_records).  track_abundance=True:
+        an abundance set -- a kept hash's abundance is the number of times its record holds it, as
+        MinHash(track_abundance=True).add_sequence counts (smgpu_sketchset_sketch_records_abund and its residue sibling).
 
         seq: uint8 device tensor; starts: int64 device tensor of n_records + 1 ascending offsets, record r =
         seq[starts[r]:starts[r + 1]].  ksize 1 .. 88 (longer k-mers: sketch the records one by one).
@@ -203,22 +222,25 @@ class SketchSet(RustObject):
         hf = _check_records(torch, seq, starts, moltype, is_protein, ends)
         torch.cuda.current_stream().synchronize()                   # the library works on its own stream
         lib.sourmash_err_clear()
+        ab = int(bool(track_abundance))
         if hf == 1:
-            ptr = lib.smgpu_sketchset_sketch_records(_ptr(seq), seq.numel(), _ptr(starts), starts.numel() - 1, int(ksize), int(seed),
-                                                     int(scaled))
+            ptr = lib.smgpu_sketchset_sketch_records_abund(_ptr(seq), seq.numel(), _ptr(starts), starts.numel() - 1, int(ksize), int(seed),
+                                                           int(scaled), ab)
         else:
-            ptr = lib.smgpu_sketchset_sketch_residue_records(_ptr(seq), seq.numel(), _ptr(starts), _ptr(ends) if ends is not None else None,
-                                                             starts.numel() - 1, int(ksize), hf, int(not is_protein), int(seed), int(scaled))
+            ptr = lib.smgpu_sketchset_sketch_residue_records_abund(_ptr(seq), seq.numel(), _ptr(starts), _ptr(ends) if ends is not None else None,
+                                                                   starts.numel() - 1, int(ksize), hf, int(not is_protein), int(seed), int(scaled), ab)
         code = lib.sourmash_err_get_last_code()
         if code:
             raise _records_error(code, decode_str(lib.sourmash_err_get_last_message()))
         return cls._from_objptr(ptr)
 
     @classmethod
-    def sketch_file(cls, path, *, ksize=31, scaled=1000, seed=42, moltype="DNA", input_is_protein=False):
+    def sketch_file(cls, path, *, ksize=31, scaled=1000, seed=42, moltype="DNA", input_is_protein=False, track_abundance=False):
         """One flat scaled sketch per record of a FASTA / FASTQ file (plain or gzip): the device parses the file and
         sketches every record in one pass (smgpu_sketchset_sketch_file); manifest[row] carries the record's name and the
         file name.  What that path does not take (k > 88, a file above its size limit) is sketched record by record.
+        track_abundance=True: an abundance set (manifest rows say with_abundance=True); the record-by-record way builds
+        MinHash(track_abundance=True) objects and a SketchSet(..., track_abundance=True) of them.
         moltype protein / dayhoff / hp (smgpu_sketchset_sketch_residue_file): ksize counts residues, the one-pass path takes
         1 .. 79; input_is_protein: the records are residues, otherwise DNA translated in six frames."""
         from .device import _residue_hash_function
@@ -227,28 +249,29 @@ class SketchSet(RustObject):
         hf = _residue_hash_function(moltype)
         if hf == 1 and input_is_protein:
             raise ValueError("input_is_protein goes with moltype protein, dayhoff or hp")
+        ab = int(bool(track_abundance))
         if hf == 1 and _records_path_takes(path, [int(ksize)]):
-            return cls._from_objptr(rustcall(lib.smgpu_sketchset_sketch_file, os.fsencode(path), int(ksize), int(seed), int(scaled)))
+            return cls._from_objptr(rustcall(lib.smgpu_sketchset_sketch_file_abund, os.fsencode(path), int(ksize), int(seed), int(scaled), ab))
         if hf != 1 and _residue_records_path_takes(path, [int(ksize)]):
-            return cls._from_objptr(rustcall(lib.smgpu_sketchset_sketch_residue_file, os.fsencode(path), int(ksize), hf,
-                                             int(not input_is_protein), int(seed), int(scaled)))
+            return cls._from_objptr(rustcall(lib.smgpu_sketchset_sketch_residue_file_abund, os.fsencode(path), int(ksize), hf,
+                                             int(not input_is_protein), int(seed), int(scaled), ab))
         from .minhash import MinHash
         mhs, names = [], []
         mol = {2: dict(is_protein=True), 3: dict(dayhoff=True), 4: dict(hp=True)}.get(hf, {})
         for name, seq in read_records(path):
-            mh = MinHash(0, int(ksize), scaled=int(scaled), seed=int(seed), **mol)
+            mh = MinHash(0, int(ksize), scaled=int(scaled), seed=int(seed), track_abundance=bool(track_abundance), **mol)
             if input_is_protein:
                 mh.add_protein(seq)
             else:
                 mh.add_sequence(seq, True)
             mhs.append(mh)
             names.append(name)
-        out = cls(mhs)
+        out = cls(mhs, track_abundance=bool(track_abundance))
         out.set_names(names, [path] * len(names))                   # (what to_json / save write; the manifest below says the same)
         sizes = out.sizes
         out._manifest = [dict(internal_location="", md5="", md5short="", ksize=int(ksize), moltype={1: "DNA", 2: "protein", 3: "dayhoff", 4: "hp"}[hf],
-                              num=0, scaled=int(scaled),
-                              n_hashes=int(sizes[i]), with_abundance=False, name=names[i], filename=path) for i in range(len(names))]
+                              num=0, scaled=int(scaled), n_hashes=int(sizes[i]), with_abundance=bool(track_abundance), name=names[i], filename=path)
+                         for i in range(len(names))]
         return out
 
     def __len__(self):
@@ -284,9 +307,59 @@ class SketchSet(RustObject):
         moltype = {1: "DNA", 2: "protein", 3: "dayhoff", 4: "hp"}[hf.value]
         return k.value, moltype, seed.value, _get_scaled_for_max_hash(mx.value) if mx.value else 0, num.value
 
+    @property
+    def track_abundance(self):
+        "does the set carry an abundance column beside its hashes?"
+        return bool(lib.smgpu_sketchset_track_abundance(self._get_objptr()))
+
+    @property
+    def abund_sums(self):
+        "MinHash.sum_abundances of every row as uint64 (wrapping), summed on the device (smgpu_sketchset_abund_sums)"
+        _need_abundance_set(self.track_abundance, "abund_sums")
+        out = np.zeros(max(len(self), 1), dtype=np.uint64)
+        self._methodcall(lib.smgpu_sketchset_abund_sums, out.ctypes.data_as(C.c_void_p))
+        return out[:len(self)]
+
     def minhash(self, row):
+        "the sketch of a row; an abundance set gives abundance sketches"
         from .minhash import MinHash
         return MinHash._from_objptr(self._methodcall(lib.smgpu_sketchset_get, int(row)))
+
+    def flatten(self):
+        "a flat copy of the set (device-to-device): the hashes without the abundances; the manifest says with_abundance=False"
+        return SketchSet._from_objptr(self._methodcall(lib.smgpu_sketchset_flatten))
+
+    def inflate(self, other):
+        """Every row's hashes that `other` holds, with `other`'s abundances (MinHash.inflate, `sig inflate`, and what -A does in
+        `sig intersect` / `sig subtract`) -> an abundance set.  This set is flat (flatten() an abundance set first; the reference
+        refuses the other order with the same words); `other` is an abundance MinHash, or an abundance SketchSet of one row or
+        of len(self) rows (row by row).  Parameters must match as for intersect."""
+        from .minhash import MinHash
+        is_mh = isinstance(other, MinHash)
+        if not is_mh and not isinstance(other, SketchSet):
+            raise TypeError("the other side is a MinHash or a SketchSet")
+        _check_inflate(self.track_abundance, other.track_abundance)
+        if is_mh:
+            return SketchSet._from_objptr(self._methodcall(lib.smgpu_sketchset_inflate_sketch, other._get_objptr()))
+        _check_other_rows(len(self), len(other))
+        return SketchSet._from_objptr(self._methodcall(lib.smgpu_sketchset_inflate, other._get_objptr()))
+
+    def filter_abund(self, min_abundance=1, max_abundance=None):
+        """Every row's hashes whose abundance a has min_abundance <= a and (max_abundance is None or a <= max_abundance), with
+        their abundances (`sig filter`) -> an abundance set.  A flat set is a ValueError."""
+        _need_abundance_set(self.track_abundance, "filter_abund")
+        lo, hi = _abund_range(min_abundance, max_abundance)
+        return SketchSet._from_objptr(self._methodcall(lib.smgpu_sketchset_filter_abund, lo, hi))
+
+    def compare_angular(self):
+        """-> f64 [n, n]: the angular similarity of every pair of rows, what compare_all_pairs(..., ignore_abundance=False) gives
+        for the same sketches: the integer sums of the abundance kernels on the set's own buffers, then the host's formula.  A flat
+        set is a ValueError."""
+        _need_abundance_set(self.track_abundance, "compare_angular")
+        n = len(self)
+        out = np.zeros((n, n), dtype=np.float64)
+        self._methodcall(lib.smgpu_sketchset_compare_angular, out.ctypes.data_as(C.c_void_p))
+        return out
 
     def set_names(self, names=None, filenames=None):
         """One name / file name per row: what the set's signatures are written with (to_json, save, SketchSetWriter) and what its
@@ -474,16 +547,22 @@ class SketchSet(RustObject):
 
 
     # ---- the result rows of gather (csrc/gather_rows.hip) ------------------------------------------------------------------------
-    def gather_stats_many(self, queries, threshold_bp=0, abunds=None):
+    def gather_stats_many(self, queries, threshold_bp=0, abunds=None, ignore_abundance=False):
         """gather_many, and for every pick the integers its result row is made of -> GatherStats.  One more pass over the resident
         sets: per pick |query ∩ row|, the query hashes it covered first (the rank's "remaining query ∩ match") and the sum of
         their abundances, and those abundances in hash order.  abunds: a flat uint64 array aligned with the queries' hashes (row
         after row, ascending within a row), or one array per query; None: every abundance is 1 and rows() gives the columns of
-        an ignore-abundance gather."""
+        an ignore-abundance gather.  Queries that are an abundance set bring their own: with abunds None their resident column is
+        what the pass reads (no host array, no upload); ignore_abundance=True gives the all-ones rows instead."""
         if not isinstance(queries, SketchSet):
             raise TypeError("the queries of a many-query search are a SketchSet")
+        if ignore_abundance:
+            abunds = None
         common_scaled = max(queries.params[3], self.params[3])
         thr = math.ceil(float(threshold_bp) / common_scaled) if threshold_bp and common_scaled else 0
+        if abunds is None and not ignore_abundance and queries.track_abundance:
+            ptr = rustcall(lib.smgpu_sketchset_gather_rows_many_resident, self._get_objptr(), queries._get_objptr(), None, int(thr), 1)
+            return GatherStats._from_handle(ptr, self, queries=queries, with_abundance=True, query_scaled=queries.params[3])
         flat = None
         if abunds is not None:
             if isinstance(abunds, (list, tuple)):
@@ -515,15 +594,20 @@ class SketchSet(RustObject):
 
 
     # ---- set algebra on the resident CSR (csrc/setops.hip): every method returns a NEW set, this one is unchanged ------------------
-    def merge(self, groups=None, *, min_rows=1, names=None):
+    def merge(self, groups=None, *, min_rows=1, names=None, count_rows=False):
         """The rows merged by group -> a set of G rows: row g holds the hashes that at least min_rows rows of group g hold.
         groups: one integer per row, any order, values 0 .. G - 1 with G = max + 1 (None: all rows in one group).  min_rows=1 is
         the union (MinHash.merge, `sig merge --flatten`), min_rows="all" the intersection of a group's rows (`sig intersect`).  A
         group without rows, or of fewer rows than an integer min_rows, gives an empty row.  A num set gives the num smallest of
-        the union, and takes min_rows=1 only.  names: one name per group."""
+        the union, and takes min_rows=1 only.  names: one name per group.
+        An abundance set gives an abundance set: a kept hash's abundance is the sum (uint64, wrapping) of the abundances of the
+        group's rows that hold it (MinHash.merge, `sig merge`).  count_rows=True, on a flat set: an abundance set whose abundance
+        is the number of rows of the group that hold the hash; on an abundance set it is a ValueError."""
+        _check_count_rows(count_rows, self.track_abundance)
         g_arr, n_groups, need, need_all, name_arr = _merge_plan(len(self), self.params[4], groups, min_rows, names)
-        return SketchSet._from_objptr(self._methodcall(lib.smgpu_sketchset_merge_groups, g_arr.ctypes.data_as(C.c_void_p) if g_arr is not None else None,
-                                                       n_groups, need.ctypes.data_as(C.c_void_p) if need is not None else None, need_all, name_arr))
+        return SketchSet._from_objptr(self._methodcall(lib.smgpu_sketchset_merge_groups_values, g_arr.ctypes.data_as(C.c_void_p) if g_arr is not None else None,
+                                                       n_groups, need.ctypes.data_as(C.c_void_p) if need is not None else None, need_all, name_arr,
+                                                       int(bool(count_rows))))
 
     def _filter(self, other, keep_present):
         from .minhash import MinHash
@@ -588,6 +672,43 @@ def _merge_plan(n_rows, num, groups, min_rows, names):
             raise ValueError("one name per group is needed")
         name_arr = (C.c_char_p * max(n_groups, 1))(*enc)
     return g_arr, n_groups, need, need_all, name_arr
+
+
+def _check_count_rows(count_rows, track_abundance):
+    if count_rows and track_abundance:
+        raise ValueError("count_rows counts the rows of a flat set: this set carries abundance and its merge sums them (flatten() first)")
+
+
+def _need_abundance_set(track_abundance, what):
+    if not track_abundance:
+        raise ValueError(f"{what} needs a set that carries abundance (SketchSet(minhashes, track_abundance=True), from_csr(..., abunds=...))")
+
+
+def _check_inflate(receiver_tracks, other_tracks):
+    "the reference's order (minhash.py:1078-1091): the receiver is flat, the other side carries the abundances"
+    if receiver_tracks or not other_tracks:
+        raise ValueError("inflate operates on a flat MinHash and takes a MinHash object with track_abundance=True")
+
+
+def _abund_range(min_abundance, max_abundance):
+    "-> (lo, hi) as the C entry takes them: no upper bound is 2^64 - 1"
+    lo = int(min_abundance)
+    hi = 0xffffffffffffffff if max_abundance is None else int(max_abundance)
+    if lo < 0 or hi < 0 or lo > 0xffffffffffffffff or hi > 0xffffffffffffffff:
+        raise ValueError("abundance bounds are unsigned 64-bit integers")
+    return lo, hi
+
+
+def _check_csr_abunds(abunds, hashes):
+    "from_csr: the abundance tensor is 64-bit integers, one per hash, on the device"
+    if abunds is None:
+        return
+    if abunds.is_floating_point() or abunds.is_complex() or abunds.element_size() != 8:
+        raise ValueError("the abundances are 64-bit integers (int64 / uint64: the bits are the values)")
+    if abunds.dim() != 1 or abunds.numel() != hashes.numel():
+        raise ValueError(f"the abundances must be as many as the hashes: {abunds.numel()} for {hashes.numel()}")
+    if not abunds.is_cuda or not abunds.is_contiguous():
+        raise ValueError("the abundances are a contiguous device tensor")
 
 
 def _check_other_rows(n_rows, n_other):
@@ -1277,11 +1398,15 @@ class LinearIndex(Index):
         items, sset, mhs = native
         with_abundance = [bool(mh.track_abundance and not ignore_abundance) for mh in mhs]
         abunds = None
-        if any(with_abundance):
-            # MinHash.hashes is ascending, as the set's rows are; a query whose abundances do not count carries ones
-            abunds = [np.fromiter(mh.hashes.values(), dtype=np.uint64, count=len(mh)) if w else np.ones(len(mh), dtype=np.uint64)
-                      for mh, w in zip(mhs, with_abundance)]
-        stats = sset.gather_stats_many(SketchSet([mh.flatten() for mh in mhs]), threshold_bp, abunds=abunds)
+        if all(with_abundance):
+            # every query brings abundances that count: an abundance set, whose resident column the pass reads where it lies
+            stats = sset.gather_stats_many(SketchSet(mhs, track_abundance=True), threshold_bp)
+        else:
+            if any(with_abundance):
+                # MinHash.hashes is ascending, as the set's rows are; a query whose abundances do not count carries ones
+                abunds = [np.fromiter(mh.hashes.values(), dtype=np.uint64, count=len(mh)) if w else np.ones(len(mh), dtype=np.uint64)
+                          for mh, w in zip(mhs, with_abundance)]
+            stats = sset.gather_stats_many(SketchSet([mh.flatten() for mh in mhs]), threshold_bp, abunds=abunds)
         # Subjects with the same md5 are one entry of the loop's counter: it keeps the first one's place and the LAST one's
         # signature and location (CounterGather._register), so a picked row -- the first of its kind -- reports the last subject
         # of the walk with its md5.  The same md5 means the same hashes, hence the same size at the common scaled: only rows of
