@@ -25,23 +25,16 @@
 #include <stdlib.h>
 #include "arena.hpp"
 #include "device_api.hpp"
+#include "compare_core.hpp"
 
 namespace smg {
 
+using namespace ap_geom;
+
 namespace {
 
-constexpr int AP_T = 64;                 // sketches per block = tile edge
-constexpr int AP_TS = AP_T + 1;          // row stride of the tile's accumulators in LDS: a hash shared by a whole block puts the 64
-                                         // lanes of a wave on 64 different rows and ONE column -- at a stride of 64 that is one bank
-constexpr int AP_THREADS = 1024;
-constexpr int AP_CHUNK = 4096;           // entries of list B staged per round (64 KB of hashes + payloads)
-constexpr int AP_ZMAX = 16;              // hash slices per tile at most
-#ifndef AP_INLINE_N
-#define AP_INLINE_N 16
-#endif
-constexpr int AP_INLINE = AP_INLINE_N;            // an entry of list A that meets at most this many entries of B adds its products itself
-constexpr int AP_G = 16;                 // lanes that share a longer run
-
+// (the constants AP_* / SM_* and the arithmetic of the plan, the cuts, the slices, the chunks, the searches and the worklist:
+//  compare_core.hpp)
 #define AP_TRY(expr)                       \
     do {                                   \
         hipError_t e_ = (expr);            \
@@ -57,13 +50,6 @@ constexpr int AP_G = 16;                 // lanes that share a longer run
 // of the slice (count, prefix, place), and an entry's final position is its bucket's start + the number of the bucket's entries with
 // a smaller (hash, row) -- a handful of compares, no sort.  A slice with more entries than the LDS room (hashes far from uniform)
 // is ranked against the rows' parts in memory instead: slow, same result.
-constexpr int SM_CAP = 2048;             // entries of a (block, slice) merged in LDS
-constexpr int SM_BUCKETS = 2048;         // sub-buckets of a slice
-constexpr int SM_BUCKET_BITS = 11;
-constexpr int SM_THREADS = 256;
-constexpr int SM_TARGET = 640;           // entries per (block, slice) aimed at; the shift lands between this and twice this
-
-struct ApPlan { uint32_t shift, n_slices; };
 
 __global__ __launch_bounds__(1024) void ap_plan_kernel(const uint64_t* __restrict__ hashes, const uint64_t* __restrict__ offsets, uint32_t n,
                                                        uint32_t s_max, ApPlan* __restrict__ plan) {
@@ -79,10 +65,7 @@ __global__ __launch_bounds__(1024) void ap_plan_kernel(const uint64_t* __restric
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < 16; ++w) m = s_m[w] > m ? s_m[w] : m;
-        uint32_t shift = 0;
-        while ((m >> shift) >= (unsigned long long)s_max) ++shift;             // s_max >= 2: ends at 63 at the latest
-        plan->shift = shift;
-        plan->n_slices = (uint32_t)(m >> shift) + 1u;                           // <= s_max
+        *plan = ap_plan(m, s_max);
     }
 }
 
@@ -92,20 +75,8 @@ __global__ __launch_bounds__(256) void ap_cuts_kernel(const uint64_t* __restrict
     const uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     const uint32_t r = (uint32_t)(idx / (s_max + 1u)), s = (uint32_t)(idx % (s_max + 1u));
     if (r >= n) return;
-    const uint32_t shift = plan->shift, ns = plan->n_slices;
     const uint64_t o0 = offsets[r];
-    const uint32_t len = (uint32_t)(offsets[r + 1] - o0);
-    uint32_t lo = 0, hi = len;
-    if (s >= ns) lo = len;
-    else if (s > 0) {
-        const uint64_t x = (uint64_t)s << shift;                               // <= the largest hash: no overflow
-        const uint64_t* row = hashes + o0;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (row[mid] < x) lo = mid + 1; else hi = mid;
-        }
-    }
-    cuts[idx] = lo;
+    cuts[idx] = ap_cut(hashes + o0, (uint32_t)(offsets[r + 1] - o0), s, *plan);
 }
 
 template <bool NARROW>
@@ -151,7 +122,7 @@ __global__ __launch_bounds__(SM_THREADS) void ap_slice_kernel(const uint64_t* __
     const uint64_t* row = hashes + my_at;
     const uint64_t* arow = abunds + my_at;
     const uint64_t base = (uint64_t)s << shift;
-    auto bucket = [&](uint64_t h) { const uint64_t rel = h - base; return (uint32_t)(shift > (uint32_t)SM_BUCKET_BITS ? rel >> (shift - SM_BUCKET_BITS) : rel); };
+    auto bucket = [&](uint64_t h) { return ap_bucket(h, base, shift); };
     auto put = [&](uint64_t o, uint64_t h, uint64_t a, uint32_t r) {
         l_hash[o] = h;
         if (NARROW) l_pay[o] = ((uint64_t)r << 32) | (uint32_t)a;            // row and 32-bit abundance in one word
@@ -197,7 +168,7 @@ __global__ __launch_bounds__(SM_THREADS) void ap_slice_kernel(const uint64_t* __
         }
     } else {
         // more entries than the LDS holds: an entry's place = the entries of the other rows' parts in front of it (equal hashes: the
-        // earlier rows') + its own index
+        // earlier rows': a lower bound ordered by (hash, row)) + its own index
         for (uint32_t i = q; i < my_len; i += 4) {
             const uint64_t h = row[i];
             uint64_t rank = i;
@@ -215,14 +186,6 @@ __global__ __launch_bounds__(SM_THREADS) void ap_slice_kernel(const uint64_t* __
             put(out0 + rank, h, arow[i], rr);
         }
     }
-}
-
-__device__ __forceinline__ uint64_t ap_lower_bound(const uint64_t* __restrict__ a, uint64_t lo, uint64_t hi, uint64_t x) {
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // one workgroup per (tile, slice): tile t = (bi, bj), bi <= bj, enumerated row by row of the upper triangle
@@ -243,8 +206,10 @@ __global__ __launch_bounds__(AP_THREADS) void ap_join_kernel(const uint64_t* __r
     __shared__ uint64_t s_bound[4];                                  // this slice's ranges in the two lists
     const int tid = threadIdx.x;
     const uint32_t z = blockIdx.x % Z;
+    // The arithmetic of this kernel -- ap_tile_of, ap_slice_bounds, ap_trim_to_runs, ap_find, ap_run_len, ap_work_pack / ap_work_unpack
+    // (compare_core.hpp) -- is kept inline: through the calls the wide form ran 2 % slower.  Each piece names its function.
     uint32_t t = blockIdx.x / Z, bi = 0;
-    while (t >= nb - bi) { t -= nb - bi; ++bi; }                     // (nb is small: at most a few hundred steps)
+    while (t >= nb - bi) { t -= nb - bi; ++bi; }                     // ap_tile_of (nb is small: at most a few hundred steps)
     const uint32_t bj = bi + t;
     const bool diag = bi == bj;
     const uint32_t row0 = bi * AP_T, col0 = bj * AP_T;
@@ -253,15 +218,15 @@ __global__ __launch_bounds__(AP_THREADS) void ap_join_kernel(const uint64_t* __r
     for (int i = tid; i < AP_T * AP_TS; i += AP_THREADS) { s_prod[i] = 0; s_cnt[i] = 0; }
     if (tid < 2) s_wn[tid] = 0;
     if (tid == 0) {
-        // slice z of the tile: an equal share of list A's entries, moved to the start of a run of equal hashes; list B between the
-        // same two hash values
+        // ap_slice_bounds: an equal share of list A's entries, moved to the start of a run of equal hashes; list B between the same two
+        // hash values
         uint64_t a0 = A0 + (A1 - A0) * z / Z, a1 = z + 1 == Z ? A1 : A0 + (A1 - A0) * (z + 1) / Z;
-        if (a0 > A0 && a0 < A1) a0 = ap_lower_bound(l_hash, A0, a0, l_hash[a0]);
-        if (a1 > A0 && a1 < A1) a1 = ap_lower_bound(l_hash, A0, a1, l_hash[a1]);
+        if (a0 > A0 && a0 < A1) a0 = lower_bound_u64(l_hash, A0, a0, l_hash[a0]);
+        if (a1 > A0 && a1 < A1) a1 = lower_bound_u64(l_hash, A0, a1, l_hash[a1]);
         uint64_t b0 = B0, b1 = B1;
         if (a0 < a1) {
-            if (a0 > A0) b0 = ap_lower_bound(l_hash, B0, B1, l_hash[a0]);
-            if (a1 < A1) b1 = ap_lower_bound(l_hash, b0, B1, l_hash[a1]);
+            if (a0 > A0) b0 = lower_bound_u64(l_hash, B0, B1, l_hash[a0]);
+            if (a1 < A1) b1 = lower_bound_u64(l_hash, b0, B1, l_hash[a1]);
         } else b1 = b0;
         s_bound[0] = a0; s_bound[1] = a1; s_bound[2] = b0; s_bound[3] = b1;
     }
@@ -310,7 +275,7 @@ __global__ __launch_bounds__(AP_THREADS) void ap_join_kernel(const uint64_t* __r
             if (!NARROW) s_br[i] = rr[u];
         }
         __syncthreads();
-        if (b_cur + nb_stage < b_end) {                              // the run the chunk ends in may go on: leave it for the next round
+        if (b_cur + nb_stage < b_end) {                              // ap_trim_to_runs: the run the chunk ends in may go on
             const uint64_t last = s_bh[nb_stage - 1];
             uint64_t cut = nb_stage - 1;
             while (cut > 0 && s_bh[cut - 1] == last) --cut;           // (every thread walks the same <= AP_T broadcast reads)
@@ -350,12 +315,12 @@ __global__ __launch_bounds__(AP_THREADS) void ap_join_kernel(const uint64_t* __r
             // instruction issue and by these dependent LDS reads, profiles/r05_abund_join_experiments.txt).  The whole staging area is
             // searched, not just its first nb_stage entries: what lies behind them is the cut-off run of the largest staged hash and
             // 2^64 - 1 fillers, and no entry of A taken in this round (h <= hi) can equal either.
-            uint32_t lo = 0;
+            uint32_t lo = 0;                                          // ap_find
 #pragma unroll
             for (uint32_t len = AP_CHUNK / 2; len; len >>= 1) lo += s_bh[lo + len - 1] < h ? len : 0u;
             if (mine) {
                 if (lo < (uint32_t)nb_stage && s_bh[lo] == h) {
-                    uint32_t cnt = 1;                                 // the run of h: entries lo .. lo + cnt - 1, cnt <= 64
+                    uint32_t cnt = 1;                                 // ap_run_len: the run of h is entries lo .. lo + cnt - 1, cnt <= 64
 #pragma unroll
                     for (uint32_t len = AP_T / 2; len; len >>= 1) {
                         const uint32_t at = lo + cnt + len - 1;
@@ -367,7 +332,7 @@ __global__ __launch_bounds__(AP_THREADS) void ap_join_kernel(const uint64_t* __r
                         for (uint32_t j = lo; j < ulo; ++j) add(ra, aa, j);
                     } else {
                         const uint32_t slot = atomicAdd(&s_wn[par], 1u) - wbase;      // < AP_THREADS: one per thread at most
-                        s_work[par * AP_THREADS + slot] = lo | (cnt << 12) | (ra << 19);
+                        s_work[par * AP_THREADS + slot] = lo | (cnt << 12) | (ra << 19);      // ap_work_pack
                         s_wpay[par * AP_THREADS + slot] = aa;
                     }
                 }
@@ -383,7 +348,7 @@ __global__ __launch_bounds__(AP_THREADS) void ap_join_kernel(const uint64_t* __r
                 for (uint32_t w = (q % 4u) * 16u + q / 4u; w < nw; w += AP_THREADS / AP_G) {
                     const uint32_t e = s_work[par * AP_THREADS + w];
                     const unsigned long long aa = s_wpay[par * AP_THREADS + w];
-                    const uint32_t lo = e & 4095u, cnt = (e >> 12) & 127u, row_a = e >> 19;
+                    const uint32_t lo = e & 4095u, cnt = (e >> 12) & 127u, row_a = e >> 19;     // ap_work_unpack
                     for (uint32_t o = (uint32_t)tid % AP_G; o < cnt; o += AP_G) add(row_a, aa, lo + o);
                 }
                 par ^= 1u;
@@ -412,9 +377,6 @@ __global__ __launch_bounds__(AP_THREADS) void ap_join_kernel(const uint64_t* __r
 }
 
 constexpr size_t AP_LDS = (size_t)AP_CHUNK * 16 + (size_t)AP_T * AP_TS * 12 + (size_t)AP_THREADS * 2 * 12 + AP_CHUNK;
-static_assert(AP_CHUNK <= 4096 && AP_T <= 64, "a worklist word holds a 12-bit run start, a 7-bit length and a 6-bit row");
-static_assert((AP_CHUNK & (AP_CHUNK - 1)) == 0 && AP_T == 64, "the searches halve a power of two");
-static_assert(AP_THREADS == 1024 && AP_G == 16, "the list walk deals 64 groups of 16 lanes, four to a wave");
 
 }  // namespace
 
@@ -430,8 +392,7 @@ hipError_t abund_pairs_launch(const uint64_t* d_hashes, const uint64_t* d_abunds
     AP_TRY(hipMemsetAsync(d_prod, 0, (size_t)n * n * 8, stream));
     if (total == 0) return hipSuccess;
     // the per-block lists: plan (shift of the slices from the largest hash), cuts, one workgroup per (block, slice)
-    uint64_t per_block = total / nb / (uint64_t)SM_TARGET;
-    const uint32_t s_max = (uint32_t)(per_block < 2 ? 2 : (per_block > 0x100000ull ? 0x100000ull : per_block));
+    const uint32_t s_max = ap_s_max(total, nb);
     const uint64_t n_cuts = (uint64_t)n * (s_max + 1u);
     if ((uint64_t)s_max * nb > 0x7fffffffull || n_cuts / 256 > 0x7ffffff0ull) return hipErrorNotSupported;
     ArenaBuf plan_b, cuts_b, lh_b, lp_b, lr_b;
@@ -454,11 +415,7 @@ hipError_t abund_pairs_launch(const uint64_t* d_hashes, const uint64_t* d_abunds
     AP_TRY(hipGetLastError());
     // hash slices per tile: enough work items to fill the chip twice over when the tiles alone do not (SMG_ABUND_SLICES overrides)
     static const uint32_t z_env = [] { const char* e = getenv("SMG_ABUND_SLICES"); return e ? (uint32_t)atoi(e) : 0u; }();
-    // ~2.5 workgroups per CU, and an ODD count: C3 (136 tiles, round 6) 1.49 / 1.19 / 1.28 / 1.18 / 1.28 / 1.21 / 1.27 ms for the call at
-    // 2 / 3 / 4 / 5 / 6 / 7 / 8 slices -- with an even count the slices of one tile sit on workgroup ids that differ by less than 8 and
-    // so on different XCDs at the same moment, all adding into the same output tile through eight L2s
-    uint32_t Z = tiles >= 640 ? 1u : (uint32_t)((640 + tiles - 1) / tiles) | 1u;
-    if (Z > (uint32_t)AP_ZMAX - 1u) Z = (uint32_t)AP_ZMAX - 1u;
+    uint32_t Z = ap_slices_per_tile(tiles);
     if (z_env >= 1 && z_env <= (uint32_t)AP_ZMAX) Z = z_env;
     // (initialised once, whichever host thread comes first: a function-local static's initialiser is serialised by the language)
     static const int attr = [] {

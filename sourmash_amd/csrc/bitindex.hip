@@ -12,21 +12,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "device_api.hpp"
+#include "compare_core.hpp"
 
 namespace smg {
 
 constexpr int BT = 64;            // tile edge (sketches)
 constexpr int BKC = 32;           // bitmap words staged per k-step
 constexpr int BSTRIDE = BKC + 4;  // LDS row stride in words: 36*t mod 64 is a distinct multiple of 4 for t = 0..15
-
-__device__ __forceinline__ uint64_t lower_bound_u64(const uint64_t* __restrict__ a, uint64_t n, uint64_t x) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // one wave per sketch: set bit rank(h) for every hash h of the row
 __global__ __launch_bounds__(256) void bitmap_build_kernel(const uint64_t* __restrict__ hashes,
@@ -40,7 +32,7 @@ __global__ __launch_bounds__(256) void bitmap_build_kernel(const uint64_t* __res
         const uint64_t lo = offsets[row], hi = offsets[row + 1];
         uint32_t* out = bits + row * (uint64_t)words_per_row;
         for (uint64_t i = lo + lane; i < hi; i += 64) {
-            const uint64_t rank = lower_bound_u64(dict, U, hashes[i]);
+            const uint64_t rank = lower_bound_u64(dict, 0ull, U, hashes[i]);
             atomicOr(&out[rank >> 5], 1u << (rank & 31));
         }
     }

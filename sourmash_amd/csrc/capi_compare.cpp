@@ -6,6 +6,7 @@
 #include <memory>
 #include <thread>
 #include "capi_common.hpp"
+#include "compare_core.hpp"
 
 using namespace smg;
 
@@ -33,16 +34,20 @@ struct BitIndex {
     }
 };
 
-// measured rates behind the cost model (1 x MI355X)
-constexpr double RATE_MERGE_STEPS = 6.0e12;   // merge-step equivalents / s of compare_hash_kernel (a pair of sketches = n_i + n_j steps): 5.7e12 at 1,000 x 5,000
-                                              // hashes, 7.0e12 at 2,000, 9.5e12 at C4 (profiles/r06_compare_small.jsonl) -- the smaller one decides small problems
-constexpr double MERGE_ROUND_FLOOR = 6.0e-8;  // seconds per hash of the mean sketch: the latency floor of the general kernel's rounds
-constexpr double RATE_BIT_WORDS = 9.5e12;     // 32-bit AND+popcount / s (bitmatrix_kernel at C4: the VALU roof)
-constexpr double RATE_PAIR_ATOMICS = 4.0e9;   // matrix increments / s (rare_pairs_kernel)
-// the all-pairs callers compute the triangle and mirror it: a pair costs ONE visit of its tile / ONE increment, like the
-// n * total / 2 ... steps the merge rate is calibrated on.  (A bit column costs n^2/2 pairs x 1/32 word, a rare hash held by
-// m sketches m^2/2 increments: they meet at m = n * sqrt(RATE_PAIR_ATOMICS / (32 * 2 * RATE_BIT_WORDS)), the threshold below.)
-constexpr double TRIANGLE = 0.5;
+// What both builders end in: the cost model's verdict on what the builder counted (compare_core.hpp: compare_index_accept), the
+// index's fields, and the zeroed bit rows.  false: the merge kernel wins, or the bitmap cap (~BitIndex frees what was allocated).
+static bool bitindex_finish(BitIndex* bi, const ComparePathModel& model, uint64_t universe, uint64_t n_freq, uint64_t rare_pairs,
+                            bool forced, hipStream_t st) {
+    const CompareIndexAccept acc = compare_index_accept(bi->n, n_freq, rare_pairs, bi->total, model.t_merge, forced);
+    if (!acc.accept) return false;
+    bi->universe = universe; bi->frequent = n_freq; bi->rare_pairs = rare_pairs;
+    bi->threshold = model.threshold; bi->words_per_row = acc.words;
+    if (acc.words) {
+        hip_check(arena_alloc((void**)&bi->bits, (size_t)bi->n * acc.words * 4, st), "arena_alloc");
+        hip_check(hipMemsetAsync(bi->bits, 0, (size_t)bi->n * acc.words * 4, st), "memset");
+    }
+    return true;
+}
 
 // Build the cheapest exact index for the collection, or return nullptr (no error) when the merge kernel is.
 static BitIndex* bitindex_build(const uint64_t* d_hashes, const uint64_t* d_offsets, uint32_t n, hipStream_t st,
@@ -53,22 +58,14 @@ static BitIndex* bitindex_build(const uint64_t* d_hashes, const uint64_t* d_offs
         hip_check(hipStreamSynchronize(st), "sync");
     }
     if (total == 0 || total > 0xffffffffull) return nullptr;
-    // (the general kernel walks a tile's sketches in lock-step rounds of <= 64 hashes, ~4 us a round however few tiles there are:
-    //  sixteen 5,000-hash sketches take 0.32 ms, 256 of them 0.43 -- tools/bench_compare_small.py, profiles/r06_compare_small.jsonl)
-    const double t_merge = std::max((double)n * (double)total / RATE_MERGE_STEPS, (double)total / (double)n * MERGE_ROUND_FLOOR);
-    // a hash held by m sketches costs m^2 increments as a rare hash, or one bit column (n^2/2 pairs x 1/32 word) as
-    // a frequent one: the two meet at m ~ n * sqrt(RATE_PAIR_ATOMICS / (64 * RATE_BIT_WORDS))
-    uint32_t threshold = (uint32_t)((double)n * std::sqrt(RATE_PAIR_ATOMICS / (64.0 * RATE_BIT_WORDS)));
-    if (threshold < 1) threshold = 1;
-    if (forced_threshold) threshold = forced_threshold;
-    const double pairs = 0.5 * (double)n * (double)n;
+    // the threshold, the general kernel's expected time, and whether a builder is worth starting: compare_core.hpp
+    const ComparePathModel model = compare_path_model(n, total, forced_threshold, one_shot);
+    const uint32_t threshold = model.threshold;
     // The sort-free builder first (dictindex.hip): it serves collections whose distinct hashes fit its per-bucket tables
     // (any collection with heavy sharing: C3 / C4 have 55,000 distinct hashes for 5e6 / 5e7 elements); a bucket that
     // overflows sends the build to the sort below.  SMG_COMPARE_INDEX=sort skips it (tests run both).
     static const bool sort_only = [] { const char* e = getenv("SMG_COMPARE_INDEX"); return e && !strcmp(e, "sort"); }();
-    // an index that serves ONE compare must also pay for its own build (~0.1 ms of launches + three passes over the elements)
-    // (its slice bounds take 2 KB per sketch: past two million sketches the sort's scratch is the smaller one)
-    if (!sort_only && n <= (2u << 20) && !(one_shot && !forced_threshold && t_merge < 0.1e-3 + (double)total / 4.0e10)) {
+    if (!sort_only && model.try_dict) {
         std::unique_ptr<BitIndex> bi(new BitIndex());
         bi->n = n; bi->total = total; bi->stream = st;
         AsyncBuf scratch(dict_scratch_bytes(n), st);
@@ -79,32 +76,20 @@ static BitIndex* bitindex_build(const uint64_t* d_hashes, const uint64_t* d_offs
         hip_check(hipMemcpyAsync(out, d_out, sizeof(out), hipMemcpyDeviceToHost, st), "D2H");
         hip_check(hipStreamSynchronize(st), "sync");
         if (out[4] == 0) {
-            const uint64_t U = out[0], n_freq = out[1], rare_pairs = out[2], rare_elems = out[3];
-            bi->universe = U;
-            const uint32_t words = n_freq ? (uint32_t)(((n_freq + 31) / 32 + 31) / 32 * 32) : 0;     // whole 32-word k-steps
-            const double t_index = TRIANGLE * (pairs * (double)words / RATE_BIT_WORDS + 2.0 * (double)rare_pairs / RATE_PAIR_ATOMICS) +
-                                   (double)total / 2.0e10;
-            if ((t_index > t_merge && !forced_threshold) || (double)n * words * 4.0 > 8.0 * (1ull << 30)) return nullptr;
-            bi->frequent = n_freq; bi->rare_pairs = rare_pairs; bi->threshold = threshold; bi->words_per_row = words;
-            if (words) {
-                hip_check(arena_alloc((void**)&bi->bits, (size_t)n * words * 4, st), "arena_alloc");
-                hip_check(hipMemsetAsync(bi->bits, 0, (size_t)n * words * 4, st), "memset");
-            }
+            const uint64_t rare_elems = out[3];
+            if (!bitindex_finish(bi.get(), model, out[0], out[1], out[2], forced_threshold != 0, st)) return nullptr;
             if (rare_elems) {
                 hip_check(arena_alloc((void**)&bi->rows_sorted, rare_elems * 4 + 16, st), "arena_alloc");
                 hip_check(arena_alloc((void**)&bi->run_end, rare_elems * 4 + 16, st), "arena_alloc");
                 bi->inv_total = rare_elems;
             }
-            hip_check(dict_emit_launch(d_hashes, d_offsets, n, scratch.p, bi->bits, words, bi->rows_sorted, bi->run_end, st),
+            hip_check(dict_emit_launch(d_hashes, d_offsets, n, scratch.p, bi->bits, bi->words_per_row, bi->rows_sorted, bi->run_end, st),
                       "dictionary pass 2");
             bi->builder = 1;
             return bi.release();
         }
     }
-    // an index that serves ONE compare must also pay for its own sort: ~0.6 ms of fixed cost + total / 1.4e9 s (round 6: a collection
-    // of mostly private hashes, 1,000 / 2,000 sketches of 5,000: 3.8 / 8.2 ms through this builder against 0.88 / 2.8 ms for the general
-    // kernel -- the earlier total / 5e9 sent such collections here, tools/bench_compare_small.py)
-    if (one_shot && !forced_threshold && t_merge < 0.6e-3 + (double)total / 1.4e9) return nullptr;
+    if (!model.try_sort) return nullptr;
     // (hash, row) of the whole collection sorted by hash; runs = distinct hashes with their number of holders.
     // Scratch comes from the stream-ordered pool and the host reads back once: the kernels of a small build take
     // less time than one hipMalloc / hipFree pair or one extra synchronisation.
@@ -126,21 +111,11 @@ static BitIndex* bitindex_build(const uint64_t* d_hashes, const uint64_t* d_offs
     hip_check(hipMemcpyAsync(out, d_out, 24, hipMemcpyDeviceToHost, st), "D2H");
     hip_check(hipStreamSynchronize(st), "sync");
     const uint64_t U = out[0], n_freq = out[1], rare_pairs = out[2];
-    bi->universe = U;
     bi->inv_total = total;
-    const uint32_t words = n_freq ? (uint32_t)(((n_freq + 31) / 32 + 31) / 32 * 32) : 0;     // whole 32-word k-steps
-    const double t_index = TRIANGLE * (pairs * (double)words / RATE_BIT_WORDS + 2.0 * (double)rare_pairs / RATE_PAIR_ATOMICS) +
-                           (double)total / 2.0e10;                                         // + one pass over the elements
-    if ((t_index > t_merge && !forced_threshold) || (double)n * words * 4.0 > 8.0 * (1ull << 30))
-        return nullptr;                                             // merge kernel wins / bitmap cap (~BitIndex frees)
-    bi->frequent = n_freq; bi->rare_pairs = rare_pairs; bi->threshold = threshold; bi->words_per_row = words;
-    if (words) {
-        hip_check(arena_alloc((void**)&bi->bits, (size_t)n * words * 4, st), "arena_alloc");
-        hip_check(hipMemsetAsync(bi->bits, 0, (size_t)n * words * 4, st), "memset");
-    }
+    if (!bitindex_finish(bi.get(), model, U, n_freq, rare_pairs, forced_threshold != 0, st)) return nullptr;
     hip_check(arena_alloc((void**)&bi->run_end, total * 4 + 16, st), "arena_alloc");
     hip_check(inverted_apply_launch(run_off.as<uint64_t>(), flags.as<uint32_t>(), freq_rank.as<uint64_t>(), U, total, bi->rows_sorted,
-                                    bi->run_end, bi->bits, words, st), "inverted apply");
+                                    bi->run_end, bi->bits, bi->words_per_row, st), "inverted apply");
     if (rare_pairs == 0 && n_freq == U) {             // nothing is rare: plain bit rows, drop the inverted part
         arena_free(bi->rows_sorted, st); arena_free(bi->run_end, st);
         bi->rows_sorted = bi->run_end = nullptr;

@@ -29,19 +29,13 @@
 #include "device_api.hpp"
 #include "arena.hpp"
 #include "wavemask.hpp"
+#include "compare_core.hpp"
 
 namespace smg {
 
-constexpr int CT = 16;            // tile edge (sketches)
-constexpr int CMP_ZMAX = 16;      // hash-range slices per tile (grid.z); a tile uses ceil(longest / slice_len) of them
+using namespace cmp_tile;
 
-__device__ __forceinline__ uint64_t lower_bound_row(const uint64_t* __restrict__ a, uint64_t lo, uint64_t hi, uint64_t x) {
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
+// (tile geometry -- CT, HR x HC sketches, HSEG hashes per round, HWAVES waves -- and every rule named below: compare_core.hpp)
 
 // One unit of work: slice z (of zt) of the tile (row tile index `ty` in launch order, column tile cb).
 struct WorkItem { uint32_t ty, cb, z, zt; };
@@ -68,8 +62,7 @@ __global__ __launch_bounds__(256) void compare_plan_kernel(
         if (c < n) { const uint64_t l = offsets[c + 1] - offsets[c]; best = l > best ? l : best; }
     }
     if (best == 0) return;                                    // nothing can intersect
-    uint32_t zt = (uint32_t)((best + slice_len - 1) / slice_len);
-    zt = zt < 1 ? 1 : (zt > (uint32_t)CMP_ZMAX ? (uint32_t)CMP_ZMAX : zt);
+    const uint32_t zt = cmp_slice_count(best, slice_len, (uint32_t)CMP_ZMAX);
     WorkItem* list = zt > 1 ? heavy : light;
     const unsigned int base = atomicAdd(&counters[zt > 1 ? 0 : 1], zt);
     for (uint32_t z = 0; z < zt; ++z) list[base + z] = WorkItem{ty, cb, z, zt};
@@ -89,42 +82,20 @@ __global__ __launch_bounds__(256) void compare_plan_kernel(
 // what bounded the first version): the masks are counted in per-lane 4-bit counters (3 instructions per 8
 // (row, column) cells, nothing divergent) that go to the tile's LDS counters every 15 rounds through a DPP row sum; a
 // probe reads an aligned pair of slots; the sets of lanes still probing live in scalar registers as wave masks.
-constexpr int HR = CT;                // row sketches of a tile (inserted)
-constexpr int HC = 32;                // column sketches of a tile (looked up)
-constexpr int HSEG = 64;              // hashes staged per sketch and round: one per lane
 // table slots: 2^LOGT (template parameter); rows put in at most 16 x 64 = 1024 distinct hashes per round
-constexpr unsigned long long H_EMPTY = ~0ull;   // never a key: a staged hash equal to 2^64 - 1 is counted out of band
-constexpr int HWAVES = 8;             // waves per workgroup: sketch s = i * HWAVES + wave, so every wave holds HR / 8 rows
-constexpr int HBLOCK = HWAVES * 64;
-constexpr int HPW = (HR + HC) / HWAVES;   // sketches per wave
-static_assert(HR % HWAVES == 0 && HC % HWAVES == 0, "");
-
-constexpr int NR = HR / HWAVES;       // row sketches per wave
-constexpr int NC = HC / HWAVES;       // column sketches per wave
-static_assert(HR == 16 && NC == 4 && HC == 32, "the packed counters below hold 16 rows x 4 columns per wave");
-
-template <int LOGT>
-__device__ __forceinline__ uint32_t pair_slot(uint64_t v) {           // the even slot a hash's probe sequence starts on
-    // the hashes of a round share their top bits (a narrow value range), so the slot comes from the low word folded with
-    // the high one; shifts and xors only -- a 32-bit multiply costs four of them on this VALU
-    uint32_t x = (uint32_t)v ^ (uint32_t)(v >> 32);
-    x ^= x >> 15;
-    return (x & (uint32_t)((1 << (LOGT - 1)) - 1)) << 1;
-}
 
 template <int CTRL>
 __device__ __forceinline__ uint32_t row_rotated(uint32_t x) {         // lane l of a 16-lane row <- lane (l + n) % 16: DPP row_ror:n
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, false);
 }
 
-// The per-lane 4-bit counters of a wave (see the kernel) go to the tile's LDS counters.  acc[p][k] nibble j counts bit
-// t = 4j + k of y_p = m[2p] | m[2p+1] << 16, i.e. row t & 15 of column j' = 2p + (t >> 4) of this wave (tile column
-// 8j' + wave).  Even and odd nibbles are split into byte lanes (<= 15 each), summed over the 16 lanes of a DPP row
-// (<= 240, still a byte), and lane b < 4 of each row adds byte b of every register to its counter.
+// The per-lane 4-bit counters of a wave (see the kernel) go to the tile's LDS counters.  Even and odd nibbles are split into
+// byte lanes (<= 15 each), summed over the 16 lanes of a DPP row (<= 240, still a byte), and lane b < 4 of each row adds byte
+// b of every register to the counter cmp_nibble_cell names.
 __device__ __forceinline__ void flush_nibble_counts(uint32_t (&acc)[NC / 2][4], uint32_t* s_cnt, int lane, int wave) {
     const int b = lane & 3;
     const bool pusher = (lane & 15) < 4;
-    uint32_t* const mine = s_cnt + (8 * (b & 1)) * HC + (b >> 1) * HWAVES + wave;
+    uint32_t* const mine = s_cnt + (8 * (b & 1)) * HC + (b >> 1) * HWAVES + wave;      // cmp_nibble_cell_of_lane, kept inline
     const uint32_t sh = 8u * (uint32_t)b;
 #pragma unroll
     for (int p = 0; p < NC / 2; ++p)
@@ -138,8 +109,7 @@ __device__ __forceinline__ void flush_nibble_counts(uint32_t (&acc)[NC / 2][4], 
                 x += row_rotated<0x124>(x);
                 x += row_rotated<0x122>(x);
                 x += row_rotated<0x121>(x);
-                // byte b of (p, k, h): row 8 (b & 1) + 4 h + k, column 8 (2 p + (b >> 1)) + wave
-                if (pusher) atomicAdd(&mine[(4 * h + k) * HC + 2 * HWAVES * p], (x >> sh) & 0xffu);
+                if (pusher) atomicAdd(&mine[cmp_nibble_cell_of_reg(p, k, h)], (x >> sh) & 0xffu);
             }
             acc[p][k] = 0;
         }
@@ -192,20 +162,22 @@ __global__ __launch_bounds__(HBLOCK, MINW) void compare_hash_kernel(
         }
         __syncthreads();
         if (it.zt > 1) {                                   // hash-range slice of a heavy tile
+            // cmp_longest_first, cmp_slice_pivots and cmp_slice_cut (compare_core.hpp), kept inline: through the calls both pivots are
+            // read and stored together and the item setup is no longer the parent's instructions
             if (tid == 0) {
                 uint64_t best_len = 0, best_pos = 0;
                 for (int i = 0; i < HR + HC; ++i) {
                     const uint64_t len = s_end[i] - s_pos[i];
                     if (len > best_len) { best_len = len; best_pos = s_pos[i]; }
                 }
-                s_piv[0] = it.z == 0 ? 0ull : hashes[best_pos + (uint64_t)it.z * best_len / it.zt];
+                s_piv[0] = it.z == 0 ? 0ull : hashes[best_pos + (uint64_t)it.z * best_len / it.zt];                    // cmp_slice_pivot_at
                 s_piv[1] = it.z + 1 == it.zt ? ~0ull : hashes[best_pos + (uint64_t)(it.z + 1) * best_len / it.zt];
             }
             __syncthreads();
             if (tid < HR + HC) {
                 const uint64_t lo = s_pos[tid], hi = s_end[tid];
-                const uint64_t a = it.z == 0 ? lo : lower_bound_row(hashes, lo, hi, s_piv[0]);
-                const uint64_t b = it.z + 1 == it.zt ? hi : lower_bound_row(hashes, a, hi, s_piv[1]);
+                const uint64_t a = it.z == 0 ? lo : lower_bound_u64(hashes, lo, hi, s_piv[0]);
+                const uint64_t b = it.z + 1 == it.zt ? hi : lower_bound_u64(hashes, a, hi, s_piv[1]);
                 s_pos[tid] = a;
                 s_end[tid] = b;
             }
@@ -240,27 +212,27 @@ __global__ __launch_bounds__(HBLOCK, MINW) void compare_hash_kernel(
             uint32_t live = 0;
 #pragma unroll
             for (int i = 0; i < HPW; ++i) {
-                if (left[i] > (uint32_t)HSEG) wmin = e[i] < wmin ? e[i] : wmin;
-                if (left[i]) live |= i < NR ? 1u : 2u;
+                if (cmp_round_bounds(left[i], (uint32_t)HSEG)) wmin = e[i] < wmin ? e[i] : wmin;
+                if (left[i]) live |= i < NR ? CMP_LIVE_ROWS : CMP_LIVE_COLS;
             }
             if (lane == HSEG - 1 && wmin != ~0ull) atomicMin(&s_hi2[par], (unsigned long long)wmin);
             if (lane == 0 && live) atomicOr(&s_live2[par], live);
             __syncthreads();
-            if (s_live2[par] != 3u) break;                 // every row or every column exhausted
+            if (!cmp_round_live(s_live2[par])) break;      // every row or every column exhausted
             const uint64_t hi = uniform64(s_hi2[par]);
             if (tid == 0) { s_hi2[par ^ 1u] = ~0ull; s_live2[par ^ 1u] = 0; }     // next round's cells (not touched before its atomics)
             // ---- what this round consumes (a prefix of every staged segment); the next round's hashes start loading now.
-            //      hi = 2^64 - 1 only when no sketch has more than it has staged: that round consumes everything left and is
-            //      the only one that can meet the hash 2^64 - 1 (the empty-slot key), which is counted out of band.  Lanes
-            //      past a segment's end hold 2^64 - 1 and fail `<= cut` by themselves ----
-            const bool last = hi == ~0ull;
-            const uint64_t cut = last ? ~0ull - 1 : hi;
+            //      The last round (cmp_round_last) consumes everything left and is the only one that can meet the hash
+            //      2^64 - 1 (the empty-slot key), which is counted out of band.  Lanes past a segment's end hold 2^64 - 1
+            //      and fail `<= cut` by themselves ----
+            const bool last = cmp_round_last(hi);
+            const uint64_t cut = cmp_round_cut(hi);
             bool mine[HPW];
             uint32_t take[HPW];
 #pragma unroll
             for (int i = 0; i < HPW; ++i) {
                 mine[i] = e[i] <= cut;
-                take[i] = last ? left[i] : (uint32_t)__popcll(mask_of(mine[i]));
+                take[i] = last ? left[i] : (uint32_t)__popcll(mask_of(mine[i]));     // cmp_round_take, the count made only when it is used
                 at[i] += take[i];
                 left[i] -= take[i];
             }
@@ -292,12 +264,12 @@ __global__ __launch_bounds__(HBLOCK, MINW) void compare_hash_kernel(
                 for (int i = 0; i < NR; ++i) {
                     opaque(old[i]);                        // lanes outside ron[i] hold nothing; their compare bits are masked
                     ron[i] &= mask_of(old[i] != H_EMPTY) & mask_of(old[i] != e[i]);     // slot taken by another hash
-                    if (lanes_of(ron[i])) ro[i] = (ro[i] + 8u) & (uint32_t)(HT * 8 - 1);
+                    if (lanes_of(ron[i])) ro[i] = cmp_probe_next<LOGT>(ro[i], 8u);
                 }
             }
 #pragma unroll
-            for (int i = 0; i < NR; ++i)                   // 16-bit row masks, two to a word: slot s -> half (s & 1) of word s >> 1
-                if (mine[i]) atomicOr(&s_mask[ro[i] >> 4], (1u << (i * HWAVES + wave)) << ((ro[i] & 8u) << 1));
+            for (int i = 0; i < NR; ++i)                   // 16-bit row masks, two to a word
+                if (mine[i]) atomicOr(&s_mask[cmp_mask_word(ro[i])], (1u << (i * HWAVES + wave)) << cmp_mask_shift(ro[i]));
             __syncthreads();
             // ---- columns: one lookup per hash, a pair of slots per probe (a key sits before the first empty slot of its
             //      probe sequence, and an odd slot is never filled before its even neighbour) ----
@@ -328,13 +300,13 @@ __global__ __launch_bounds__(HBLOCK, MINW) void compare_hash_kernel(
                     fnd[j] |= bh;
                     odd[j] |= b1;
                     con[j] &= mask_of(kk[j].y != H_EMPTY) & ~bh;
-                    if (lanes_of(con[j])) co[j] = (co[j] + 16u) & (uint32_t)(HT * 8 - 1);
+                    if (lanes_of(con[j])) co[j] = cmp_probe_next<LOGT>(co[j], 16u);
                 }
             }
             uint32_t m[NC];
 #pragma unroll
             for (int j = 0; j < NC; ++j)
-                m[j] = lanes_of(fnd[j]) ? (uint32_t)((const uint16_t*)s_mask)[(co[j] >> 3) + (lanes_of(odd[j]) ? 1u : 0u)] : 0u;
+                m[j] = lanes_of(fnd[j]) ? (uint32_t)((const uint16_t*)s_mask)[cmp_mask_half(co[j]) + (lanes_of(odd[j]) ? 1u : 0u)] : 0u;
             const bool hit = (fnd[0] | fnd[1] | fnd[2] | fnd[3]) != 0;
             // ---- counts: bit r of m[j] says row r shares the lane's hash of column j.  Every lane keeps 4-bit counters of
             //      its own (16 rows x 4 columns in 8 registers: 3 instructions per 8 counters, nothing divergent, no LDS);
@@ -355,7 +327,7 @@ __global__ __launch_bounds__(HBLOCK, MINW) void compare_hash_kernel(
             for (int i = 0; i < NR; ++i)
                 if (mine[i]) {
                     *(unsigned long long*)((char*)s_key + ro[i]) = H_EMPTY;
-                    ((uint16_t*)s_mask)[ro[i] >> 3] = 0;
+                    ((uint16_t*)s_mask)[cmp_mask_half(ro[i])] = 0;
                 }
 #pragma unroll
             for (int i = 0; i < HPW; ++i) e[i] = en[i];
@@ -398,20 +370,10 @@ __global__ __launch_bounds__(256) void jaccard_from_counts_kernel(const uint32_t
             v = 1.0;                                              // compare.py:33 np.ones diagonal
         } else {
             const uint64_t ni = offsets[row + 1] - offsets[row], nj = offsets[col + 1] - offsets[col];
-            const uint64_t cm = common[i];
-            const uint64_t uni = ni + nj - cm;
-            v = (double)cm / (double)(uni > 1 ? uni : 1);         // minhash.rs:624-631
+            v = jaccard_scaled(common[i], ni, nj);                // minhash.rs:624-631
         }
         out[i] = v;
     }
-}
-
-// Slice length: long enough that ordinary sketches (a few thousand hashes) are never cut when there
-// are plenty of tiles, shorter when the tile count alone cannot fill 256 CUs x 4 workgroups.
-static uint32_t pick_slice_len(uint64_t n_tiles) {
-    if (n_tiles >= 2048) return 8192;
-    if (n_tiles >= 512) return 2048;
-    return 1024;
 }
 
 size_t compare_workspace_bytes(uint32_t n_row_tiles, uint32_t n_col_tiles) {
@@ -440,7 +402,7 @@ static hipError_t compare_launch(const uint64_t* d_hashes, const uint64_t* d_off
         const uint64_t work_tiles = tiles / (symmetric ? 2 : 1);
         hipLaunchKernelGGL(compare_plan_kernel, dim3((unsigned)((tiles + 255) / 256)), dim3(256), 0, stream, d_offsets, n,
                            row_lo, row_hi, symmetric, rb_first, rb_stride, n_row_tiles, n_col_tiles,
-                           pick_slice_len(work_tiles), heavy, light, counters, ctc);
+                           cmp_pick_slice_len(work_tiles), heavy, light, counters, ctc);
         const uint64_t cap = 256ull * 3;                               // 4,096 slots (load factor 1/4), 43 KiB of LDS, 80 VGPRs: 3 workgroups per CU
         const unsigned grid0 = (unsigned)(work_tiles + 1 < cap ? work_tiles + 1 : cap);
         hipLaunchKernelGGL((compare_hash_kernel<6, 12>), dim3(grid0 < 1 ? 1 : grid0), dim3(HBLOCK), 0, stream, d_hashes, d_offsets, n, row_lo, row_hi,

@@ -29,29 +29,19 @@
 #include <string.h>
 #include <type_traits>
 #include "device_api.hpp"
+#include "compare_core.hpp"
 
 namespace smg {
 
+using namespace cmp_tile;
+
 namespace {
 
-constexpr int XT = 16;                 // tile edge (sketches)
-constexpr int XSEG = 64;               // hashes staged per sketch and round
+// (XT, XSEG, XZMAX, XSLICE, XSLICE_SMALL and every rule named below: compare_core.hpp)
 constexpr int XPAD = 2;                // u64 slack per staged segment (the 16 column streams of a half-wave hit distinct banks)
 constexpr int XSTRIDE = XSEG + XPAD;
 
-constexpr int XZMAX = 16;              // hash-range slices a tile of abundance sketches can be cut into (grid.z)
-constexpr uint32_t XSLICE = 6144;      // hashes of the tile's longest sketch per slice: ordinary sketches (~5,000) are never cut
-constexpr uint32_t XSLICE_SMALL = 1700;   // ... for small grids (see compare_abund_launch)
-
 enum { X_NUM = 0, X_ABUND32 = 1, X_ABUND64 = 2 };
-
-__device__ __forceinline__ uint64_t lower_bound_u64(const uint64_t* __restrict__ a, uint64_t lo, uint64_t hi, uint64_t x) {
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 template <int MODE>
 __global__ __launch_bounds__(XT * XT) void compare_ext_kernel(
@@ -103,15 +93,16 @@ __global__ __launch_bounds__(XT * XT) void compare_ext_kernel(
 #pragma unroll
             for (int o = 32; o; o >>= 1) { const uint64_t x = __shfl_xor(best_len, o); best_len = x > best_len ? x : best_len; }
             const unsigned long long holders = __ballot(len == best_len);
-            const uint64_t best_pos = __shfl(pos, (int)__builtin_ctzll(holders));
+            const uint64_t best_pos = __shfl(pos, (int)__builtin_ctzll(holders));      // the first longest, as cmp_longest_first
             if (lane == 0) {
-                uint32_t zt = (uint32_t)((best_len + slice_len - 1) / slice_len);
-                zt = zt < 1 ? 1 : (zt > (uint32_t)XZMAX ? (uint32_t)XZMAX : zt);
+                const uint32_t zt = cmp_slice_count(best_len, slice_len, (uint32_t)XZMAX);
                 s_zt = zt;
                 const uint32_t z = blockIdx.z;
                 if (z < zt && zt > 1) {
-                    s_piv[0] = z == 0 ? 0ull : hashes[best_pos + (uint64_t)z * best_len / zt];
-                    s_piv[1] = z + 1 == zt ? ~0ull : hashes[best_pos + (uint64_t)(z + 1) * best_len / zt];
+                    uint64_t piv_lo, piv_hi;
+                    cmp_slice_pivots(hashes, best_pos, best_len, z, zt, &piv_lo, &piv_hi);
+                    s_piv[0] = piv_lo;
+                    s_piv[1] = piv_hi;
                 }
             }
         }
@@ -120,9 +111,8 @@ __global__ __launch_bounds__(XT * XT) void compare_ext_kernel(
         if (z >= zt) return;
         if (zt > 1) {
             if (tid < 2 * XT) {
-                const uint64_t lo = s_pos[tid], hi = s_end[tid];
-                const uint64_t a = z == 0 ? lo : lower_bound_u64(hashes, lo, hi, s_piv[0]);
-                const uint64_t b = z + 1 == zt ? hi : lower_bound_u64(hashes, a, hi, s_piv[1]);
+                uint64_t a, b;
+                cmp_slice_cut(hashes, s_pos[tid], s_end[tid], z, zt, s_piv[0], s_piv[1], &a, &b);
                 s_pos[tid] = a;
                 s_end[tid] = b;
             }
@@ -154,15 +144,15 @@ __global__ __launch_bounds__(XT * XT) void compare_ext_kernel(
             else s_seg[s][lane] = v;
             if (MODE == X_ABUND32) s_ab[s][lane] = (uint32_t)lane < len ? (uint32_t)abunds[pos + lane] : 0u;
             if (lane == 0) {
-                if (left > (uint64_t)XSEG) atomicMin(&s_hi, (unsigned long long)hashes[pos + XSEG - 1]);
+                if (left > (uint64_t)XSEG) atomicMin(&s_hi, (unsigned long long)hashes[pos + XSEG - 1]);     // cmp_round_bounds
                 if (len) atomicOr(&s_live[s < XT ? 0 : 1], 1u);
             }
         }
         __syncthreads();
         // every row or every column used up: no pair of the tile can meet another common hash, and in num mode further union
         // elements cannot change a count either
-        if (s_live[0] == 0 || s_live[1] == 0) break;
-        const uint64_t hi = s_hi;
+        if (!cmp_round_live(s_live[0], s_live[1])) break;
+        const uint64_t hi = s_hi;                                  // (2^64 - 1 is an ordinary hash here: no table, no cut below it)
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int s = wave * 8 + i;
@@ -176,8 +166,8 @@ __global__ __launch_bounds__(XT * XT) void compare_ext_kernel(
             const uint64_t* B = s_seg[PACKED ? 0 : XT + c];
             uint32_t ia = 0, ib = 0;
             if (MODE == X_NUM) {
-                while (ia < na && ib < nb && steps < cap) {
-                    const uint64_t a = A[ia], b = B[ib];
+                while (ia < na && ib < nb && steps < cap) {    // ext_num_walk (compare_core.hpp), kept inline: as a call the loop's exit is laid
+                    const uint64_t a = A[ia], b = B[ib];       // out with one more branch and the launch is 12 % slower
                     const bool lt = a < b, gt = b < a;
                     cnt += !(lt | gt);
                     ia += !gt;
@@ -199,12 +189,7 @@ __global__ __launch_bounds__(XT * XT) void compare_ext_kernel(
                     } else {
                         a = A[ia]; b = B[ib]; wa = (AbT)WA[ia]; wb = (AbT)WB[ib];
                     }
-                    const bool lt = a < b, gt = b < a, eq = !(lt | gt);
-                    // no branch: with 64 walks per wave some lane meets a common hash at almost every step anyway
-                    cnt += eq;
-                    acc += (unsigned long long)wa * (unsigned long long)(eq ? wb : (AbT)0);   // AbT = u32: select + one v_mad_u64_u32
-                    ia += !gt;
-                    ib += !lt;
+                    ext_abund_step<AbT>(a, b, wa, wb, &ia, &ib, &cnt, &acc);
                 }
             }
         }
@@ -273,11 +258,9 @@ __global__ __launch_bounds__(256) void num_jaccard_kernel(const uint32_t* __rest
     const uint32_t lo = i < j ? i : j;
     const uint64_t ni = offsets[i + 1] - offsets[i], nj = offsets[j + 1] - offsets[j];
     const uint64_t c = common[idx];
-    uint64_t u = ni + nj - c;
-    if (i == j) u = ni;
-    if (u > nums[lo]) u = nums[lo];
+    const uint64_t u = num_union_size(ni, nj, c, nums[lo], i == j);
     if (usize) usize[idx] = (uint32_t)u;
-    if (jaccard) jaccard[idx] = i == j ? 1.0 : (double)c / (double)(u > 1 ? u : 1);
+    if (jaccard) jaccard[idx] = i == j ? 1.0 : jaccard_of(c, u);
 }
 
 }  // namespace
@@ -326,10 +309,7 @@ hipError_t compare_abund_launch(const uint64_t* d_hashes, const uint64_t* d_abun
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(d_prod, 0, (size_t)n * n * 8, stream);
     if (e != hipSuccess) return e;
-    // slice length: tiles of ordinary sketches are cut as well when the grid is small -- a 1,000-sketch collection is 2,016 tiles
-    // on 1,536 resident workgroups (two rounds, the second a third full); three slices per tile fill the rounds (5.83 -> 5.47 ms at C3)
-    const uint32_t tiles = nt * (nt + 1) / 2;
-    uint32_t slice_len = tiles >= 16384 ? XSLICE : XSLICE_SMALL;
+    const uint32_t slice_len = cmp_ext_slice_len(nt * (nt + 1) / 2);
     if (narrow)
         hipLaunchKernelGGL((compare_ext_kernel<X_ABUND32>), dim3(nt, nt, XZMAX), dim3(XT * XT), 0, stream, d_hashes, d_abunds, d_offsets,
                            (const uint32_t*)nullptr, n, d_common, d_prod, slice_len);

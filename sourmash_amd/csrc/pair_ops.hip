@@ -20,17 +20,9 @@
 #include "pair_api.hpp"
 #include "qindex.hpp"
 #include "gather_api.hpp"
+#include "compare_core.hpp"
 
 namespace smg {
-
-__device__ __forceinline__ uint64_t lower_bound_dev(const uint64_t* __restrict__ a, uint64_t n, uint64_t x) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 // flags[i] = 1 iff A[i] in B; matchB[i] = index in B.  sums[0] += matches,
 // sums[1] += sum abundA[i]*abundB[j] over matches (if abundances given).
@@ -44,7 +36,7 @@ __global__ __launch_bounds__(256) void pair_match_kernel(const uint64_t* __restr
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < na;
          i += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t x = A[i];
-        const uint64_t j = lower_bound_dev(B, nb, x);
+        const uint64_t j = lower_bound_u64(B, 0ull, nb, x);
         const bool hit = j < nb && B[j] == x;
         if (flags) flags[i] = (hit != (invert != 0)) ? 1 : 0;
         if (hit) {
@@ -77,11 +69,7 @@ __global__ __launch_bounds__(1024) void pair_count_small_kernel(const uint64_t* 
     uint32_t cnt = 0;
     for (uint32_t i = threadIdx.x; i < na; i += 1024) {
         const uint64_t x = A[i];
-        uint32_t lo = 0, hi = nb;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (s_b[mid] < x) lo = mid + 1; else hi = mid;
-        }
+        const uint32_t lo = lower_bound_u64(s_b, 0u, nb, x);
         cnt += lo < nb && s_b[lo] == x;
     }
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
@@ -121,7 +109,7 @@ __global__ __launch_bounds__(256) void num_rank_kernel(const uint64_t* __restric
     unsigned long long cnt = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ni; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t x = I[i];
-        const uint64_t ra = lower_bound_dev(A, na, x) + 1, rb = lower_bound_dev(B, nb, x) + 1;  // x is in both
+        const uint64_t ra = lower_bound_u64(A, 0ull, na, x) + 1, rb = lower_bound_u64(B, 0ull, nb, x) + 1;  // x is in both
         const uint64_t rank_union = ra + rb - (i + 1);
         if (rank_union <= num) ++cnt;
     }
